@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""bench.py -- DMRG sweep throughput + dAC matvec TFLOP/s on MI355X (contract: see task brief).
+"""bench.py -- DMRG sweep throughput on MI355X (+ dAC matvec TFLOP/s and the secondary legs with --full).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is ONE full 1-site DMRG sweep (2L-2 site updates, dmrg.jl:33-38 of the reference) of
@@ -10,12 +10,16 @@ site, on a seeded synthetic uniform[0,1) random MPS that 
 left-canonical and resident in HBM when the timed region starts.  N > 1: the bond index is
 block-sharded over the ranks -- storage-sharded environments, one in-place RCCL all-gather per
 matvec, one all-reduce per left-environment update (strong scaling: the same chain on N GPUs).
-After the timed steps two more legs run on FRESH copies of the initial state psi0 (so that they
-do not depend on --steps): `early_sweeps` = sweeps 1-2 from psi0 with the same fixed budget (the
-gauge steps of unconverged tensors are worse conditioned: CholeskyQR retries are counted), and
-`to_tolerance` = sweeps 1..T from psi0 with the reference's default eigensolver
-Arnoldi(tol=1e-12, krylovdim=30, maxiter=100) (defaults.jl:33).  At N = 1 the oracle's CPU
-restatement is timed on the host cores (`cpu_baseline`).  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if
+--dump-outputs is given, and prints the result line (`value` sweeps/s, `ms_per_step`).
+--full adds everything else, measured after the timed steps: the per-kernel event profile of the
+timed sweeps (`roofline`) and their QR counters, the whole-matvec dAC rate, and two more legs on
+FRESH copies of the initial state psi0 (so that they do not depend on --steps): `early_sweeps` =
+sweeps 1-2 from psi0 with the same fixed budget (the gauge steps of unconverged tensors are worse
+conditioned: CholeskyQR retries are counted), and `to_tolerance` = sweeps 1..T from psi0 with the
+reference's default eigensolver Arnoldi(tol=1e-12, krylovdim=30, maxiter=100) (defaults.jl:33).
+At N = 1 the oracle's CPU restatement is timed on the host cores (`cpu_baseline`).  Rank 0 prints
+ONE JSON line.
 """
 import argparse
 import json
@@ -43,6 +47,28 @@ def kernel_source_hash():
         with open(os.path.join(ROOT, "mpskit.jl_amd", "csrc", f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(out_dir, psi, eps, per_site=32768, seed=20240213):
+    """Write what the last timed step handed its caller: the per-site galerkin errors dmrg_sweep returns
+    (`galerkin.npy`) and the state it leaves in mixed canonical form -- AL left of the centre, AC at the centre,
+    AR right of it (`mps_sample.npy`).  The site tensors are 1.6 GB at L=100, D=1024, so each one is sampled at
+    fixed seeded positions of its column-major storage (every entry of the small edge tensors); the samples of all
+    sites are concatenated in site order: at most L * per_site float64 values (26 MB at L=100)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "galerkin.npy"), np.asarray(eps, dtype=np.float64))
+    rng = np.random.default_rng(seed)
+    parts = []
+    for i in range(len(psi)):
+        t = next(a for a in (psi.ACs[i], psi.ALs[i], psi.ARs[i]) if a is not None)
+        flat = t.buf[: t.size]
+        if t.size > per_site:
+            idx = np.sort(rng.choice(t.size, per_site, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        parts.append(flat.double().cpu().numpy())
+    np.save(os.path.join(out_dir, "mps_sample.npy"), np.concatenate(parts))
 
 
 def cpu_baseline(L, D, d, matvecs, budget_s=24.0, min_samples=3):
@@ -144,14 +170,23 @@ def main():
     ap.add_argument("--L", type=int, default=100)
     ap.add_argument("--D", type=int, default=1024)
     ap.add_argument("--matvecs", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-tolerance-sweep", action="store_true", help="skip the converged-tolerance leg")
-    ap.add_argument("--tol-sweeps", type=int, default=2, help="sweeps of the converged-tolerance leg (from psi0)")
-    ap.add_argument("--early-sweeps", type=int, default=2, help="fixed-budget sweeps from psi0 reported as `early_sweeps`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the timed sweeps' kernel profile and QR counters, the dAC matvec rate, the "
+                         "early-sweep and converged-tolerance legs and the CPU baseline (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (galerkin errors, a seeded sample of the MPS tensors) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-tolerance-sweep", action="store_true", help="(--full) skip the converged-tolerance leg")
+    ap.add_argument("--tol-sweeps", type=int, default=2, help="(--full) sweeps of the converged-tolerance leg (from psi0)")
+    ap.add_argument("--early-sweeps", type=int, default=2,
+                    help="(--full) fixed-budget sweeps from psi0 reported as `early_sweeps`")
     ap.add_argument("--force-shard", action="store_true",
                     help="run the sharded sweep (blocked vectors, storage-sharded environments, RCCL collectives) even with "
                          "one rank: exercises the N > 1 code path on a 1-GPU box")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -213,9 +248,10 @@ def main():
 
     for _ in range(args.warmup):
         alg.dmrg_sweep(psi, H, envs, eig, ws)
-    be.prof_enable(True)
-    qr0 = be.qr_stats()
-    qr_retry0 = be.qr_retries()
+    if args.full:
+        be.prof_enable(True)
+        qr0 = be.qr_stats()
+        qr_retry0 = be.qr_retries()
     barrier()
     t0 = time.perf_counter()
     eps = None
@@ -223,18 +259,21 @@ def main():
         eps = alg.dmrg_sweep(psi, H, envs, eig, ws)
     barrier()
     dt = time.perf_counter() - t0
-    be.prof_enable(False)
-    qr_timed = {k: be.qr_stats()[k] - qr0[k] for k in qr0}
-    qr_timed["shift_retries"] = be.qr_retries() - qr_retry0
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=be.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    prof = be.prof_summary()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, psi, eps)
+    if args.full:
+        be.prof_enable(False)
+        qr_timed = {k: be.qr_stats()[k] - qr0[k] for k in qr0}
+        qr_timed["shift_retries"] = be.qr_retries() - qr_retry0
+        prof = be.prof_summary()
 
     # dominant kernel = the matvec-stage GEMM instance with the largest total time
     roofline = None
-    if prof:
+    if args.full and prof:
         top = max(prof, key=lambda r: r["total_ms"])
         achieved = top["flops"] / (top["total_ms"] * 1e-3) / 1e12
         roofline = {"bound": "mfma", "kernel": top["kernel"], "achieved": round(achieved, 3),
@@ -258,7 +297,7 @@ def main():
 
     # whole-matvec rate at the north-star point (D, d=2, W=5) on the same stream, HIP events
     dac_tflops = None
-    if rank == 0:
+    if args.full and rank == 0:
         GL = mk.DTensor(torch.rand(W * D * D, dtype=torch.float64, device=be.device), (W, D, D))
         GR = mk.DTensor(torch.rand(W * D * D, dtype=torch.float64, device=be.device), (W, D, D))
         x = mk.DTensor(torch.rand(D * d * D, dtype=torch.float64, device=be.device), (D, d, D))
@@ -295,7 +334,7 @@ def main():
     # early sweeps: the SAME fixed-budget sweep, but on sweeps 1..k from psi0 (the timed steps above run on the state
     # W + K sweeps have already converged; unconverged tensors make the gauge steps' Gram matrices worse conditioned)
     early = None
-    if args.early_sweeps > 0:
+    if args.full and args.early_sweeps > 0:
         p1 = psi0.copy()
         e1 = make_envs(p1)
         rows = []
@@ -320,7 +359,7 @@ def main():
     # (N = 1 only: a tolerance-mode solve takes data-dependent host decisions per Krylov step; the ranks of a sharded sweep
     #  hold bit-identical scalars by construction, but that lock-step has never met N > 1 on hardware -- the scaling runs
     #  time the fixed-budget sweeps, which have no data-dependent control flow)
-    if not args.no_tolerance_sweep and args.tol_sweeps > 0 and world == 1:
+    if args.full and not args.no_tolerance_sweep and args.tol_sweeps > 0 and world == 1:
         nmv = {"n": 0}
         orig_eig = krylov.eigsolve_sr
 
@@ -367,17 +406,20 @@ def main():
                        "parallelism": "single GPU" if not sharded else
                        f"bond index sharded x{world}: storage-sharded environments (1/{world} per GPU), one in-place RCCL "
                        "all-gather per matvec, one all-reduce per left-environment update, gauge steps replicated"},
-            "dAC_tflops": None if dac_tflops is None else round(dac_tflops, 3),
-            "dAC_frac_of_fp64_mfma_peak": None if dac_tflops is None else round(dac_tflops / FP64_MFMA_PEAK_TFLOPS, 4),
             "operator_applications_per_site": args.matvecs,       # the galerkin image reuses the eigensolver's first matvec
-            "early_sweeps": early,
-            "to_tolerance": to_tol,
             "max_galerkin_last_sweep": None if eps is None else float(max(eps)),
-            "qr_calls_timed": qr_timed,
-            "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(L, D, d, args.matvecs)
+        if args.full:
+            out.update({
+                "dAC_tflops": None if dac_tflops is None else round(dac_tflops, 3),
+                "dAC_frac_of_fp64_mfma_peak": None if dac_tflops is None else round(dac_tflops / FP64_MFMA_PEAK_TFLOPS, 4),
+                "early_sweeps": early,
+                "to_tolerance": to_tol,
+                "qr_calls_timed": qr_timed,
+                "roofline": roofline,
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(L, D, d, args.matvecs)
         print(json.dumps(out), flush=True)
     if world > 1 or args.force_shard:
         dist.destroy_process_group()

@@ -320,9 +320,13 @@ def split_two_site(be, theta: DTensor, trunc_dim=0, trunc_err=0.0, rng=None):
         be.copy2d(m2, r2, Qc.ptr, m2, B.ptr + 8 * m2 * lo, m2)
     Xs = be.upload(embed(rng.standard_normal((m2 // 2, K2 // 2)) + 1j * rng.standard_normal((m2 // 2, K2 // 2))))
     W = be.gemm(B, be.gemm(B, Xs, transA=True))
-    al, _ = be.qrpos(W)                                        # embedded orthonormal basis of the kept subspace
+    # embedded orthonormal basis of the kept subspace.  The plain QRpos is an embedding only as far as span(B) is invariant
+    # under J; a cut through a cluster takes its part of the cluster from a projection of random columns on the cluster
+    # vectors (Qc above), which magnifies their error (a degenerate pair at 192 x 160, k = 40: 2e-12), so the factors
+    # are made embeddings the way the gauge steps make them (no-op when they already are)
+    al, _ = qrpos_structured(be, W)
     M = be.gemm(al, th, transA=True)                           # K2 x n2
-    c, arm = be.lqpos(M)
+    c, arm = lqpos_structured(be, M)
     ar = be.empty(K2, d2, Dr2)
     for s2 in range(d2):                                       # arm[k, (b, s2)] -> ar[k, s2, b]
         be.copy2d(K2, Dr2, arm.ptr + 8 * s2 * K2 * Dr2, K2, ar.ptr + 8 * s2 * K2, K2 * d2)

@@ -23,13 +23,13 @@ if [ "$PART" = all ] || [ "$PART" = core ]; then
   for f in $(find $O/pmc_fetch -name "*counter_collection.csv" | head -1); do cp $f $O/${TAG}_pmc_fetch_size_dac_only.csv; done
   for f in $(find $O/pmc_write -name "*counter_collection.csv" | head -1); do cp $f $O/${TAG}_pmc_write_size_dac_only.csv; done
   for f in $(find $O/pmc_mfma -name "*counter_collection.csv" | head -1); do cp $f $O/${TAG}_pmc_mfma_busy_dac_only.csv; done
-  timeout -k 10 900 python bench.py > $O/bench_n1.log 2>&1 || { tail -5 $O/bench_n1.log; exit 3; }
+  timeout -k 10 900 python bench.py --full > $O/bench_n1.log 2>&1 || { tail -5 $O/bench_n1.log; exit 3; }
   tail -1 $O/bench_n1.log > $O/${TAG}_bench_n1.json; cut -c1-300 $O/${TAG}_bench_n1.json
   cd /tmp
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 $R/bench.py --no-cpu-baseline --no-tolerance-sweep > $O/prof_bench.log 2>&1 || exit 4
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 $R/bench.py --full --no-cpu-baseline --no-tolerance-sweep > $O/prof_bench.log 2>&1 || exit 4
   cd $R
   for f in $(find $O/prof_bench -name "*kernel_stats.csv" | head -1); do cp $f $O/${TAG}_kernel_stats.csv; done
-  timeout -k 10 300 python bench.py --steps 1 --warmup 1 --force-shard --no-cpu-baseline --no-tolerance-sweep > $O/${TAG}_bench_force_shard.json 2> $O/force_shard.err
+  timeout -k 10 300 python bench.py --steps 1 --warmup 1 --force-shard --full --no-cpu-baseline --no-tolerance-sweep > $O/${TAG}_bench_force_shard.json 2> $O/force_shard.err
 fi
 if [ "$PART" = all ] || [ "$PART" = configs ]; then
   timeout -k 10 300 python tools/bench_site.py > $O/${TAG}_site_breakdown.log 2>&1
@@ -39,7 +39,7 @@ if [ "$PART" = all ] || [ "$PART" = configs ]; then
   timeout -k 10 200 python tools/bench_cplx.py 128 256 512 1024 > $O/${TAG}_bench_cplx.log 2>&1
   (timeout -k 10 100 python tools/qr_only.py 2048 1024; timeout -k 10 100 python tools/qr_only.py 768 256; timeout -k 10 100 python tools/qr_only.py 4096 4096 3; timeout -k 10 200 python tools/qr_fallback_cost.py) > $O/${TAG}_qr_only.log 2>&1
   MPSK_BENCH_PROF=1 timeout -k 10 300 python tools/bench_dac.py 1024,2,5 2048,2,5 1024,4,6 256,3,5 512,2,3 > $O/${TAG}_bench_dac.log 2>&1
-  timeout -k 10 400 python bench.py --L 28 --D 4096 --steps 1 --warmup 1 --no-cpu-baseline --no-tolerance-sweep > $O/${TAG}_bench_D4096_L28.json 2>/dev/null
+  timeout -k 10 400 python bench.py --L 28 --D 4096 --steps 1 --warmup 1 --full --no-cpu-baseline --no-tolerance-sweep > $O/${TAG}_bench_D4096_L28.json 2>/dev/null
   cd /tmp
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c4 -- python3 $R/tools/bench_configs.py c4sweep:16:1024:1 > $O/prof_c4.log 2>&1
   cd $R

@@ -13,6 +13,6 @@ echo "== pytest new" > $O/s1_pytest.log
 timeout -k 10 900 python -m pytest tests/test_gpu_golden.py tests/test_gpu_traces.py "tests/test_gpu_ops.py" -x -q -m gpu >> $O/s1_pytest.log 2>&1
 echo "pytest rc=$?" >> $O/s1_pytest.log
 echo "== bench" > $O/s1_bench.log
-( time timeout -k 10 900 python bench.py --steps 2 --warmup 1 ) >> $O/s1_bench.log 2>&1
+( time timeout -k 10 900 python bench.py --steps 2 --warmup 1 --full ) >> $O/s1_bench.log 2>&1
 echo "bench rc=$?" >> $O/s1_bench.log
 tail -5 $O/s1_svd.log; tail -5 $O/s1_pytest.log; tail -3 $O/s1_bench.log

@@ -34,5 +34,5 @@ PY
 done
 cd $R
 echo "== bench to-tolerance with thick restart" > $O/s2_bench.log
-( time timeout -k 10 600 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --early-sweeps 0 ) >> $O/s2_bench.log 2>&1
+( time timeout -k 10 600 python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --early-sweeps 0 ) >> $O/s2_bench.log 2>&1
 cat $O/s2_dbg.log | grep -v amdgpu.ids | tail -30; cat $O/s2_trace.log
