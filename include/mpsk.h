@@ -165,6 +165,21 @@ int mpsk_dAC_blocked(mpsk_ctx* ctx, const mpsk_mposlice* H, int nblk, int Dlo, i
 typedef struct mpsk_hac mpsk_hac;
 int mpsk_hac_create(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
                     mpsk_hac** out);
+/* mpsk_hac_create with flags.  MPSK_HAC_CANONICAL: the caller guarantees that level 0 of GL and level W-1 of GR are
+ * identities -- true for the environments of a finite chain in canonical form (FinEnv starts them as identities and
+ * every update with an isometric AL / AR keeps them so, to the isometry error of the gauge step).  For a real slice in
+ * Jordan form (levels 0 and W-1 of chi 1, O[0,0] = O[W-1,W-1] = 1, O[w,v] = 0 for w > 0, v < W-1: nothing enters level
+ * 0, nothing leaves level W-1, no A blocks) and Dlo == Dl the operator is then prepared in mode 3:
+ *   y[:,t,:] = sum_s x[:,s,:] GRc0[(s,t)] + sum_s GLc[(s,t)] x[:,s,:],
+ *   GRc0[(s,t)] = sum_v O[0,t,s,v] GR[v]  (start level, C blocks, D block),  GLc[(s,t)] = sum_{w>0} O[w,t,s,W-1] GL[w],
+ * both folded once at create time; an application is ONE GEMM launch (two when Dl != Dr) with no intermediate:
+ * 2 d n D^3 flops (n = non-zero (s,t) slabs per t and family; Heisenberg: 16 D^3 against the 40 D^3 of mode 1).
+ * Slices with A blocks (longer-range MPOs), complex slices and every other case keep the mode mpsk_hac_create picks.
+ * Environment MPSK_HAC_CHECK=1 (debug, synchronises): a mode-3 candidate whose max|GL[0] - I| or max|GR[W-1] - I|
+ * exceeds 1e-10 fails with MPSK_ERR_INVALID.  mpsk_hac_info: mode 3, nslabs = folded slabs (2 d^2). */
+enum { MPSK_HAC_CANONICAL = 1 };
+int mpsk_hac_create_ex(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
+                       int flags, mpsk_hac** out);
 int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y);
 /* Fixed-budget smallest-real eigensolve with the prepared operator in ONE call: V[0] = x0 / |x0|, m Krylov steps (apply,
  * CGS2 + normalise), Ritz step of the projected matrix on the device, y = normalised Ritz vector -- fixedpoint(H_AC, AC, :SR,

@@ -252,6 +252,11 @@ class Backend:
         keeps GL / GR alive and releases the device-side object when it is garbage collected."""
         return PreparedHAC(self, H, GL, GR)
 
+    def hac_create_ex(self, H, GL: DTensor, GR: DTensor, canonical: bool = False):
+        """mpsk_hac_create_ex: as hac_create; canonical=True promises that level 0 of GL and level W-1 of GR are
+        identities (MPSK_HAC_CANONICAL), which lets a real Jordan-form slice take the 16 D^3 operator (mode 3)."""
+        return PreparedHAC(self, H, GL, GR, flags=1 if canonical else 0)
+
     def dC(self, GL: DTensor, GR: DTensor, c: DTensor, out: DTensor = None, cplx=False):
         if cplx:
             Dl2, Dr = c.shape
@@ -688,7 +693,7 @@ class Backend:
 class PreparedHAC:
     """Owner of an mpsk_hac handle (include/mpsk.h): `apply(x, out, nblk)` is one matvec."""
 
-    def __init__(self, be: Backend, H, GL: DTensor, GR: DTensor):
+    def __init__(self, be: Backend, H, GL: DTensor, GR: DTensor, flags: int = 0):
         Wl, Dlo, Dl = GL.shape
         Wr, Dr2, Dr = GR.shape
         self.cplx = bool(getattr(H, "cplx", False))
@@ -698,7 +703,11 @@ class PreparedHAC:
         self.be, self.H, self.GL, self.GR = be, H, GL, GR           # references keep the operands alive
         self.Dlo, self.Dl, self.Dr, self.d = Dlo, Dl, Dr, H.d
         h = C.c_void_p()
-        check(be.lib.mpsk_hac_create(be.ctx, H.handle, Dlo, Dl, Dr, GL.ptr, GR.ptr, C.byref(h)), "mpsk_hac_create")
+        if flags:
+            check(be.lib.mpsk_hac_create_ex(be.ctx, H.handle, Dlo, Dl, Dr, GL.ptr, GR.ptr, int(flags), C.byref(h)),
+                  "mpsk_hac_create_ex")
+        else:
+            check(be.lib.mpsk_hac_create(be.ctx, H.handle, Dlo, Dl, Dr, GL.ptr, GR.ptr, C.byref(h)), "mpsk_hac_create")
         self.handle = h
 
     def info(self):

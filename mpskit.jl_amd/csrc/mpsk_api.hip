@@ -45,6 +45,18 @@ struct mpsk_mposlice {
   MixPlan rc;                      // out slab c <- in slab v
   std::vector<int> rc_w, rc_s, rc_t;
   int rc_nseg = 0;                 // max over t of the number of c with t_c = t (lists are padded to this length)
+  // Jordan form (mpsk_hac mode 3, real slices): levels 0 and W-1 have chi = 1, O[0,0] = O[W-1,W-1] = 1 and
+  // O[w,v] = 0 for every w > 0, v < W-1 (nothing enters level 0, nothing leaves level W-1, no A blocks).  With level 0
+  // of GL and level W-1 of GR identities (canonical environments) the matvec is then
+  //   y[:,t,:] = sum_s x[:,s,:] GRc0[(s,t)] + sum_s GLc[(s,t)] x[:,s,:],
+  //   GRc0[(s,t)] = sum_v O[0,t,s,v] GR[v]   (start level + C blocks + D block),
+  //   GLc[(s,t)]  = sum_{w>0} O[w,t,s,W-1] GL[w]   (B blocks + finished level).
+  // Slab p = s + d t of both folds; jr_p / jl_p [d][nseg]: per t the slabs p with terms, padded to jr_nseg / jl_nseg
+  // with an empty slab of the same family (the fold writes zeros there).
+  bool jordan = false;
+  MixPlan jr, jl;                  // out slab p <- in slab v of GR / w of GL
+  std::vector<int> jr_p, jl_p;
+  int jr_nseg = 0, jl_nseg = 0;
   double O(int w, int t, int s, int v) const { return Ofull[w + (size_t)Wl * (t + d * (s + (size_t)d * v))]; }
 };
 
@@ -110,9 +122,13 @@ struct mpsk_hac {
   int Dlo, Dl, Dr;
   const double* GL;
   const double* GR;
-  int mode;                     // 0: GEMM -> slab mix -> GEMM (mpsk_dAC);  1: right-combined environment, no mix
-  double* GRc = nullptr;        // [nc + 1][Dr, Dr]   (last slab: zeros, pads the shorter segment lists)
-  int64_t* zseg = nullptr;      // device [2][d][nseg]: A offsets (into T1), B offsets (into GRc)
+  int mode;                     // 0: GEMM -> slab mix -> GEMM (mpsk_dAC);  1: right-combined environment, no mix;
+                                // 2: complex128;  3: Jordan form on canonical environments (one GEMM, no intermediate)
+  double* GRc = nullptr;        // mode 1: [nc + 1][Dr, Dr] (last slab: zeros, pads the shorter segment lists)
+                                // mode 3: GRc0, per t a [Dr, d, Dr] tensor (slab (s, t) = its plane s)
+  double* GLc = nullptr;        // mode 3: per t a [Dlo, d, Dl] tensor (slab (s, t) = its plane s)
+  int launches = 1;             // mode 3: 1 = both families in one launch (Dl == Dr), 2 = x GRc0, then GLc x with beta = 1
+  int64_t* zseg = nullptr;      // device [2][d][nseg]: A offsets (into T1), B offsets (into GRc); mode 3: see hac_jordan_prepare
   std::vector<int64_t> zseg_host;   // source of the asynchronous upload of zseg: lives as long as the handle (no sync)
   hipEvent_t ev_up = nullptr;       // completion of that upload (waited for before the handle is freed)
   int pool_idx = -1;
@@ -381,6 +397,48 @@ int mpsk_mposlice_create(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l,
     for (int t = 0; t < d; ++t) if (per_t[t] > s->rc_nseg) s->rc_nseg = per_t[t];
     HIPCHK(mix_plan_create(rc, (int)s->rc_w.size(), s->Wr, &s->rc));
   }
+  if (!cx && odim >= 2 && chi_l[0] == 1 && chi_r[0] == 1 && chi_l[odim - 1] == 1 && chi_r[odim - 1] == 1) {
+    const int Wl = s->Wl, Wr = s->Wr;
+    bool ok = true;
+    for (int t = 0; t < d && ok; ++t)
+      for (int si = 0; si < d && ok; ++si) {
+        ok = s->O(0, t, si, 0) == (t == si ? 1.0 : 0.0) && s->O(Wl - 1, t, si, Wr - 1) == (t == si ? 1.0 : 0.0);
+        for (int v = 0; v < Wr - 1 && ok; ++v)
+          for (int w = 1; w < Wl && ok; ++w) ok = s->O(w, t, si, v) == 0.0;
+      }
+    if (ok) {
+      std::vector<MixTerm> jr, jl;
+      std::vector<char> r_used(d * d, 0), l_used(d * d, 0);
+      for (int t = 0; t < d; ++t)
+        for (int si = 0; si < d; ++si) {
+          const int p = si + d * t;
+          for (int v = 0; v < Wr; ++v)
+            if (s->O(0, t, si, v) != 0.0) { jr.push_back({p, v, s->O(0, t, si, v)}); r_used[p] = 1; }
+          for (int w = 1; w < Wl; ++w)
+            if (s->O(w, t, si, Wr - 1) != 0.0) { jl.push_back({p, w, s->O(w, t, si, Wr - 1)}); l_used[p] = 1; }
+        }
+      // per-t slab lists, padded with an empty slab of the family (one exists whenever a list is shorter than the longest)
+      auto lists = [&](const std::vector<char>& used, std::vector<int>& out, int& nseg) {
+        int empty = -1;
+        for (int p = 0; p < d * d; ++p) if (!used[p]) { empty = p; break; }
+        for (int t = 0; t < d; ++t) {
+          int n = 0;
+          for (int si = 0; si < d; ++si) n += used[si + d * t];
+          nseg = std::max(nseg, n);
+        }
+        out.assign((size_t)d * nseg, empty);
+        for (int t = 0; t < d; ++t) {
+          int k = 0;
+          for (int si = 0; si < d; ++si) if (used[si + d * t]) out[(size_t)t * nseg + k++] = si + d * t;
+        }
+      };
+      lists(r_used, s->jr_p, s->jr_nseg);
+      lists(l_used, s->jl_p, s->jl_nseg);
+      HIPCHK(mix_plan_create(jr, d * d, Wr, &s->jr));
+      HIPCHK(mix_plan_create(jl, d * d, Wl, &s->jl));
+      s->jordan = s->jr_nseg > 0 && s->jl_nseg > 0;
+    }
+  }
   *out = s;
   return MPSK_OK;
 }
@@ -398,6 +456,8 @@ int mpsk_mposlice_destroy(mpsk_mposlice* s) {
   mix_plan_destroy(&s->bwd);
   mix_plan_destroy(&s->rgt);
   mix_plan_destroy(&s->rc);
+  mix_plan_destroy(&s->jr);
+  mix_plan_destroy(&s->jl);
   delete s;
   return MPSK_OK;
 }
@@ -712,9 +772,65 @@ static int pool_take(mpsk_ctx* c, size_t bytes, void** p, int* idx) {
   return MPSK_OK;
 }
 
+// max |G - I| of one n x n environment slab (MPSK_HAC_CHECK: a debug mode, it synchronises)
+static int identity_deviation(mpsk_ctx* c, const double* G, int n, double* dev) {
+  std::vector<double> h((size_t)n * n);
+  HIPCHK(hipMemcpyAsync(h.data(), G, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  double m = 0.0;
+  for (int j = 0; j < n; ++j)
+    for (int i = 0; i < n; ++i) m = std::max(m, std::fabs(h[i + (size_t)n * j] - (i == j ? 1.0 : 0.0)));
+  *dev = m;
+  return MPSK_OK;
+}
+
+// mode 3 (Jordan form): fold GRc0 / GLc into the pool buffer and upload the per-batch segment tables, on the ctx stream.
+// Tables (element offsets), one launch: A[d][n1 + n2], B[d][n1 + n2] -- segments k < n1 relative to (x, GRc0), the others
+// to (GLc, x); two launches: A1[d][n1], B1[d][n1], A2[d][n2], B2[d][n2].
+static hipError_t hac_jordan_prepare(mpsk_ctx* c, mpsk_hac* h, const double* GL, const double* GR) {
+  const mpsk_mposlice* H = h->H;
+  const int d = H->d, n1 = H->jr_nseg, n2 = H->jl_nseg;
+  const int Dlo = h->Dlo, Dl = h->Dl, Dr = h->Dr;
+  const int64_t tR = (int64_t)Dr * d * Dr, tL = (int64_t)Dlo * d * Dl;     // one t-group of GRc0 / GLc
+  // GRc0[(s,t)] = sum_v O[0,t,s,v] GR[v] ;  GLc[(s,t)] = sum_{w>0} O[w,t,s,W-1] GL[w]   (slab p = s + d t)
+  SlabIndex ir{1 << 30, 1, (int64_t)Dr * Dr, 0, 0, (int64_t)Dr}, orr{d, 1 << 30, (int64_t)Dr, tR, 0, (int64_t)d * Dr};
+  SlabIndex il{1 << 30, 1, (int64_t)Dlo * Dl, 0, 0, (int64_t)Dlo}, ol{d, 1 << 30, (int64_t)Dlo, tL, 0, (int64_t)d * Dlo};
+  hipError_t e = mix_apply(H->jr, GR, ir, h->GRc, orr, Dr, Dr, c->stream);
+  if (e == hipSuccess) e = mix_apply(H->jl, GL, il, h->GLc, ol, Dlo, Dl, c->stream);
+  if (e != hipSuccess) return e;
+  const int n = n1 + n2;
+  h->zseg_host.assign((size_t)2 * d * n, 0);
+  int64_t* tab = h->zseg_host.data();
+  int64_t *a1 = tab, *b1 = tab + (size_t)d * n, *a2 = tab + n1, *b2 = tab + (size_t)d * n + n1;
+  int64_t st1 = n, st2 = n;
+  if (h->launches == 2) { b1 = tab + (size_t)d * n1; a2 = tab + (size_t)2 * d * n1; b2 = a2 + (size_t)d * n2; st1 = n1; st2 = n2; }
+  for (int t = 0; t < d; ++t) {
+    for (int k = 0; k < n1; ++k) {
+      const int p = H->jr_p[(size_t)t * n1 + k], si = p % d, tt = p / d;
+      a1[t * st1 + k] = (int64_t)si * Dl;                               // x[:, s, :]
+      b1[t * st1 + k] = tt * tR + (int64_t)si * Dr;                     // GRc0[(s, tt)]
+    }
+    for (int k = 0; k < n2; ++k) {
+      const int p = H->jl_p[(size_t)t * n2 + k], si = p % d, tt = p / d;
+      a2[t * st2 + k] = tt * tL + (int64_t)si * Dlo;                    // GLc[(s, tt)]
+      b2[t * st2 + k] = (int64_t)si * Dl;                               // x[:, s, :]
+    }
+  }
+  e = hipMemcpyAsync(h->zseg, tab, sizeof(int64_t) * h->zseg_host.size(), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_up, hipEventDisableTiming | hipEventDisableSystemFence);
+  if (e == hipSuccess) e = hipEventRecord(h->ev_up, c->stream);
+  return e;
+}
+
 int mpsk_hac_create(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
                     mpsk_hac** out) {
+  return mpsk_hac_create_ex(c, H, Dlo, Dl, Dr, GL, GR, 0, out);
+}
+
+int mpsk_hac_create_ex(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
+                       int flags, mpsk_hac** out) {
   REQUIRE(c && H && GL && GR && out, "NULL argument");
+  REQUIRE((flags & ~MPSK_HAC_CANONICAL) == 0, "unknown flags");
   REQUIRE(Dlo > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
@@ -729,8 +845,23 @@ int mpsk_hac_create(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   const double t_rc = (double)H->rc_nseg * d * u3 / 50e12;
   auto* h = new mpsk_hac();
   h->ctx = c; h->H = H; h->Dlo = Dlo; h->Dl = Dl; h->Dr = Dr; h->GL = (const double*)GL; h->GR = (const double*)GR;
-  h->mode = (H->rc_nseg > 0 && t_rc <= t_mix) ? 1 : 0;
-  if (const char* ev = getenv("MPSK_HAC_MODE")) h->mode = (ev[0] == '1' && H->rc_nseg > 0) ? 1 : 0;
+  // Jordan form: only on the caller's promise that level 0 of GL and level W-1 of GR are identities
+  const bool jordan = (flags & MPSK_HAC_CANONICAL) && H->jordan && H->dtype == MPSK_F64 && Dlo == Dl;
+  if (jordan && getenv("MPSK_HAC_CHECK") && getenv("MPSK_HAC_CHECK")[0] == '1') {
+    double dl = 0.0, dr = 0.0;
+    int rc = identity_deviation(c, (const double*)GL, Dl, &dl);
+    if (!rc) rc = identity_deviation(c, (const double*)GR + (size_t)(Wr - 1) * Dr * Dr, Dr, &dr);
+    if (rc) { delete h; return rc; }
+    if (!(dl <= 1e-10 && dr <= 1e-10)) {
+      delete h;
+      char msg[160];
+      snprintf(msg, sizeof(msg), "MPSK_HAC_CHECK: environments are not canonical (max|GL[0] - I| = %.3e, max|GR[W-1] - I| = %.3e)", dl, dr);
+      return fail(MPSK_ERR_INVALID, msg);
+    }
+  }
+  h->mode = jordan ? 3 : (H->rc_nseg > 0 && t_rc <= t_mix) ? 1 : 0;
+  if (const char* ev = getenv("MPSK_HAC_MODE"))
+    h->mode = (ev[0] == '3' && jordan) ? 3 : (ev[0] == '1' && H->rc_nseg > 0) ? 1 : 0;
   if (H->dtype == MPSK_C128) {
     // complex128: mix form; what is prepared once per site is the planar copy of the right environment (the B operand
     // of stage 3), so that an application converts only x
@@ -747,6 +878,26 @@ int mpsk_hac_create(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
     }
     *out = h;
     return MPSK_OK;
+  }
+  if (h->mode == 3) {
+    // one launch when both operand families share lda / ldb / K (Dl == Dr: the bulk of a chain); MPSK_HAC_LAUNCHES=2
+    // forces the two-launch form (A/B switch)
+    const char* ev = getenv("MPSK_HAC_LAUNCHES");
+    h->launches = (Dl == Dr && !(ev && ev[0] == '2')) ? 1 : 2;
+    auto up = [](size_t n) { return (n + 31) & ~(size_t)31; };      // 256-B aligned parts
+    const size_t nR = up((size_t)d * d * Dr * Dr), nL = up((size_t)d * d * Dlo * Dl);
+    const size_t bytes = sizeof(double) * (nR + nL) + sizeof(int64_t) * 2 * d * (H->jr_nseg + H->jl_nseg);
+    void* buf = nullptr;
+    if (int rc = pool_take(c, bytes, &buf, &h->pool_idx)) { delete h; return rc; }
+    h->GRc = (double*)buf;
+    h->GLc = h->GRc + nR;
+    h->zseg = (int64_t*)(h->GLc + nL);
+    hipError_t e = hac_jordan_prepare(c, h, (const double*)GL, (const double*)GR);
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(c->stream);
+      if (h->ev_up) (void)hipEventDestroy(h->ev_up);
+      c->pool[h->pool_idx].used = false; delete h; return fail(MPSK_ERR_HIP, hipGetErrorString(e));
+    }
   }
   if (h->mode == 1) {
     const int nc = (int)H->rc_w.size(), ns = H->rc_nseg;
@@ -801,7 +952,7 @@ int mpsk_hac_destroy(mpsk_hac* h) {
 int mpsk_hac_info(const mpsk_hac* h, int* mode, int* nslabs) {
   REQUIRE(h, "hac is NULL");
   if (mode) *mode = h->mode;
-  if (nslabs) *nslabs = h->mode == 1 ? (int)h->H->rc_w.size() : 0;
+  if (nslabs) *nslabs = h->mode == 1 ? (int)h->H->rc_w.size() : h->mode == 3 ? h->H->jr.n_out + h->H->jl.n_out : 0;
   return MPSK_OK;
 }
 
@@ -817,6 +968,32 @@ int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
   }
   if (h->mode == 0) return dAC_impl(c, H, Dlo, Dl, Dr, h->GL, h->GR, x, nblk, y);
   HIPCHK(hipSetDevice(c->device));
+  if (h->mode == 3) {
+    // y[:, t, :] = sum_k x[:, s_k, :] GRc0[(s_k, t)] + sum_k GLc[(s_k, t)] x[:, s_k, :]     (batch over t)
+    if (nblk != 1) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_hac_apply: the Jordan-form operator takes the plain vector layout only");
+    const int d = H->d, n1 = H->jr_nseg, n2 = H->jl_nseg;
+    const bool even = Dlo % 2 == 0 && Dl % 2 == 0 && Dr % 2 == 0;
+    GemmArgs g = mk((const double*)x, h->GRc, (double*)y, Dlo, Dr, Dr, (int64_t)Dl * d, (int64_t)Dr * d, (int64_t)Dlo * d);
+    g.batch = d; g.bsA = 0; g.bsB = 0; g.bsC = (int64_t)Dlo;
+    g.tabs_even = even;
+    g.tag = 1;
+    if (h->launches == 1) {        // Dl == Dr: the (GLc, x) family has the same lda / ldb / K
+      g.A2 = h->GLc; g.B2 = (const double*)x; g.nseg1 = n1;
+      g.nseg = n1 + n2; g.zsegA = h->zseg; g.zsegB = h->zseg + (size_t)d * (n1 + n2);
+      HIPCHK(gemm_f64(g, c->stream));
+      return MPSK_OK;
+    }
+    g.nseg = n1; g.zsegA = h->zseg; g.zsegB = h->zseg + (size_t)d * n1;
+    HIPCHK(gemm_f64(g, c->stream));
+    GemmArgs g2 = mk(h->GLc, (const double*)x, (double*)y, Dlo, Dr, Dl, (int64_t)Dlo * d, (int64_t)Dl * d, (int64_t)Dlo * d);
+    g2.batch = d; g2.bsA = 0; g2.bsB = 0; g2.bsC = (int64_t)Dlo;
+    g2.beta = 1.0;
+    g2.tabs_even = even;
+    g2.tag = 1;
+    g2.nseg = n2; g2.zsegA = h->zseg + (size_t)2 * d * n1; g2.zsegB = g2.zsegA + (size_t)d * n2;
+    HIPCHK(gemm_f64(g2, c->stream));
+    return MPSK_OK;
+  }
   const int d = H->d, Wl = H->Wl, ns = H->rc_nseg;
   const size_t slab = (size_t)Dlo * d * Dr;
   if (int rc = ensure_ws(c, sizeof(double) * slab * Wl)) return rc;

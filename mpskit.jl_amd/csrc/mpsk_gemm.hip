@@ -164,13 +164,19 @@ __device__ __forceinline__ void gemm_accumulate(const GemmArgs& g, const double*
   LA la; LB lb;
   int seg = ktb / tps, kt = ktb % tps;
   // K-segment offsets: from the argument block, or (ZS, compile time: a run-time choice cost the plain kernels 30 %)
-  // per batch from device tables -- uniform scalar loads
+  // per batch from device tables -- uniform scalar loads, segments from nseg1 on relative to the second bases A2 / B2
   const int64_t* const zsa = ZS ? g.zsegA + (int64_t)z * g.nseg : nullptr;
   const int64_t* const zsb = ZS ? g.zsegB + (int64_t)z * g.nseg : nullptr;
-  auto offA = [&](int sg) -> int64_t { if constexpr (ZS) return uniform_load_i64(zsa + sg); else return g.segA[sg]; };
-  auto offB = [&](int sg) -> int64_t { if constexpr (ZS) return uniform_load_i64(zsb + sg); else return g.segB[sg]; };
-  la.load(Ab + offA(seg), g.lda, m0, kt * BK, g.M, g.K, tid);
-  lb.load(Bb + offB(seg), g.ldb, n0, kt * BK, g.N, g.K, tid);
+  const double* const Ab2 = ZS ? g.A2 + (Ab - g.A) : Ab;
+  const double* const Bb2 = ZS ? g.B2 + (Bb - g.B) : Bb;
+  auto ptrA = [&](int sg) -> const double* {
+    if constexpr (ZS) return (sg < g.nseg1 ? Ab : Ab2) + uniform_load_i64(zsa + sg); else return Ab + g.segA[sg];
+  };
+  auto ptrB = [&](int sg) -> const double* {
+    if constexpr (ZS) return (sg < g.nseg1 ? Bb : Bb2) + uniform_load_i64(zsb + sg); else return Bb + g.segB[sg];
+  };
+  la.load(ptrA(seg), g.lda, m0, kt * BK, g.M, g.K, tid);
+  lb.load(ptrB(seg), g.ldb, n0, kt * BK, g.N, g.K, tid);
   la.store(sA, tid, CJ ? (int)g.segJ[seg] : 0);
   lb.store(sB, tid);
   __syncthreads();
@@ -179,8 +185,8 @@ __device__ __forceinline__ void gemm_accumulate(const GemmArgs& g, const double*
     int kt2 = kt + 1, seg2 = seg;
     if (kt2 == tps) { kt2 = 0; seg2 = seg + 1; }
     if (t + 1 < kte) {
-      la.load(Ab + offA(seg2), g.lda, m0, kt2 * BK, g.M, g.K, tid);
-      lb.load(Bb + offB(seg2), g.ldb, n0, kt2 * BK, g.N, g.K, tid);
+      la.load(ptrA(seg2), g.lda, m0, kt2 * BK, g.M, g.K, tid);
+      lb.load(ptrB(seg2), g.ldb, n0, kt2 * BK, g.N, g.K, tid);
     }
     const double* a_s = sA + cur * IA::SIZE;
     const double* b_s = sB + cur * IB::SIZE;
@@ -289,13 +295,19 @@ __device__ __forceinline__ void gemm_accumulate_pf2(const GemmArgs& g, const dou
   const int tps = (g.K + BK - 1) / BK;
   const int64_t* const zsa = ZS ? g.zsegA + (int64_t)z * g.nseg : nullptr;
   const int64_t* const zsb = ZS ? g.zsegB + (int64_t)z * g.nseg : nullptr;
-  auto offA = [&](int sg) -> int64_t { if constexpr (ZS) return uniform_load_i64(zsa + sg); else return g.segA[sg]; };
-  auto offB = [&](int sg) -> int64_t { if constexpr (ZS) return uniform_load_i64(zsb + sg); else return g.segB[sg]; };
+  const double* const Ab2 = ZS ? g.A2 + (Ab - g.A) : Ab;
+  const double* const Bb2 = ZS ? g.B2 + (Bb - g.B) : Bb;
+  auto ptrA = [&](int sg) -> const double* {
+    if constexpr (ZS) return (sg < g.nseg1 ? Ab : Ab2) + uniform_load_i64(zsa + sg); else return Ab + g.segA[sg];
+  };
+  auto ptrB = [&](int sg) -> const double* {
+    if constexpr (ZS) return (sg < g.nseg1 ? Bb : Bb2) + uniform_load_i64(zsb + sg); else return Bb + g.segB[sg];
+  };
   LA la0, la1; LB lb0, lb1;
   int jf0 = 0, jf1 = 0;
   int segL = ktb / tps, ktL = ktb % tps;          // the next k-tile to be requested from memory
-  const double* pa = Ab + offA(segL);             // segment bases: looked up when the segment changes, not per k-tile
-  const double* pb = Bb + offB(segL);
+  const double* pa = ptrA(segL);                  // segment bases: looked up when the segment changes, not per k-tile
+  const double* pb = ptrB(segL);
   int jfL = CJ ? (int)g.segJ[segL] : 0;
   auto issue = [&](LA& a, LB& b, int& jf) {
     a.load(pa, g.lda, m0, ktL * BK, g.M, g.K, tid);
@@ -304,7 +316,7 @@ __device__ __forceinline__ void gemm_accumulate_pf2(const GemmArgs& g, const dou
     if (++ktL == tps) {
       ktL = 0; ++segL;
       if (segL * tps < kte) {                     // (uniform; scalar loads only: the vmcnt bookkeeping of the two paths agrees)
-        pa = Ab + offA(segL); pb = Bb + offB(segL);
+        pa = ptrA(segL); pb = ptrB(segL);
         if (CJ) jfL = (int)g.segJ[segL];
       }
     }
@@ -881,6 +893,8 @@ hipError_t gemm_f64(const GemmArgs& g_in, hipStream_t s) {
   if (g.K <= 0 || g.nseg <= 0) {  // pure scaling C = beta*C is not needed by any caller
     return hipErrorInvalidValue;
   }
+  if (!g.A2 && !g.B2) { g.A2 = g.A; g.B2 = g.B; g.nseg1 = g.nseg; }
+  else if (!g.A2 || !g.B2 || !g.zsegA || !g.zsegB || g.nseg1 < 0 || g.nseg1 > g.nseg) return hipErrorInvalidValue;
   int bm = 128, bn = 128;
   choose_tile(g.M, g.N, g.K * g.nseg, g.batch, &bm, &bn);
   g.sk_units = 0;
@@ -964,6 +978,7 @@ hipError_t gemm_f64(const GemmArgs& g_in, hipStream_t s) {
   bool aligned = (g.M % bm == 0) && (g.N % bn == 0) && (g.K % BK == 0) && (g.lda % 2 == 0) &&
                  (g.ldb % 2 == 0) && (g.bsA % 2 == 0) && (g.bsB % 2 == 0) &&
                  ((uintptr_t)g.A % 16 == 0) && ((uintptr_t)g.B % 16 == 0) &&
+                 ((uintptr_t)g.A2 % 16 == 0) && ((uintptr_t)g.B2 % 16 == 0) &&
                  g.lda < ((int64_t)1 << 21) && g.ldb < ((int64_t)1 << 21);   // 32-bit per-thread byte offsets
   if (g.tabA || g.tabB || g.zsegA || g.zsegB) aligned = aligned && g.tabs_even;
   if (!g.zsegA) for (int i = 0; i < g.nseg && i < MAXSEG; ++i) aligned = aligned && (g.segA[i] % 2 == 0);

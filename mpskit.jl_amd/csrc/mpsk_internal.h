@@ -56,6 +56,13 @@ struct GemmArgs {
   // A + tabA/bsA offset + zsegA[z * nseg + i] (override segA / segB when set; nseg is uniform over the batches)
   const int64_t* zsegA;
   const int64_t* zsegB;
+  // second operand family of a per-batch-table launch: segments i >= nseg1 read A2 / B2 (plus the batch offset of A / B)
+  // instead of A / B, with the same lda / ldb / K.  The Jordan-form matvec (mpsk_hac mode 3) sums x GRc0 and GLc x in
+  // one launch this way while its tables stay relative to their own bases (x changes every Krylov step, they do not).
+  // A2 / B2 null: one family (gemm_f64 sets A2 = A, B2 = B, nseg1 = nseg).
+  const double* A2;
+  const double* B2;
+  int nseg1;
   // complex128 operands carried as REAL matrices with (re, im) interleaved along the first (row) index of the A operand
   // and of C ("half-embedded" real view of TensorKit's interleaved complex storage), B planar (separate re / im planes):
   //   C_half = A_half Br + (J A_half) Bi,   J (re, im) = (-im, re)  -- the multiplication by i on a row pair.

@@ -21,16 +21,25 @@ class MPO_ddAC:  # MPO_∂∂AC  derivatives.jl:11-15
     operator (mpsk_hac_create: MPO tensor folded into the right environment where that saves the slab mix), every
     application is then mpsk_hac_apply."""
 
-    def __init__(self, be, o, leftenv, rightenv):
+    def __init__(self, be, o, leftenv, rightenv, canonical=False):
         self.be, self.o, self.leftenv, self.rightenv = be, o, leftenv, rightenv
+        # canonical: level 0 of leftenv and level W-1 of rightenv are identities (environments of a finite chain in
+        # canonical form), which lets a Jordan-form slice skip the identity products (mpsk_hac_create_ex, mode 3)
+        self.canonical = bool(canonical)
         self._hac = None
+
+    def _prepare(self):
+        if self._hac is None:
+            if self.canonical and hasattr(self.be, "hac_create_ex"):
+                self._hac = self.be.hac_create_ex(self.o, self.leftenv, self.rightenv, canonical=True)
+            else:
+                self._hac = self.be.hac_create(self.o, self.leftenv, self.rightenv)
+        return self._hac
 
     def __call__(self, x: DTensor, out: DTensor = None):
         if not hasattr(self.be, "hac_create"):                   # host stand-in backend of the CPU tests
             return self.be.dAC(self.o, self.leftenv, self.rightenv, x, out=out)
-        if self._hac is None:
-            self._hac = self.be.hac_create(self.o, self.leftenv, self.rightenv)
-        return self._hac.apply(x, out=out)
+        return self._prepare().apply(x, out=out)
 
     __mul__ = __call__
 
@@ -39,8 +48,7 @@ class MPO_ddAC:  # MPO_∂∂AC  derivatives.jl:11-15
         (host stand-in backend, complex operator)."""
         if not hasattr(self.be, "hac_create"):
             return None
-        if self._hac is None:
-            self._hac = self.be.hac_create(self.o, self.leftenv, self.rightenv)
+        self._prepare()
         if self._hac.cplx or self._hac.Dlo != self._hac.Dl:
             return None
         return self._hac.eigsolve_fixed(x0, m, vecs, scal, out, first_image)
@@ -72,7 +80,8 @@ class LazyDerivativeSum:  # derivatives.jl:310-323 : (h::LazySum{<:DerivativeOpe
 
 
 def _lazy(fn, pos, psi, H, envs):
-    op = LazyDerivativeSum(psi.be, [fn(pos, psi, h, e) for h, e in zip(H, envs.envs)], H.fs)
+    kw = {"canonical": False} if fn is ddAC else {}          # the terms of a sum keep the dense operator
+    op = LazyDerivativeSum(psi.be, [fn(pos, psi, h, e, **kw) for h, e in zip(H, envs.envs)], H.fs)
     if getattr(psi, "cplx", False) and any(hasattr(e, "vector") for e in envs.envs):
         # a projector term exists in the embedded sector only: iterate on half-embedded vectors (cplx.HalfSpaceOp)
         from .cplx import HalfSpaceOp
@@ -127,7 +136,10 @@ def ddC(pos, psi, H, envs):  # ∂∂C  derivatives.jl:34-36
     return _half_space(psi, MPO_ddC(psi.be, envs.leftenv(pos + 1, psi), GR), "C", GR)
 
 
-def ddAC(pos, psi, H, envs):  # ∂∂AC  derivatives.jl:44-46
+def ddAC(pos, psi, H, envs, canonical=None):  # ∂∂AC  derivatives.jl:44-46
+    """canonical: None = decide here -- only the environments of a plain FinEnv on a real state are canonical (level 0 of
+    GL and level W-1 of GR identities); every other kind (sums, projectors, infinite / sharded environments) and every
+    complex state keeps the dense operator."""
     if _is_lazy(H, envs):
         return _lazy(ddAC, pos, psi, H, envs)
     if hasattr(envs, "vector"):          # ProjectionOperator term (excitations.py): rank-one |v><v|
@@ -138,7 +150,10 @@ def ddAC(pos, psi, H, envs):  # ∂∂AC  derivatives.jl:44-46
         from .cplx import HalfEmbeddedOp
         return HalfEmbeddedOp(psi.be, "AC", [opp], envs.leftenv(pos, psi), envs.rightenv(pos, psi))
     GR = envs.rightenv(pos, psi)
-    return _half_space(psi, MPO_ddAC(psi.be, opp, envs.leftenv(pos, psi), GR), "AC", GR)
+    if canonical is None:
+        from .environments import FinEnv
+        canonical = type(envs) is FinEnv and not getattr(psi, "cplx", False)
+    return _half_space(psi, MPO_ddAC(psi.be, opp, envs.leftenv(pos, psi), GR, canonical=canonical), "AC", GR)
 
 
 def ddAC2(pos, psi, H, envs):  # ∂∂AC2  derivatives.jl:55-58
