@@ -36,22 +36,26 @@
  *    INTERLEAVED complex128 in the same column-major index order (TensorKit / Julia Array{ComplexF64} storage); a
  *    complex MPO slice takes interleaved scalars[2 odim^2] and dense blocks.  Internally a complex product runs on
  *    the real fp64 MFMA core as two K-segments (re / im of the second operand, the first one through a loader that
- *    multiplies by i): 4x the real flops, the complex optimum.  The single gauge steps mpsk_qrpos / mpsk_lqpos and the
- *    two-site split mpsk_tsplit follow mpsk_ctx_set_dtype too: with MPSK_C128 their operands are interleaved complex matrices (leading dimensions count
- *    COMPLEX elements), Q / R / L come back complex with a real positive diagonal on the triangular factor
- *    (TensorKit leftorth! / rightorth! with QRpos() / LQpos() on ComplexF64 tensors).  They run on the real 2m x 2n
- *    embedding INSIDE the library -- 2x the GEMM flops of a native complex kernel and a Cholesky chain of 2n columns --
- *    and keep the complex structure also for ill-conditioned / rank-deficient input (structured part + one more
- *    factorization, R = triu(Q^H A)); the caller's tensors stay interleaved (2x the real memory, not 4x).  Complex
- *    mpsk_tsplit (max_keep only: trunc_err must be 0) returns complex isometries AL / AR, C lower triangular with a real
- *    positive diagonal and the kept COMPLEX singular values; the real split of the embedding (every value twice, arbitrary
- *    basis inside each pair) only supplies the kept subspace, which is made an embedding again by projecting structured
- *    random vectors on it, with a J-invariant choice inside a cluster that straddles the cut.  mpsk_gemm under MPSK_C128
- *    multiplies interleaved complex matrices (trans = conjugate transpose, alpha / beta real, leading dimensions in complex
- *    elements) as ONE real GEMM on the embedded A and the interleaved B: 8 M N K flops, the complex optimum.  The remaining
- *    entry points (mpsk_qrpos2, mpsk_qrlq_pair, mpsk_tsvd, Krylov vector helpers, mpsk_regularize) are fp64 only and ignore
- *    the ctx dtype: a complex host runs its vector arithmetic on the 2n doubles of an interleaved vector (real inner
- *    products suffice for the Hermitian Lanczos solvers).
+ *    multiplies by i): 4x the real flops, the complex optimum.
+ *    The gauge entry points follow mpsk_ctx_set_dtype too: mpsk_qrpos, mpsk_lqpos, mpsk_tsvd, mpsk_tsplit and mpsk_gemm.
+ *    With MPSK_C128 their matrix operands are interleaved complex, leading dimensions count COMPLEX elements, and
+ *    singular values (S) stay real doubles.
+ *     - mpsk_qrpos / mpsk_lqpos: Q / R / L complex with a real positive diagonal on the triangular factor (TensorKit
+ *       leftorth! / rightorth! with QRpos() / LQpos()).  They run on the real 2m x 2n embedding inside the library and
+ *       keep the complex structure also for ill-conditioned / rank-deficient input (structured part + one more
+ *       factorization, R = triu(Q^H A)).
+ *     - mpsk_tsvd: a NATIVE complex one-sided block Jacobi (complex rotations, Hermitian Gram matrices) on the R^H of a
+ *       complex QRpos of the tall orientation; each complex singular value appears once.  Same truncation rule as fp64.
+ *     - mpsk_tsplit: trunc_err = 0 (truncdim): the real split of the embedding supplies the kept subspace (every value
+ *       twice, arbitrary basis inside each pair), made an embedding again by projecting structured random vectors on it,
+ *       with a J-invariant choice inside a cluster that straddles the cut.  trunc_err > 0 (truncerr, optionally with
+ *       max_keep): the complex mpsk_tsvd chooses k, AL = U[:, :k] and (C, AR) = LQpos(AL^H theta).  Both return complex
+ *       isometries AL / AR and C lower triangular with a real positive diagonal.
+ *     - mpsk_gemm: interleaved complex matrices (trans = conjugate transpose, alpha / beta real) as ONE real GEMM on the
+ *       embedded A and the interleaved B: 8 M N K flops, the complex optimum.
+ *    The remaining entry points (mpsk_qrpos2, mpsk_qrlq_pair, Krylov vector helpers, mpsk_regularize) are fp64 only and
+ *    ignore the ctx dtype: a complex host runs its vector arithmetic on the 2n doubles of an interleaved vector (real
+ *    inner products suffice for the Hermitian Lanczos solvers).
  */
 #ifndef MPSK_H
 #define MPSK_H
@@ -253,7 +257,13 @@ int mpsk_qr_commit(mpsk_ctx* ctx, int* redone);
  * bound, as TensorKit 0.12's truncerr(eps) (p = 2) applies it [restated from the published TensorKit source, which the
  * reference does not vendor: parity unpinned; equal to the relative rule for the normalised theta of DMRG2 / IDMRG2 /
  * real-time TDVP2].  *kept / *disc_norm are written on the host (sync).
- * Returns MPSK_ERR_HIP with "did not converge" if the Jacobi iteration is not orthogonal to 1e-9 after 40 sweeps. */
+ * Returns MPSK_ERR_HIP with "did not converge" if the Jacobi iteration is not orthogonal to 1e-9 after 40 sweeps;
+ * trunc_err < 0 is MPSK_ERR_INVALID.
+ * MPSK_C128 (mpsk_ctx_set_dtype): theta, U, Vh interleaved complex (ldt / ldu / ldv in complex elements), S kmax real
+ * doubles, descending; theta = U diag(S) Vh with Vh = V^H.  The truncation counts every complex value once.
+ * Rank-deficient input (MPSK_C128): a zero singular value gets a ZERO vector on one side (the side the Jacobi normalises
+ * by 1 / sigma) and a vector of an orthonormal completion on the other.  The zero is the column of U when m >= n and
+ * min(m, n) <= 64, or m < n and min(m, n) > 64; otherwise it is the row of Vh. */
 int mpsk_tsvd(mpsk_ctx* ctx, int m, int n, const void* theta, int ldt, void* U, int ldu, void* S, void* Vh,
               int ldv, int max_keep, double trunc_err, int* kept, double* disc_norm);
 /* Truncated two-site split theta (m x n, min(m, n) > 64) ~ AL (m x k) . C (k x k) . AR (k x n): what dmrg.jl:96-104 /
@@ -264,7 +274,11 @@ int mpsk_tsvd(mpsk_ctx* ctx, int m, int n, const void* theta, int ldt, void* U, 
  * an LQpos); S (min(m, n) doubles) receives all singular values (svd mode 3: see mpsk_ctx_set_svd_mode), *kept = k.
  * Buffers: AL m x min(m,n), C min(m,n)^2, AR min(m,n) x n (only the leading k columns / rows are written).
  * Any scale: a theta whose largest entry is outside [1e-100, 1e100] is split as theta / max|theta_ij| (C, S, disc_norm scaled
- * back); theta = 0 returns C = 0 with identity isometries. */
+ * back); theta = 0 returns C = 0 with identity isometries.
+ * MPSK_C128: interleaved complex operands (leading dimensions in complex elements), C lower triangular with a real positive
+ * diagonal.  trunc_err = 0: truncdim only, S receives the k kept values (the rest NaN).  trunc_err > 0: k = the smaller of
+ * the max_keep and truncerr results of the complex mpsk_tsvd, S receives all min(m, n) values, *disc_norm = the 2-norm of
+ * the discarded complex values; any min(m, n) >= 1.  trunc_err < 0: MPSK_ERR_INVALID. */
 int mpsk_tsplit(mpsk_ctx* ctx, int m, int n, const void* theta, int ldt, int max_keep, double trunc_err,
                 void* AL, int ldal, void* C, int ldc, void* AR, int ldar, void* S, int* kept, double* disc_norm);
 /* Interleaved complex matrix (m x n complex: 2m x n doubles, ldh in doubles) <-> its real 2m x 2n embedding

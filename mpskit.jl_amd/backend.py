@@ -445,9 +445,27 @@ class Backend:
             self._set_dtype(False)
         return L, Q
 
-    def tsplit_c(self, theta: DTensor, max_keep=0):
-        """Two-site split of an interleaved complex128 tensor (shape (2 m, n) = complex m x n; mpsk_tsplit under MPSK_C128,
-        truncdim scheme): al (2 m, k), c (2 k, k) lower triangular, ar (2 k, n), the k kept singular values, discarded norm."""
+    def tsvd_c(self, theta: DTensor, max_keep=0, trunc_err=0.0):
+        """Truncated SVD of an interleaved complex128 matrix (upload_c layout: shape (2 m, n) = complex m x n; mpsk_tsvd under
+        MPSK_C128): U (2 m, kmax), S (kmax,) real descending, Vh (2 kmax, n), kept, discarded norm -- as tsvd."""
+        m2, n = theta.shape
+        m = m2 // 2
+        assert m2 == 2 * m
+        kmax = min(m, n)
+        U, S, Vh = self.empty(m2, kmax), self.empty(kmax), self.empty(2 * kmax, n)
+        kept, disc = C.c_int(0), C.c_double(0.0)
+        self._set_dtype(True)
+        try:
+            check(self.lib.mpsk_tsvd(self.ctx, m, n, theta.ptr, m, U.ptr, m, S.ptr, Vh.ptr, kmax, int(max_keep),
+                                     float(trunc_err), C.byref(kept), C.byref(disc)), "mpsk_tsvd (C128)")
+        finally:
+            self._set_dtype(False)
+        return U, S, Vh, kept.value, disc.value
+
+    def tsplit_c(self, theta: DTensor, max_keep=0, trunc_err=0.0):
+        """Two-site split of an interleaved complex128 tensor (shape (2 m, n) = complex m x n; mpsk_tsplit under MPSK_C128):
+        al (2 m, k), c (2 k, k) lower triangular, ar (2 k, n), the k kept singular values, discarded norm.  trunc_err = 0:
+        truncdim scheme (max_keep); trunc_err > 0: k from the native complex SVD (the smaller of the two schemes)."""
         m2, n = theta.shape
         m = m2 // 2
         kf = min(m, n)
@@ -455,8 +473,8 @@ class Backend:
         kept, disc = C.c_int(0), C.c_double(0.0)
         self._set_dtype(True)
         try:
-            check(self.lib.mpsk_tsplit(self.ctx, m, n, theta.ptr, m, int(max_keep), 0.0, AL.ptr, m, Cm.ptr, kf, AR.ptr, kf,
-                                       S.ptr, C.byref(kept), C.byref(disc)), "mpsk_tsplit (C128)")
+            check(self.lib.mpsk_tsplit(self.ctx, m, n, theta.ptr, m, int(max_keep), float(trunc_err), AL.ptr, m, Cm.ptr, kf,
+                                       AR.ptr, kf, S.ptr, C.byref(kept), C.byref(disc)), "mpsk_tsplit (C128)")
         finally:
             self._set_dtype(False)
         k = kept.value

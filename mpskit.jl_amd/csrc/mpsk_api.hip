@@ -1646,8 +1646,8 @@ static int lqpos_f64(mpsk_ctx* c, int m, int n, const void* A, int lda, void* L,
   HIPCHK(transpose(Rt, m, m, m, (double*)L, ldl, c->stream));
   return MPSK_OK;
 }
-int mpsk_tsvd(mpsk_ctx* c, int m, int n, const void* theta, int ldt, void* U, int ldu, void* S, void* Vh,
-              int ldv, int max_keep, double trunc_err, int* kept, double* disc_norm) {
+static int tsvd_f64(mpsk_ctx* c, int m, int n, const void* theta, int ldt, void* U, int ldu, void* S, void* Vh,
+                    int ldv, int max_keep, double trunc_err, int* kept, double* disc_norm) {
   REQUIRE(c && theta && U && S && Vh && kept && disc_norm, "NULL argument");
   REQUIRE(m > 0 && n > 0, "dimensions must be positive");
   const int kmax = m < n ? m : n;
@@ -1716,6 +1716,62 @@ int mpsk_tsvd(mpsk_ctx* c, int m, int n, const void* theta, int ldt, void* U, in
                       trunc_err, kept, disc_norm, c->ws, c->stream, &err, &c->last_svd_sweeps, nullptr, 0, 0, 0, c->xstreams, 3);
   if (e != hipSuccess) return fail(MPSK_ERR_HIP, std::string("mpsk_tsvd: ") + (err.empty() ? hipGetErrorString(e) : err.c_str()));
   return MPSK_OK;
+}
+
+// complex128 (ctx dtype MPSK_C128): interleaved theta / U / Vh, leading dimensions in complex elements, S real.  As the fp64
+// entry, the tall orientation A' (theta or theta^H) is factored first, A' = Qb Rb (qrpos_c128), and the Jacobi runs on
+// Rb^H.  ONE workspace plan covers the whole call, reserved before anything runs:
+//   c->ws = [ region 0 | A^H (wide input only) | Qb | Rb ]
+//   region 0 = max(the real workspace of the embedded QRpos inside qrpos_c128 (qrpos_f64 on 2 mm x 2 nn, at c->ws + 0),
+//                  the Jacobi workspace (tsvd_c128_workspace_bytes)) -- the QR is finished before the Jacobi starts.
+// qrpos_c128's own ensure_ws then finds the workspace large enough and never moves it under Qb / Rb.
+static int tsvd_c128_entry(mpsk_ctx* c, int m, int n, const void* theta, int ldt, void* U, int ldu, void* S, void* Vh,
+                           int ldv, int max_keep, double trunc_err, int* kept, double* disc_norm) {
+  REQUIRE(c && theta && U && S && Vh && kept && disc_norm, "NULL argument");
+  REQUIRE(m > 0 && n > 0, "dimensions must be positive");
+  const int kmax = m < n ? m : n;
+  REQUIRE(ldt >= m && ldu >= m && ldv >= kmax, "leading dimension too small");
+  REQUIRE(trunc_err >= 0.0, "trunc_err must be >= 0");
+  REQUIRE(!c->pend.active, "a deferred factorization is pending (mpsk_qr_commit first)");
+  c->defer_next = false;
+  HIPCHK(hipSetDevice(c->device));
+  std::string err;
+  const int mm = m < n ? n : m, nn = m < n ? m : n, transposed = m < n ? 1 : 0;
+  hipError_t e = hipSuccess;
+  if (c->svd_precondition && nn > 64) {
+    const size_t a_d = transposed ? 2 * ev2((size_t)mm * nn) : 0, q_d = 2 * ev2((size_t)mm * nn), r_d = 2 * ev2((size_t)nn * nn);
+    size_t r0 = sizeof(double) * qr_ws_doubles(2 * mm, 2 * nn);
+    r0 = std::max(r0, tsvd_c128_workspace_bytes(nn, nn, mm));
+    r0 = (r0 + 255) & ~(size_t)255;
+    if (int rc = ensure_ws(c, r0 + sizeof(double) * (a_d + q_d + r_d))) return rc;
+    double* At = (double*)((char*)c->ws + r0);
+    double* Qb = At + a_d;
+    double* Rb = Qb + q_d;
+    const void* Ap = theta;
+    int lda = ldt;
+    if (transposed) {
+      hipLaunchKernelGGL(cx_ctranspose_kernel, dim3(1024), dim3(256), 0, c->stream, (const double*)theta, (int64_t)2 * ldt, m, n,
+                         At, (int64_t)2 * mm);
+      Ap = At; lda = mm;
+    }
+    if (int rc = qrpos_c128(c, mm, nn, Ap, lda, Qb, mm, Rb, nn)) return rc;
+    e = tsvd_c128(nn, nn, Rb, nn, (double*)U, ldu, (double*)S, (double*)Vh, ldv, max_keep, trunc_err, kept, disc_norm, c->ws,
+                  c->stream, &err, &c->last_svd_sweeps, Qb, mm, mm, transposed);
+  } else {
+    if (int rc = ensure_ws(c, tsvd_c128_workspace_bytes(m, n, 0))) return rc;
+    e = tsvd_c128(m, n, (const double*)theta, ldt, (double*)U, ldu, (double*)S, (double*)Vh, ldv, max_keep, trunc_err, kept,
+                  disc_norm, c->ws, c->stream, &err, &c->last_svd_sweeps, nullptr, 0, 0, 0);
+  }
+  if (e != hipSuccess) return fail(MPSK_ERR_HIP, std::string("mpsk_tsvd (C128): ") + (err.empty() ? hipGetErrorString(e) : err.c_str()));
+  return MPSK_OK;
+}
+
+// the ABI entry: fp64, or complex128 when the ctx dtype says so (mpsk_ctx_set_dtype)
+int mpsk_tsvd(mpsk_ctx* c, int m, int n, const void* theta, int ldt, void* U, int ldu, void* S, void* Vh,
+              int ldv, int max_keep, double trunc_err, int* kept, double* disc_norm) {
+  REQUIRE(c, "ctx is NULL");
+  return c->dtype == MPSK_C128 ? tsvd_c128_entry(c, m, n, theta, ldt, U, ldu, S, Vh, ldv, max_keep, trunc_err, kept, disc_norm)
+                               : tsvd_f64(c, m, n, theta, ldt, U, ldu, S, Vh, ldv, max_keep, trunc_err, kept, disc_norm);
 }
 
 // Truncated two-site split  theta ~ AL . C . AR  (tsvd!(theta; trunc) followed by al, c, ar of dmrg.jl:96-104 /
@@ -2176,11 +2232,15 @@ static int tsplit_core(mpsk_ctx* c, int m, int n, const void* theta, int ldt, in
 // value, so what is taken from it is the kept SUBSPACE (2k + 16 leading left vectors through the truncation-aware
 // real split), made an embedding again by projecting structured random vectors on it -- the construction of
 // cplx.split_two_site (mpskit.jl_amd/cplx.py), including a J-invariant choice inside a cluster that straddles the cut.
-// Truncation by max_keep only (truncdim); trunc_err > 0 is refused.
+// This path truncates by max_keep only (truncdim); trunc_err > 0 takes tsplit_c128_truncerr instead.
+static int tsplit_c128_truncerr(mpsk_ctx* c, int m, int n, const void* theta, int ldt, int max_keep, double trunc_err,
+                                void* AL, int ldal, void* Cm, int ldc, void* AR, int ldar, void* S, int* kept, double* disc_norm);
 static int tsplit_c128(mpsk_ctx* c, int m, int n, const void* theta, int ldt, int max_keep, double trunc_err,
                        void* AL, int ldal, void* Cm, int ldc, void* AR, int ldar, void* S, int* kept, double* disc_norm) {
   REQUIRE(c && theta && AL && Cm && AR && S && kept && disc_norm, "NULL argument");
   REQUIRE(m > 0 && n > 0, "dimensions must be positive");
+  if (trunc_err > 0.0)
+    return tsplit_c128_truncerr(c, m, n, theta, ldt, max_keep, trunc_err, AL, ldal, Cm, ldc, AR, ldar, S, kept, disc_norm);
   REQUIRE(trunc_err == 0.0, "complex mpsk_tsplit truncates by max_keep only (trunc_err must be 0)");
   const int kfull = m < n ? m : n;
   const int k = (max_keep > 0 && max_keep < kfull) ? max_keep : kfull;
@@ -2207,7 +2267,7 @@ static int tsplit_c128(mpsk_ctx* c, int m, int n, const void* theta, int ldt, in
     if (kE > 64) {
       if (int rc = tsplit_f64(c, m2, n2, E, m2, req, 0.0, ALe, m2, Ce, kE, ARe, kE, Se, &kk, &dn)) return rc;
     } else {        // small tensors: the full decomposition (mpsk_tsvd has no size floor); only its left vectors are used
-      if (int rc = mpsk_tsvd(c, m2, n2, E, m2, ALe, m2, Se, ARe, kE, req, 0.0, &kk, &dn)) return rc;
+      if (int rc = tsvd_f64(c, m2, n2, E, m2, ALe, m2, Se, ARe, kE, req, 0.0, &kk, &dn)) return rc;
     }
     have = kk;
     hs.resize(have);
@@ -2261,6 +2321,35 @@ static int tsplit_c128(mpsk_ctx* c, int m, int n, const void* theta, int ldt, in
   HIPCHK(hipStreamSynchronize(c->stream));                                    // sc is a host temporary
   *kept = k;
   *disc_norm = std::sqrt(std::max(0.5 * tn * tn - mn * mn, 0.0));
+  return MPSK_OK;
+}
+
+static int gemm_c128(mpsk_ctx* c, int transA, int transB, int M, int N, int K, double alpha, const void* A, int64_t lda,
+                     const void* B, int64_t ldb, double beta, void* C, int64_t ldc);
+// trunc_err > 0: the native complex SVD chooses k (the smaller of the max_keep and truncerr results, every complex value
+// counted once), AL = U[:, :k], M = AL^H theta and (C, AR) = LQpos(M): the contract of the truncdim path.  S receives all
+// min(m, n) values.  U / Vh / M live in complex scratch 2; the SVD, the GEMM and the LQpos use c->ws and scratches 0 / 1.
+static int tsplit_c128_truncerr(mpsk_ctx* c, int m, int n, const void* theta, int ldt, int max_keep, double trunc_err,
+                                void* AL, int ldal, void* Cm, int ldc, void* AR, int ldar, void* S, int* kept, double* disc_norm) {
+  REQUIRE(ldt >= m, "leading dimension too small");
+  HIPCHK(hipSetDevice(c->device));
+  const int kfull = m < n ? m : n;
+  const size_t u_d = 2 * ev2((size_t)m * kfull), v_d = 2 * ev2((size_t)kfull * n), s_d = ev2((size_t)kfull);
+  double* buf = nullptr;
+  if (int rc = cx_scratch(c, 2, sizeof(double) * (u_d + 2 * v_d + s_d), &buf)) return rc;
+  double *Ub = buf, *Vb = Ub + u_d, *Mh = Vb + v_d, *Sb = Mh + v_d;
+  int k = 0;
+  double dn = 0.0;
+  if (int rc = tsvd_c128_entry(c, m, n, theta, ldt, Ub, m, Sb, Vb, kfull, max_keep, trunc_err, &k, &dn)) return rc;
+  REQUIRE(ldal >= m && ldc >= k && ldar >= k, "leading dimension too small");
+  HIPCHK(hipMemcpy2DAsync(AL, sizeof(double) * 2 * ldal, Ub, sizeof(double) * 2 * m, sizeof(double) * 2 * m, k,
+                          hipMemcpyDeviceToDevice, c->stream));
+  if (int rc = gemm_c128(c, 1, 0, k, n, m, 1.0, Ub, m, theta, ldt, 0.0, Mh, k)) return rc;
+  if (int rc = lqpos_c128(c, k, n, Mh, k, Cm, ldc, AR, ldar)) return rc;
+  HIPCHK(hipMemcpyAsync(S, Sb, sizeof(double) * kfull, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *kept = k;
+  *disc_norm = dn;
   return MPSK_OK;
 }
 

@@ -163,5 +163,11 @@ hipError_t tsvd(int m, int n, const double* theta, int ldt, double* U, int ldu, 
                 int max_keep, double trunc_err, int* kept, double* disc_norm, void* ws, hipStream_t s,
                 std::string* err, int* sweeps_out, const double* Qpre = nullptr, int ldq = 0, int q_rows = 0,
                 int outer_transposed = 0, const hipStream_t* xs = nullptr, int nxs = 0, int vfree = 0);
+// complex128 counterpart (interleaved operands, leading dimensions in complex elements; mpsk_svd.hip).  q_rows: rows of
+// Qpre in the QR-preconditioned mode (0 otherwise); the workspace depends on it.
+size_t tsvd_c128_workspace_bytes(int m, int n, int q_rows);
+hipError_t tsvd_c128(int m, int n, const double* theta, int ldt, double* U, int ldu, double* S, double* Vh, int ldv,
+                     int max_keep, double trunc_err, int* kept, double* disc_norm, void* ws, hipStream_t s,
+                     std::string* err, int* sweeps_out, const double* Qpre, int ldq, int q_rows, int outer_transposed);
 
 }  // namespace mpsk

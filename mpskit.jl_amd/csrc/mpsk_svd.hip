@@ -1231,4 +1231,399 @@ hipError_t tsvd(int m, int n, const double* theta, int ldt, double* U, int ldu, 
   return hipGetLastError();
 }
 
+// ==== complex128 (mpsk_tsvd under MPSK_C128) ============================================================================
+// The same one-sided block Jacobi on interleaved complex storage, with J2 = 64 COMPLEX columns per pair.  A complex m x n
+// matrix is the real 2m x n matrix whose row pairs hold (re, im) (the "half-embedded" view of mpsk_internal.h), so with
+// X_p the 2m x 64 half view of pair p:
+//   Gram    Re(X_p^H X_p) = X_p^T X_p,   Im(X_p^H X_p) = (J X_p)^T X_p   -- two batched TN launches of the complex GEMM
+//           family (segJ = 0 / 1), each writing one plane of the interleaved Gram matrix (c_rs = 2)
+//   eig     M_p = W_p L W_p^H   -- cyclic two-sided Jacobi with complex rotations, M and W in LDS (cjacobi_eig_kernel)
+//   update  X_p <- X_p W_p = X_p Wr + (J X_p) Wi   -- one launch, two K-segments, W planar
+// The tournament, tables, tolerance and sweep logic are those of the real solver with 2m real rows; only the unchained,
+// single-stream order exists here.
+//
+// Rotation of the column pair (p, q), g = M_pq = |g| e^{i phi}:  the real Hestenes rotation (c, s) of the 2 x 2 problem
+// [[a, |g|], [|g|, b]] and sigma = s e^{i phi};  J = [[c, sigma], [-conj(sigma), c]], X <- X J, M <- J^H M J.
+// LDS: M and W, two planes each, rows padded to 65: 4 x 64 x 65 x 8 B = 130 KB -> one workgroup per CU.  A call has
+// P = n / 64 <= 256 pairs for n <= 16384, never more workgroups than CUs, so the occupancy costs nothing.
+__global__ __launch_bounds__(256) void cjacobi_eig_kernel(const double* __restrict__ Mpart, int Q, double* __restrict__ Wout,
+                                                          double tol, unsigned long long* __restrict__ flag, int inner_sweeps) {
+  __shared__ double Mr[J2][J2 + 1], Mi[J2][J2 + 1];    // M[i][j] = X_i^H X_j
+  __shared__ double Wr[J2][J2 + 1], Wi[J2][J2 + 1];
+  __shared__ double red[4];
+  __shared__ int any_rot;
+  const int tid = threadIdx.x;
+  const int p = blockIdx.x;
+  const size_t psz = (size_t)2 * J2 * J2;              // one interleaved (Gram) or planar (W) complex 64 x 64 matrix
+  const double* Mp = Mpart + (size_t)p * Q * psz;
+  for (int e = tid; e < 2 * J2 * J2; e += 256) {       // sum of the Q K-split partial Gram matrices (interleaved)
+    double acc = 0.0;
+    for (int q = 0; q < Q; ++q) acc += Mp[(size_t)q * psz + e];
+    const int ij = e >> 1, i = ij % J2, j = ij / J2;
+    if (e & 1) Mi[i][j] = acc; else Mr[i][j] = acc;
+  }
+  __syncthreads();
+  // Hermitian part + convergence measure max |g_ij|^2 / (g_ii g_jj); the thread that owns (i, j), i < j, also owns (j, i)
+  double mx = 0.0;
+  for (int e = tid; e < J2 * J2; e += 256) {
+    const int i = e % J2, j = e / J2;
+    if (i < j) {
+      const double ar = 0.5 * (Mr[i][j] + Mr[j][i]), ai = 0.5 * (Mi[i][j] - Mi[j][i]);
+      const double dd = Mr[i][i] * Mr[j][j], g2 = ar * ar + ai * ai;
+      mx = fmax(mx, g2 == 0.0 ? 0.0 : (dd > 0.0 ? g2 / dd : 1.0));
+      Mr[i][j] = ar; Mi[i][j] = ai;
+      Mr[j][i] = ar; Mi[j][i] = -ai;
+    } else if (i == j) {
+      Mi[i][i] = 0.0;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
+  if ((tid & 63) == 0) red[tid >> 6] = mx;
+  __syncthreads();
+  mx = sqrt(fmax(fmax(red[0], red[1]), fmax(red[2], red[3])));
+  if (tid == 0) atomicMax(flag, (unsigned long long)__double_as_longlong(mx));
+  double* Wp = Wout + (size_t)p * psz;                 // planar: re plane [0, J2^2), im plane [J2^2, 2 J2^2)
+  if (mx <= tol) {                                     // (uniform over the workgroup)
+    for (int e = tid; e < J2 * J2; e += 256) {
+      Wp[e] = (e % J2 == e / J2) ? 1.0 : 0.0;
+      Wp[J2 * J2 + e] = 0.0;
+    }
+    return;
+  }
+  for (int e = tid; e < J2 * J2; e += 256) {
+    const int i = e % J2, j = e / J2;
+    Wr[i][j] = (i == j) ? 1.0 : 0.0;
+    Wi[i][j] = 0.0;
+  }
+  __syncthreads();
+  // 32 disjoint pairs per step (round robin over 64 indices, the pairing of jacobi_eig_kernel), 8 lanes per pair, two phases:
+  //   A: rotation parameters from (M_pp, M_qq, M_pq), then columns p, q of M and W   (a team only touches its own columns)
+  //   B: rows p, q of M                                                              (a team only touches its own rows)
+  const int team = tid >> 3, pj = tid & 7;
+  const int pk = ((team & 3) << 3) | (team >> 2);
+  for (int sweep = 0; sweep < inner_sweeps; ++sweep) {
+    if (tid == 0) any_rot = 0;
+    __syncthreads();
+    int rotated = 0;
+    for (int st = 0; st < J2 - 1; ++st) {
+      int pp, qq;
+      if (pk == 0) { pp = J2 - 1; qq = st; }
+      else { pp = (st + pk) % (J2 - 1); qq = (st + (J2 - 1) - pk) % (J2 - 1); }
+      if (pp > qq) { const int t = pp; pp = qq; qq = t; }
+      const double a = Mr[pp][pp], b = Mr[qq][qq], gr = Mr[pp][qq], gi = Mi[pp][qq];
+      const double g2 = gr * gr + gi * gi;
+      double c = 1.0, sr = 0.0, si = 0.0;              // sigma = sr + i si
+      if (g2 > 1.0e-34 * a * b) {
+        const double ag = sqrt(g2);
+        const double zeta = (b - a) / (2.0 * ag);
+        const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        c = 1.0 / sqrt(1.0 + t * t);
+        const double sg = c * t / ag;
+        sr = sg * gr;
+        si = sg * gi;
+        if (g2 > 1.0e-20 * a * b) rotated = 1;         // |cos| > 1e-10: another inner sweep is worth it
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {                    // x_p <- c x_p - conj(sigma) x_q ,  x_q <- sigma x_p + c x_q
+        const int r = pj + 8 * i;
+        const double mpr = Mr[r][pp], mpi = Mi[r][pp], mqr = Mr[r][qq], mqi = Mi[r][qq];
+        const double wpr = Wr[r][pp], wpi = Wi[r][pp], wqr = Wr[r][qq], wqi = Wi[r][qq];
+        Mr[r][pp] = c * mpr - (sr * mqr + si * mqi);
+        Mi[r][pp] = c * mpi - (sr * mqi - si * mqr);
+        Mr[r][qq] = (sr * mpr - si * mpi) + c * mqr;
+        Mi[r][qq] = (sr * mpi + si * mpr) + c * mqi;
+        Wr[r][pp] = c * wpr - (sr * wqr + si * wqi);
+        Wi[r][pp] = c * wpi - (sr * wqi - si * wqr);
+        Wr[r][qq] = (sr * wpr - si * wpi) + c * wqr;
+        Wi[r][qq] = (sr * wpi + si * wpr) + c * wqi;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {                    // y_p <- c y_p - sigma y_q ,  y_q <- conj(sigma) y_p + c y_q
+        const int j = pj + 8 * i;
+        const double ypr = Mr[pp][j], ypi = Mi[pp][j], yqr = Mr[qq][j], yqi = Mi[qq][j];
+        Mr[pp][j] = c * ypr - (sr * yqr - si * yqi);
+        Mi[pp][j] = c * ypi - (sr * yqi + si * yqr);
+        Mr[qq][j] = (sr * ypr + si * ypi) + c * yqr;
+        Mi[qq][j] = (sr * ypi - si * ypr) + c * yqi;
+      }
+      __syncthreads();
+    }
+    if (rotated) any_rot = 1;
+    __syncthreads();
+    if (!any_rot) break;
+    __syncthreads();
+  }
+  // one Newton-Schulz step  W <- W (3 I - W^H W) / 2  (unitarity drift of the accumulated rotations, see jacobi_eig_kernel);
+  // T = W^H W goes to the M planes, which are no longer needed
+  for (int e = tid; e < J2 * J2; e += 256) {
+    const int i = e % J2, j = e / J2;
+    double tr = 0.0, ti = 0.0;
+    for (int k = 0; k < J2; ++k) {
+      const double ar = Wr[k][i], ai = Wi[k][i], br = Wr[k][j], bi = Wi[k][j];
+      tr += ar * br + ai * bi;
+      ti += ar * bi - ai * br;
+    }
+    Mr[i][j] = tr; Mi[i][j] = ti;
+  }
+  __syncthreads();
+  for (int e = tid; e < J2 * J2; e += 256) {
+    const int i = e % J2, j = e / J2;
+    double pr = 0.0, pi = 0.0;
+    for (int k = 0; k < J2; ++k) {
+      const double ar = Wr[i][k], ai = Wi[i][k], br = Mr[k][j], bi = Mi[k][j];
+      pr += ar * br - ai * bi;
+      pi += ar * bi + ai * br;
+    }
+    Wp[i + J2 * j] = 1.5 * Wr[i][j] - 0.5 * pr;
+    Wp[J2 * J2 + i + J2 * j] = 1.5 * Wi[i][j] - 0.5 * pi;
+  }
+}
+
+// G (mm x npad complex, interleaved) = theta or theta^H (ctrans), zero padded ; V (nn x npad complex) = [I 0].  ldt2: the
+// leading dimension of theta in DOUBLES
+__global__ __launch_bounds__(256) void csvd_init_kernel(const double* __restrict__ theta, int64_t ldt2, int mm, int nn, int ctrans,
+                                                        double* __restrict__ G, int npad, double* __restrict__ V) {
+  const int64_t tg = (int64_t)mm * npad, tv = (int64_t)nn * npad;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < tg + tv; e += (int64_t)gridDim.x * blockDim.x) {
+    if (e < tg) {
+      const int r = (int)(e % mm), c = (int)(e / mm);
+      double re = 0.0, im = 0.0;
+      if (c < nn) {
+        if (ctrans) { re = theta[2 * c + ldt2 * r]; im = -theta[2 * c + 1 + ldt2 * r]; }
+        else { re = theta[2 * r + ldt2 * c]; im = theta[2 * r + 1 + ldt2 * c]; }
+      }
+      G[2 * e] = re; G[2 * e + 1] = im;
+    } else {
+      const int64_t f = e - tg;
+      const int r = (int)(f % nn), c = (int)(f / nn);
+      V[2 * f] = (r == c) ? 1.0 : 0.0; V[2 * f + 1] = 0.0;
+    }
+  }
+}
+
+// column i of the result = column perm[i] (i when perm is null) of the complex src (rows x ., lds complex) times scale[i]:
+//   mode 0  out (rows x k) interleaved, ldo complex       mode 1  out (k x rows) = its conjugate transpose, ldo complex
+//   mode 2  out (rows x k) planar: re plane at out, im plane at out + plane, ldo real
+__global__ __launch_bounds__(256) void cgather_kernel(const double* __restrict__ src, int64_t lds, int rows,
+                                                      const int* __restrict__ perm, const double* __restrict__ scale, int k,
+                                                      double* __restrict__ out, int64_t ldo, int mode, int64_t plane) {
+  const int64_t total = (int64_t)rows * k;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int r = (int)(e % rows), i = (int)(e / rows);
+    const double* sp = src + 2 * (r + lds * (perm ? perm[i] : i));
+    double re = sp[0], im = sp[1];
+    if (scale) { re *= scale[i]; im *= scale[i]; }
+    if (mode == 0) { out[2 * (r + ldo * i)] = re; out[2 * (r + ldo * i) + 1] = im; }
+    else if (mode == 1) { out[2 * (i + ldo * r)] = re; out[2 * (i + ldo * r) + 1] = -im; }
+    else { out[r + ldo * i] = re; out[plane + r + ldo * i] = im; }
+  }
+}
+
+struct CSvdPlan {
+  int mm, nn, npad, P, Q, kq, transposed;    // kq: REAL rows (2 mm / Q) per K-split of the Gram product
+  size_t y_doubles, bytes;
+};
+
+static CSvdPlan csvd_plan(int m, int n, int q_rows) {
+  CSvdPlan p;
+  p.transposed = (m < n);
+  p.mm = p.transposed ? n : m;
+  p.nn = p.transposed ? m : n;
+  p.npad = ((p.nn + J2 - 1) / J2) * J2;
+  p.P = p.npad / J2;
+  const int mr = 2 * p.mm;
+  int target = 1024 / p.P;
+  if (target < 1) target = 1;
+  if (target > 16) target = 16;
+  int q = 1;                                 // largest divisor of 2 mm <= target with >= 128 (even) real rows per split
+  for (int c = target; c >= 2; --c)
+    if (mr % c == 0 && (mr / c) % 2 == 0 && mr / c >= 128) { q = c; break; }
+  p.Q = q;
+  p.kq = mr / q;
+  const size_t w = (size_t)2 * J2 * J2;
+  p.y_doubles = (size_t)2 * q_rows * p.nn;   // QR-preconditioned, wide: Qpre W before its conjugate transpose
+  const size_t d = (size_t)2 * (2 * (size_t)p.mm * p.npad) + (size_t)2 * (2 * (size_t)p.nn * p.npad) + (size_t)p.P * p.Q * w +
+                   (size_t)p.P * w + (size_t)2 * p.npad + p.y_doubles + 64;
+  const size_t tabs = (size_t)(2 * (size_t)p.P * p.Q + 10 * (size_t)p.P) * sizeof(int64_t) + 256;
+  p.bytes = d * sizeof(double) + tabs + (size_t)p.npad * sizeof(int);
+  return p;
+}
+
+size_t tsvd_c128_workspace_bytes(int m, int n, int q_rows) { return csvd_plan(m, n, q_rows).bytes; }
+
+// Host-synchronising complex truncated SVD (include/mpsk.h, mpsk_tsvd under MPSK_C128).  Every matrix is interleaved complex,
+// leading dimensions in complex elements; S real.  Qpre != nullptr: QR-preconditioned mode as in tsvd(): the caller factored
+// the tall orientation A' (q_rows x n) = Qpre R and passes theta := R (n x n); Jacobi runs on R^H:
+//   R^H V = G  =>  A' = (Qpre V) Sigma (G Sigma^-1)^H ;  outer_transposed: A' = theta^H.
+hipError_t tsvd_c128(int m, int n, const double* theta, int ldt, double* U, int ldu, double* S, double* Vh, int ldv,
+                     int max_keep, double trunc_err, int* kept, double* disc_norm, void* ws, hipStream_t s,
+                     std::string* err, int* sweeps_out, const double* Qpre, int ldq, int q_rows, int outer_transposed) {
+  const CSvdPlan pl = csvd_plan(m, n, Qpre ? q_rows : 0);
+  int ctrans = pl.transposed;
+  if (Qpre) {
+    if (m != n) return hipErrorInvalidValue;
+    ctrans = 1;                                // G <- R^H
+  }
+  const int mm = pl.mm, nn = pl.nn, npad = pl.npad, P = pl.P, Q = pl.Q, kq = pl.kq;
+  const int mr = 2 * mm, nr = 2 * nn;          // real rows of G and V
+  const int kmax = std::min(m, n);
+  const size_t wsz = (size_t)2 * J2 * J2;
+  double* G[2]; double* V[2];
+  double* base = (double*)ws;
+  G[0] = base; G[1] = G[0] + (size_t)mr * npad;
+  V[0] = G[1] + (size_t)mr * npad; V[1] = V[0] + (size_t)nr * npad;
+  double* Mpart = V[1] + (size_t)nr * npad;
+  double* Wb = Mpart + (size_t)P * Q * wsz;    // one stream: round r's update has read W before round r + 1's eig writes it
+  double* sigma2 = Wb + (size_t)P * wsz;
+  double* scale = sigma2 + npad;
+  double* Y = scale + npad;
+  unsigned long long* flag = (unsigned long long*)(Y + pl.y_doubles);
+  int64_t* tabs = (int64_t*)(flag + 8);
+  int64_t* t_gramA = tabs;
+  int64_t* t_gramC = t_gramA + (size_t)P * Q;
+  int64_t* t_updA_G = t_gramC + (size_t)P * Q;
+  int64_t* t_updA_V = t_updA_G + 2 * P;
+  int64_t* t_updB = t_updA_V + 2 * P;
+  int64_t* t_updC_G = t_updB + 2 * P;
+  int64_t* t_updC_V = t_updC_G + 2 * P;
+  int* d_perm = (int*)(t_updC_V + 2 * P);
+  auto dest_slot = [&](int p, int half) -> int {   // the round robin of tsvd()
+    if (P == 1) return half;
+    if (half == 0) {
+      if (p == 0) return 0;
+      if (p + 1 <= P - 1) return 2 * (p + 1);
+      return 2 * (P - 1) + 1;
+    }
+    if (p == 0) return 2 * 1;
+    return 2 * (p - 1) + 1;
+  };
+  std::vector<int64_t> h((size_t)2 * P * Q + 10 * P, 0);
+  int64_t* hgA = h.data(); int64_t* hgC = hgA + (size_t)P * Q;
+  int64_t* huAG = hgC + (size_t)P * Q; int64_t* huAV = huAG + 2 * P; int64_t* huB = huAV + 2 * P;
+  int64_t* huCG = huB + 2 * P; int64_t* huCV = huCG + 2 * P;
+  for (int p = 0; p < P; ++p) {
+    for (int q = 0; q < Q; ++q) {
+      hgA[p * Q + q] = (int64_t)p * J2 * mr + (int64_t)q * kq;
+      hgC[p * Q + q] = ((int64_t)p * Q + q) * (int64_t)wsz;
+    }
+    huAG[p] = (int64_t)p * J2 * mr;
+    huAV[p] = (int64_t)p * J2 * nr;
+    huB[p] = (int64_t)p * (int64_t)wsz;
+    huCG[p] = (int64_t)dest_slot(p, 0) * JB * mr;
+    huCG[P + p] = (int64_t)dest_slot(p, 1) * JB * mr;
+    huCV[p] = (int64_t)dest_slot(p, 0) * JB * nr;
+    huCV[P + p] = (int64_t)dest_slot(p, 1) * JB * nr;
+  }
+  hipError_t e;
+  if ((e = hipMemcpyAsync(tabs, h.data(), h.size() * sizeof(int64_t), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(csvd_init_kernel, dim3(2048), dim3(256), 0, s, theta, (int64_t)2 * ldt, mm, nn, ctrans, G[0], npad, V[0]);
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;   // h is a host temporary
+
+  const double tol = std::sqrt((double)mm) * 2.220446049250313e-16;
+  const int inner_sweeps = (P == 1) ? 15 : 1;     // a single pair has no tournament: the full inner iteration
+  const int rounds = (P == 1) ? 1 : 2 * P - 1;
+  int cur = 0, sweeps = 0;
+  unsigned long long hflag = 0;
+  double mx_last = 0.0;
+  for (int sweep = 0; sweep < 40; ++sweep) {
+    if ((e = hipMemsetAsync(flag, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
+    for (int r = 0; r < rounds; ++r) {
+      for (int al = 0; al < 2; ++al) {             // 1. Gram planes: Re = X^T X, Im = (J X)^T X, K split over Q
+        GemmArgs g;
+        std::memset(&g, 0, sizeof(g));
+        g.A = G[cur]; g.B = G[cur]; g.C = Mpart + al; g.M = J2; g.N = J2; g.K = kq; g.lda = mr; g.ldb = mr; g.ldc = 2 * J2;
+        g.batch = P * Q; g.nseg = 1; g.alpha = 1.0; g.beta = 0.0; g.transA = 1; g.transB = 0;
+        g.tabA = t_gramA; g.tabB = t_gramA; g.tabC = t_gramC; g.tabs_even = 1;
+        g.cplx = 1; g.c_rs = 2; g.segJ[0] = (signed char)al;
+        if ((e = gemm_f64(g, s)) != hipSuccess) return e;
+      }
+      hipLaunchKernelGGL(cjacobi_eig_kernel, dim3(P), dim3(256), 0, s, Mpart, Q, Wb, tol, flag, inner_sweeps);   // 2.
+      GemmArgs u;                                  // 3. X <- X Wr + (J X) Wi into next round's slots, G then V
+      std::memset(&u, 0, sizeof(u));
+      u.B = Wb; u.N = J2; u.K = J2; u.ldb = J2; u.batch = P; u.nseg = 2; u.segB[1] = (int64_t)J2 * J2; u.segJ[1] = 1;
+      u.alpha = 1.0; u.beta = 0.0; u.tabB = t_updB; u.tabs_even = 1; u.splitN = JB; u.cplx = 1;
+      u.A = G[cur]; u.C = G[cur ^ 1]; u.M = mr; u.lda = mr; u.ldc = mr; u.tabA = t_updA_G; u.tabC = t_updC_G; u.tabC2 = t_updC_G + P;
+      if ((e = gemm_f64(u, s)) != hipSuccess) return e;
+      u.A = V[cur]; u.C = V[cur ^ 1]; u.M = nr; u.lda = nr; u.ldc = nr; u.tabA = t_updA_V; u.tabC = t_updC_V; u.tabC2 = t_updC_V + P;
+      if ((e = gemm_f64(u, s)) != hipSuccess) return e;
+      cur ^= 1;
+    }
+    ++sweeps;
+    if ((e = hipMemcpyAsync(&hflag, flag, sizeof(hflag), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    double mx;
+    std::memcpy(&mx, &hflag, sizeof(double));
+    if (getenv("MPSK_SVD_DEBUG")) fprintf(stderr, "[mpsk_tsvd c128] sweep %d: max |cos| = %.3e (tol %.1e)\n", sweeps, mx, tol);
+    mx_last = mx;
+    if (mx <= tol || mx <= 1.0e-9) break;          // (quadratic convergence: see tsvd())
+  }
+  if (sweeps_out) *sweeps_out = sweeps;
+  if (!(mx_last <= 1.0e-9)) {
+    if (err) {
+      char buf[160];
+      snprintf(buf, sizeof(buf), "complex block-Jacobi SVD did not converge: max |cos| = %.3e after %d sweeps", mx_last, sweeps);
+      *err = buf;
+    }
+    return hipErrorNotReady;
+  }
+  if (getenv("MPSK_SVD_DEBUG")) fprintf(stderr, "[mpsk_tsvd c128] %d x %d: P=%d Q=%d rounds/sweep=%d sweeps=%d\n", mm, nn, P, Q, rounds, sweeps);
+  hipLaunchKernelGGL(colnorm2_kernel, dim3(npad), dim3(256), 0, s, G[cur], mr, mr, sigma2);
+  std::vector<double> hs(npad);
+  if ((e = hipMemcpyAsync(hs.data(), sigma2, sizeof(double) * npad, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+  std::vector<int> perm(npad);
+  std::iota(perm.begin(), perm.end(), 0);
+  std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return hs[a] > hs[b]; });
+  std::vector<double> sv(kmax), sc(kmax);
+  for (int i = 0; i < kmax; ++i) sv[i] = std::sqrt(std::max(hs[perm[i]], 0.0));
+  int k = kmax;                                    // truncation: exactly the fp64 rule (tsvd()), every value counted once
+  if (max_keep > 0 && max_keep < k) k = max_keep;
+  if (trunc_err > 0.0) {
+    double tail2 = 0.0;
+    for (int i = k; i < kmax; ++i) tail2 += sv[i] * sv[i];
+    while (k > 1 && tail2 + sv[k - 1] * sv[k - 1] <= trunc_err * trunc_err) { tail2 += sv[k - 1] * sv[k - 1]; --k; }
+  }
+  double disc2 = 0.0;
+  for (int i = k; i < kmax; ++i) disc2 += sv[i] * sv[i];
+  *kept = k;
+  *disc_norm = std::sqrt(disc2);
+  for (int i = 0; i < kmax; ++i) sc[i] = sv[i] > 0.0 ? 1.0 / sv[i] : 0.0;
+  if ((e = hipMemcpyAsync(d_perm, perm.data(), sizeof(int) * kmax, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(scale, sc.data(), sizeof(double) * kmax, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(S, sv.data(), sizeof(double) * kmax, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  const dim3 gg(1024), gb(256);
+  if (Qpre) {
+    double* Vp = G[cur ^ 1];                       // the idle ping-pong buffer: V[:, perm] planar (nn x kmax, two planes)
+    const int64_t plane = (int64_t)nn * kmax;
+    hipLaunchKernelGGL(cgather_kernel, gg, gb, 0, s, V[cur], (int64_t)nn, nn, d_perm, (const double*)nullptr, kmax, Vp,
+                       (int64_t)nn, 2, plane);
+    GemmArgs g;                                    // Qpre V_p: interleaved A, planar B
+    std::memset(&g, 0, sizeof(g));
+    g.A = Qpre; g.lda = (int64_t)2 * ldq; g.B = Vp; g.ldb = nn; g.M = 2 * q_rows; g.N = kmax; g.K = nn;
+    g.batch = 1; g.nseg = 2; g.segB[1] = plane; g.segJ[1] = 1; g.alpha = 1.0; g.beta = 0.0; g.cplx = 1;
+    if (!outer_transposed) {                       // U = Qpre V_p ;  Vh = (G_p Sigma^-1)^H
+      g.C = U; g.ldc = (int64_t)2 * ldu;
+      if ((e = gemm_f64(g, s)) != hipSuccess) return e;
+      hipLaunchKernelGGL(cgather_kernel, gg, gb, 0, s, G[cur], (int64_t)mm, nn, d_perm, scale, kmax, Vh, (int64_t)ldv, 1, (int64_t)0);
+    } else {                                       // U = G_p Sigma^-1 ;  Vh = (Qpre V_p)^H
+      g.C = Y; g.ldc = (int64_t)2 * q_rows;
+      if ((e = gemm_f64(g, s)) != hipSuccess) return e;
+      hipLaunchKernelGGL(cgather_kernel, gg, gb, 0, s, G[cur], (int64_t)mm, nn, d_perm, scale, kmax, U, (int64_t)ldu, 0, (int64_t)0);
+      hipLaunchKernelGGL(cgather_kernel, gg, gb, 0, s, (const double*)Y, (int64_t)q_rows, q_rows, (const int*)nullptr,
+                         (const double*)nullptr, kmax, Vh, (int64_t)ldv, 1, (int64_t)0);
+    }
+  } else if (!pl.transposed) {                     // theta = G V^H:  U = G_p Sigma^-1, Vh = V_p^H
+    hipLaunchKernelGGL(cgather_kernel, gg, gb, 0, s, G[cur], (int64_t)mm, m, d_perm, scale, kmax, U, (int64_t)ldu, 0, (int64_t)0);
+    hipLaunchKernelGGL(cgather_kernel, gg, gb, 0, s, V[cur], (int64_t)nn, n, d_perm, (const double*)nullptr, kmax, Vh, (int64_t)ldv, 1,
+                       (int64_t)0);
+  } else {                                         // theta^H = G V^H:  U = V_p, Vh = (G_p Sigma^-1)^H
+    hipLaunchKernelGGL(cgather_kernel, gg, gb, 0, s, V[cur], (int64_t)nn, m, d_perm, (const double*)nullptr, kmax, U, (int64_t)ldu, 0,
+                       (int64_t)0);
+    hipLaunchKernelGGL(cgather_kernel, gg, gb, 0, s, G[cur], (int64_t)mm, n, d_perm, scale, kmax, Vh, (int64_t)ldv, 1, (int64_t)0);
+  }
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;   // perm / sc / sv are host temporaries
+  return hipGetLastError();
+}
+
 }  // namespace mpsk

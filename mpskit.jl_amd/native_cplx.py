@@ -307,10 +307,18 @@ def _two_site(be, left: DTensor, right: DTensor):
     return theta
 
 
-def dmrg2_sweep(psi: NativeFiniteMPS, H, envs: NativeFinEnv, eigalg, trunc_dim, ws=None):
+def _split(be, theta, trunc_dim, trunc_err):
+    # trunc_err is passed only when set: the truncdim call stays exactly what it was
+    if trunc_err:
+        return be.tsplit_c(theta, max_keep=trunc_dim, trunc_err=trunc_err)
+    return be.tsplit_c(theta, max_keep=trunc_dim)
+
+
+def dmrg2_sweep(psi: NativeFiniteMPS, H, envs: NativeFinEnv, eigalg, trunc_dim, ws=None, trunc_err=0.0):
     """One two-site DMRG sweep (dmrg.jl:86-120) on interleaved storage: theta = AC AR, eigsolve with H_AC2 (mpsk_dAC2 complex),
-    al, c, ar = tsvd!(theta; trunc = truncdim(D)) through mpsk_tsplit under MPSK_C128, normalize!(c).  Centre at site 0 before
-    and after.  Returns the energy after the sweep."""
+    al, c, ar = tsvd!(theta; trunc) through mpsk_tsplit under MPSK_C128 (truncdim(trunc_dim); truncerr(trunc_err) when that is
+    nonzero, through the native complex SVD), normalize!(c).  Centre at site 0 before and after.  Returns the energy after the
+    sweep."""
     be, L = psi.be, len(psi)
     ws = krylov.KrylovWorkspace(be) if ws is None else ws
     psi.move_center(0)
@@ -321,7 +329,7 @@ def dmrg2_sweep(psi: NativeFiniteMPS, H, envs: NativeFinEnv, eigalg, trunc_dim, 
         _, new, _, _ = krylov.eigsolve_sr(be, op, theta, tol=eigalg.tol, krylovdim=eigalg.krylovdim, maxiter=eigalg.maxiter,
                                           fixed_matvecs=eigalg.fixed_matvecs, ws=ws)
         Dl2, d1, Dr, d2 = new.shape
-        al, c, arm, _, _ = be.tsplit_c(new.reshape(Dl2 * d1, Dr * d2), max_keep=trunc_dim)
+        al, c, arm, _, _ = _split(be, new.reshape(Dl2 * d1, Dr * d2), trunc_dim, trunc_err)
         k = c.shape[1]
         be.scal(1.0 / be.norm(c), c)                                     # normalize!(c)
         ar = be.empty(2 * k, d2, Dr)                                     # ar[k, s2, b] = arm[k, (b, s2)]
@@ -346,7 +354,7 @@ def dmrg2_sweep(psi: NativeFiniteMPS, H, envs: NativeFinEnv, eigalg, trunc_dim, 
     return energy(psi, envs)
 
 
-def tdvp2_step(psi: NativeFiniteMPS, H, envs: NativeFinEnv, t, dt, alg, trunc_dim, ws=None):
+def tdvp2_step(psi: NativeFiniteMPS, H, envs: NativeFinEnv, t, dt, alg, trunc_dim, ws=None, trunc_err=0.0):
     """timestep!(psi, H, t, dt, TDVP2(truncdim(D)))  (tdvp.jl:113-146) on interleaved storage: two-site tensors integrated
     forward by dt / 2 and split (mpsk_tsplit under MPSK_C128; NO normalisation of c: the evolution is unitary), the new
     centre integrated backward, left to right and back."""
@@ -361,7 +369,7 @@ def tdvp2_step(psi: NativeFiniteMPS, H, envs: NativeFinEnv, t, dt, alg, trunc_di
         op = lambda x, out=None: be.dAC2(h1, h2, GL, GR, x, out=out)
         new = _integrate_embedded(be, op, theta, fwd, alg, ws)
         Dl2, d1, Dr, d2 = new.shape
-        al, c, arm, _, _ = be.tsplit_c(new.reshape(Dl2 * d1, Dr * d2), max_keep=trunc_dim)
+        al, c, arm, _, _ = _split(be, new.reshape(Dl2 * d1, Dr * d2), trunc_dim, trunc_err)
         k = c.shape[1]
         ar = be.empty(2 * k, d2, Dr)
         for s2 in range(d2):
@@ -399,10 +407,9 @@ def find_groundstate(psi: NativeFiniteMPS, H, alg, envs: NativeFinEnv = None):
     ws = krylov.KrylovWorkspace(psi.be)
     E_old, delta = np.inf, np.inf
     for it in range(1, alg.maxiter + 1):
-        if isinstance(alg, DMRG2):
-            if alg.trunc_dim <= 0:
-                raise NotImplementedError("interleaved DMRG2 truncates by trunc_dim (mpsk_tsplit under MPSK_C128: truncdim scheme)")
-            E = dmrg2_sweep(psi, H, envs, alg.eigalg, alg.trunc_dim, ws)
+        if isinstance(alg, DMRG2):   # the scheme of the real host (algorithms.py: _dmrg2)
+            trunc_err = alg.trunc_err if alg.trunc_dim <= 0 else 0.0
+            E = dmrg2_sweep(psi, H, envs, alg.eigalg, alg.trunc_dim, ws, trunc_err=trunc_err)
         elif isinstance(alg, DMRG):
             E = dmrg_sweep(psi, H, envs, alg.eigalg, ws)
         else:
@@ -421,9 +428,8 @@ def timestep(psi: NativeFiniteMPS, H, t, dt, alg, envs: NativeFinEnv = None):
     from .algorithms import TDVP, TDVP2
     envs = NativeFinEnv(psi, H) if envs is None else envs
     if isinstance(alg, TDVP2):
-        if alg.trunc_dim <= 0:
-            raise NotImplementedError("interleaved TDVP2 truncates by trunc_dim (truncdim scheme)")
-        return tdvp2_step(psi, H, envs, t, dt, alg, alg.trunc_dim)
+        trunc_err = alg.trunc_err if alg.trunc_dim <= 0 else 0.0
+        return tdvp2_step(psi, H, envs, t, dt, alg, alg.trunc_dim, trunc_err=trunc_err)
     if isinstance(alg, TDVP):
         return tdvp_step(psi, H, envs, t, dt, alg)
     raise TypeError(f"timestep on interleaved states takes TDVP or TDVP2, not {type(alg).__name__}")
