@@ -142,6 +142,17 @@ int mpsk_memcpy_d2d(mpsk_ctx* ctx, void* dst, const void* src, size_t bytes);
 int mpsk_mposlice_create(mpsk_ctx* ctx, int dtype, int odim, const int32_t* chi_l, const int32_t* chi_r,
                          int d, const int32_t* kind, const double* scalars, const void* const* blocks,
                          mpsk_mposlice** out);
+/* Dense MPO slice: DenseMPO tensor of src/operators/densempo.jl:4-17 (the transfer tensor of a 2D partition function or
+ * boundary-MPS contraction), O = HOST pointer to a [Wl, d, d, Wr] column-major tensor in the index order [w, t(out),
+ * s(in), v] above: O(w,t,s,v) at w + Wl (t + d (s + d v)).  MPSK_F64 only (MPSK_C128: MPSK_ERR_INVALID).  The result is an
+ * ordinary slice handle, accepted by every entry point that takes one; it is marked dense: mpsk_dAC, mpsk_hac_* (plain
+ * vector layout), mpsk_transfer_left and mpsk_transfer_right run the middle contraction (w,s) -> (v,t) as ONE fp64 MFMA
+ * GEMM [(row, col) x (s,w)] x [(s,w) x (t,v)] on intermediates laid out for it (workspace Dlo d Dr (Wl + Wr) doubles)
+ * instead of the slab mix, once min(Wl, Wr) d >= 8 (below that the mix route is kept; environment MPSK_DENSE_ROUTE=1 / 0
+ * forces the GEMM / mix route).  mpsk_dAC2, mpsk_dAC_blocked and blocked mpsk_hac_apply keep the mix route.  mpsk_hac_info:
+ * mode 4 = dense GEMM route; below the crossover the slice is prepared exactly like the mpsk_mposlice_create slice of the
+ * same O (mode 0 or 1); above it the right-combined fold (mode 1, Wl d^2 slabs) is never built. */
+int mpsk_mposlice_create_dense(mpsk_ctx* ctx, int dtype, int Wl, int Wr, int d, const void* O, mpsk_mposlice** out);
 int mpsk_mposlice_destroy(mpsk_mposlice* s);
 int mpsk_mposlice_dims(const mpsk_mposlice* s, int* Wl, int* Wr, int* d);
 
@@ -165,7 +176,8 @@ int mpsk_dAC_blocked(mpsk_ctx* ctx, const mpsk_mposlice* H, int nblk, int Dlo, i
  * elementwise pass) whenever that does not cost extra GEMM work (Heisenberg / TFI-type MPOs): the application is then
  * TWO GEMM launches with no slab mix and one intermediate instead of two; otherwise it applies exactly what mpsk_dAC
  * does.  GL / GR must stay valid and unchanged while the object lives.  x may be in the blocked layout (nblk row
- * blocks, see mpsk_dAC_blocked; nblk = 1: plain).  mpsk_hac_info: mode 1 = combined environment (nslabs of them). */
+ * blocks, see mpsk_dAC_blocked; nblk = 1: plain).  mpsk_hac_info: mode 1 = combined environment (nslabs of them);
+ * mode 4 = dense-slice GEMM route (mpsk_mposlice_create_dense). */
 typedef struct mpsk_hac mpsk_hac;
 int mpsk_hac_create(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
                     mpsk_hac** out);

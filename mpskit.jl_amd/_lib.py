@@ -47,6 +47,7 @@ SIGNATURES = {
     "mpsk_memcpy_d2d": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
     "mpsk_mposlice_create": [C.c_void_p, C.c_int, C.c_int, c_int32_p, c_int32_p, C.c_int, c_int32_p,
                              c_double_p, c_void_pp, c_void_pp],
+    "mpsk_mposlice_create_dense": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_void_pp],
     "mpsk_mposlice_destroy": [C.c_void_p],
     "mpsk_mposlice_dims": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "mpsk_dAC": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

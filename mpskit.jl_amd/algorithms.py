@@ -109,10 +109,16 @@ def _galerkin(be, h, ac, al, g=None, slot=None, offset=0):
     return be.norm(gm)
 
 
-def calc_galerkin(psi, pos, envs, h=None, g=None):
+def calc_galerkin(psi, pos, envs=None, h=None, g=None):
     """|| (1 - AL AL^dag) normalize(H_AC AC) ||   (toolbox.jl:17-22).
     h: the site's effective Hamiltonian if the caller already built it (same operator);
-    g: H_AC AC (any positive multiple) if the caller already has it."""
+    g: H_AC AC (any positive multiple) if the caller already has it.
+    DenseMPO environments (statmech.PerMPOInfEnv): calc_galerkin(psi, envs) is the maximum over the unit cell."""
+    from .statmech import PerMPOInfEnv, calc_galerkin as _galerkin_dense
+    if isinstance(pos, PerMPOInfEnv):
+        return _galerkin_dense(psi, pos)
+    if isinstance(envs, PerMPOInfEnv):
+        return _galerkin_dense(psi, envs, pos)
     be = psi.be
     if isinstance(psi, FiniteMPS):
         ac, al = psi.AC(pos), psi.AL(pos)
@@ -123,8 +129,12 @@ def calc_galerkin(psi, pos, envs, h=None, g=None):
     return _galerkin(be, h, ac, al, g)
 
 
-def expectation_value(psi, H, envs):
-    """Per-site energies (expval.jl:92-109 finite, :111-124 infinite)."""
+def expectation_value(psi, H, envs=None):
+    """Per-site energies (expval.jl:92-109 finite, :111-124 infinite); for a DenseMPO the per-site leading eigenvalue
+    (expval.jl:156-172, statmech.expectation_value)."""
+    from .statmech import DenseMPO, expectation_value as _expval_dense
+    if isinstance(H, DenseMPO):
+        return _expval_dense(psi, H, envs)
     be = psi.be
     if isinstance(envs, MultipleEnvironments):          # expval of a LazySum: sum of the terms' (lazysum.jl)
         return sum(f * expectation_value(psi, h, e) for f, h, e in zip(H.fs, H, envs.envs))

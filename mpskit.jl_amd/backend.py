@@ -220,6 +220,11 @@ class Backend:
         entries allowed; every operand of a call that takes it is an interleaved complex128 tensor)."""
         return DeviceMPOSlice(self, odim, d, chil, chir, blocks, cplx=cplx)
 
+    def mposlice_dense(self, O):
+        """mpsk_mposlice_create_dense: one real DenseMPO tensor O[w, t(out), s(in), v] (densempo.jl:4-17) as a slice whose
+        middle contraction runs as an fp64 MFMA GEMM (mpsk_hac_info mode 4 above the crossover)."""
+        return DeviceDenseSlice(self, O)
+
     # ---- hot-path operators ----------------------------------------------------------------
     def dAC(self, H, GL: DTensor, GR: DTensor, x: DTensor, out: DTensor = None):
         if getattr(H, "cplx", False):          # interleaved complex128 operands: first dimensions are doubled
@@ -825,6 +830,38 @@ class DeviceMPOSlice:
 
     def isscal(self, i, j):
         return self.contains(i, j) and np.isscalar(self.blocks[(i, j)])
+
+
+class DeviceDenseSlice:
+    """Device-side DenseMPO tensor: one dense level [Wl, d, d, Wr] behind an mpsk_mposlice handle marked dense."""
+
+    cplx = False
+
+    def __init__(self, be: Backend, O):
+        a = np.asarray(O)
+        if np.iscomplexobj(a):
+            if np.abs(a.imag).max(initial=0.0) > 0:
+                raise MpskError("DenseMPO: complex tensors are not supported (MPSK_F64 only)")
+            a = a.real
+        if a.ndim != 4 or a.shape[1] != a.shape[2]:
+            raise MpskError(f"DenseMPO tensor must be [Wl, d, d, Wr], got {a.shape}")
+        self.be = be
+        self.Wl, self.d, _, self.Wr = (int(n) for n in a.shape)
+        self.odim, self.chil, self.chir = 1, [self.Wl], [self.Wr]
+        self.blocks = {(0, 0): a}
+        flat = np.ravel(np.asarray(a, dtype=np.float64), order="F").copy()
+        h = C.c_void_p()
+        check(be.lib.mpsk_mposlice_create_dense(be.ctx, 0, self.Wl, self.Wr, self.d, flat.ctypes.data, C.byref(h)),
+              "mpsk_mposlice_create_dense")
+        self.handle = h
+
+    def __del__(self):
+        try:
+            if self.handle and self.be.ctx:
+                self.be.lib.mpsk_mposlice_destroy(self.handle)
+        except Exception:
+            pass
+        self.handle = None
 
 
 _default = {}

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -25,6 +26,9 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
   do {                                                                      \
     if (!(cond)) return fail(MPSK_ERR_INVALID, std::string(__func__) + ": " + (msg)); \
   } while (0)
+
+// dense slices (mpsk_mposlice_create_dense) with min(Wl, Wr) d below this keep the slab-mix route (see dense_route)
+static constexpr int MPSK_DENSE_MIN_CHID = 8;
 
 struct mpsk_mposlice {
   mpsk_ctx* ctx;
@@ -58,6 +62,13 @@ struct mpsk_mposlice {
   std::vector<int> jr_p, jl_p;
   int jr_nseg = 0, jl_nseg = 0;
   double O(int w, int t, int s, int v) const { return Ofull[w + (size_t)Wl * (t + d * (s + (size_t)d * v))]; }
+  // dense slice (mpsk_mposlice_create_dense): stage 2 of dAC / the transfers is the fp64 GEMM
+  //   T2[:, (t,v)] = T1[:, (s,w)] Od[(s,w), (t,v)]  on intermediates whose K index (s,w) has ONE stride;
+  // Od = O as a column-major [d Wl, d Wr] matrix, device-resident.  dtab: per-batch offset tables of the (s,w)-batched
+  // stage 1 ([2][Wl d]: A offset w P, B offset s Q), one per (P, Q) seen, built on first use.
+  bool dense = false;
+  double* d_Od = nullptr;
+  mutable std::map<std::pair<int64_t, int64_t>, int64_t*> dtab;
 };
 
 struct PoolBuf { void* p; size_t bytes; bool used; hipStream_t last = nullptr; hipEvent_t ev = nullptr; bool ev_set = false; };
@@ -316,9 +327,12 @@ int mpsk_memcpy_d2d(mpsk_ctx* c, void* dst, const void* src, size_t bytes) {
 // --------------------------------------------------------------------------------------------
 // MPO slices
 // --------------------------------------------------------------------------------------------
-int mpsk_mposlice_create(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l, const int32_t* chi_r,
-                         int d, const int32_t* kind, const double* scalars, const void* const* blocks,
-                         mpsk_mposlice** out) {
+// dense = true: the slice of mpsk_mposlice_create_dense.  Above the crossover it has no right-combined fold (mpsk_hac never
+// takes mode 1 for it: at chi = d = 16 the fold would hold 4096 slabs); below, it is prepared exactly like the slice
+// mpsk_mposlice_create builds from the same O.
+static int mposlice_build(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l, const int32_t* chi_r, int d,
+                          const int32_t* kind, const double* scalars, const void* const* blocks, bool dense,
+                          mpsk_mposlice** out) {
   REQUIRE(c && out && chi_l && chi_r && kind, "NULL argument");
   REQUIRE(dtype == MPSK_F64 || dtype == MPSK_C128, "dtype must be MPSK_F64 or MPSK_C128");
   const bool cx = dtype == MPSK_C128;     // scalars / dense blocks are then interleaved complex128 (re, im)
@@ -383,7 +397,8 @@ int mpsk_mposlice_create(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l,
   HIPCHK(mix_plan_create(fwd, d * s->Wr, d * s->Wl, &s->fwd));
   HIPCHK(mix_plan_create(bwd, d * s->Wl, d * s->Wr, &s->bwd));
   HIPCHK(mix_plan_create(rgt, d * s->Wl, d * s->Wr, &s->rgt));
-  if (!cx) {  // right-combined plan (real slices; complex operators use the mix form)
+  const bool fold = !dense || std::min(s->Wl, s->Wr) * d < MPSK_DENSE_MIN_CHID;
+  if (!cx && fold) {  // right-combined plan (real slices; complex operators use the mix form)
     std::vector<MixTerm> rc;
     std::vector<int> per_t(d, 0);
     for (int t = 0; t < d; ++t)
@@ -439,8 +454,36 @@ int mpsk_mposlice_create(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l,
       s->jordan = s->jr_nseg > 0 && s->jl_nseg > 0;
     }
   }
+  if (dense) {
+    const int Wl = s->Wl, Wr = s->Wr;
+    std::vector<double> od((size_t)d * Wl * d * Wr);
+    for (int v = 0; v < Wr; ++v)
+      for (int t = 0; t < d; ++t)
+        for (int w = 0; w < Wl; ++w)
+          for (int si = 0; si < d; ++si)
+            od[(si + (size_t)d * w) + (size_t)d * Wl * (t + (size_t)d * v)] = s->O(w, t, si, v);
+    s->dense = true;
+    if (hipMalloc(&s->d_Od, sizeof(double) * od.size()) != hipSuccess) { mpsk_mposlice_destroy(s); return fail(MPSK_ERR_NOMEM, "dense MPO hipMalloc failed"); }
+    HIPCHK(hipMemcpy(s->d_Od, od.data(), sizeof(double) * od.size(), hipMemcpyHostToDevice));
+  }
   *out = s;
   return MPSK_OK;
+}
+
+int mpsk_mposlice_create(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l, const int32_t* chi_r,
+                         int d, const int32_t* kind, const double* scalars, const void* const* blocks,
+                         mpsk_mposlice** out) {
+  return mposlice_build(c, dtype, odim, chi_l, chi_r, d, kind, scalars, blocks, false, out);
+}
+
+int mpsk_mposlice_create_dense(mpsk_ctx* c, int dtype, int Wl, int Wr, int d, const void* O, mpsk_mposlice** out) {
+  REQUIRE(c && O && out, "NULL argument");
+  REQUIRE(dtype == MPSK_F64, "dense MPO slices are MPSK_F64 only (complex DenseMPO is not implemented; build an MPSK_C128 "
+                             "slice with mpsk_mposlice_create instead)");
+  REQUIRE(Wl > 0 && Wr > 0 && d > 0, "Wl, Wr and d must be positive");
+  const int32_t cl = Wl, cr = Wr, kind = MPSK_BLOCK_DENSE;
+  const void* blocks[1] = {O};
+  return mposlice_build(c, dtype, 1, &cl, &cr, d, &kind, nullptr, blocks, true, out);
 }
 
 int mpsk_mposlice_destroy(mpsk_mposlice* s) {
@@ -458,6 +501,8 @@ int mpsk_mposlice_destroy(mpsk_mposlice* s) {
   mix_plan_destroy(&s->rc);
   mix_plan_destroy(&s->jr);
   mix_plan_destroy(&s->jl);
+  if (s->d_Od) (void)hipFree(s->d_Od);
+  for (auto& kv : s->dtab) (void)hipFree(kv.second);
   delete s;
   return MPSK_OK;
 }
@@ -724,12 +769,116 @@ static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   return MPSK_OK;
 }
 
+// ---- dense MPO slices (mpsk_mposlice_create_dense): stage 2 on the MFMA GEMM core -------------------------------------
+// A dense O[w,t,s,v] has (Wl d)(Wr d) terms: as a slab mix every output slab re-reads Wl d input slabs.  The dense route
+// keeps the three-stage decomposition but lays the two intermediates out so that stage 2 is ONE plain GEMM:
+//   T1[(r,b), (s,w)] = sum_a GL[w][r,a] x[a,s,b]           stage 1, batched over (s,w) with offset tables
+//   T2[(r,b), (t,v)] = sum_(s,w) T1[(r,b), (s,w)] Od[(s,w), (t,v)]      stage 2, M = Dlo Dr, K = d Wl, N = d Wr
+//   y[r,t,q]         = sum_v sum_b T2[(r,b), (t,v)] GR[v][b,q]          stage 3, batched over t, K-segments over v
+// (r, b) is the row index of both intermediates, so the K index (s,w) of stage 2 has a single stride.  transfer_left
+// is the same with (Dlb, Ab) in place of (Dlo, GR); transfer_right already produces U[(b,p), (t,v)] and consumes
+// V[(b,p), (s,w)], so only its mix becomes a GEMM (B = Od^T).  Environments keep the slab layout.
+// Below a product Wl d (and Wr d) of MPSK_DENSE_MIN_CHID the GEMMs are too narrow to beat the mix (tools/bench_dense_mpo.py):
+// such slices take the mix route.  Environment MPSK_DENSE_ROUTE=1 / 0 forces the dense / mix route (tests, A/B).
+
+static bool dense_route(const mpsk_mposlice* H) {
+  if (!H || !H->dense || H->dtype != MPSK_F64) return false;
+  if (const char* ev = getenv("MPSK_DENSE_ROUTE")) {
+    if (ev[0] == '1') return true;
+    if (ev[0] == '0') return false;
+  }
+  return std::min(H->Wl, H->Wr) * H->d >= MPSK_DENSE_MIN_CHID;
+}
+
+// device table [2][Wl d]: tab[z] = w P, tab[Wl d + z] = s Q for z = s + d w (stage-1 batch offsets of GL / x)
+static int dense_tab(const mpsk_mposlice* H, int64_t P, int64_t Q, const int64_t** out) {
+  auto key = std::make_pair(P, Q);
+  auto it = H->dtab.find(key);
+  if (it != H->dtab.end()) { *out = it->second; return MPSK_OK; }
+  const int nz = H->Wl * H->d;
+  std::vector<int64_t> h((size_t)2 * nz);
+  for (int z = 0; z < nz; ++z) { h[z] = (int64_t)(z / H->d) * P; h[nz + z] = (int64_t)(z % H->d) * Q; }
+  int64_t* p = nullptr;
+  if (hipMalloc(&p, sizeof(int64_t) * h.size()) != hipSuccess) return fail(MPSK_ERR_NOMEM, "dense offset table hipMalloc failed");
+  if (hipMemcpy(p, h.data(), sizeof(int64_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(MPSK_ERR_HIP, "dense offset table upload failed");
+  }
+  H->dtab.emplace(key, p);
+  *out = p;
+  return MPSK_OK;
+}
+
+// stage 1 of the dense route: T[(r,b), (s,w)] = sum_a G[w][r,a] X[a,s,b]   (G: Wl slabs [R, Dk]; X: [Dk, d, Nb])
+static int dense_stage1(mpsk_ctx* c, const mpsk_mposlice* H, int R, int Dk, int Nb, const double* G, const double* X, double* T) {
+  const int d = H->d;
+  const int64_t* tab = nullptr;
+  if (int rc = dense_tab(H, (int64_t)R * Dk, Dk, &tab)) return rc;
+  GemmArgs g1 = mk(G, X, T, R, Nb, Dk, R, (int64_t)Dk * d, R);
+  g1.batch = H->Wl * d; g1.bsC = (int64_t)R * Nb;
+  g1.tabA = tab; g1.tabB = tab + (size_t)H->Wl * d;
+  g1.tabs_even = ((int64_t)R * Dk) % 2 == 0 && Dk % 2 == 0;
+  g1.tag = 1;
+  HIPCHK(gemm_f64(g1, c->stream));
+  return MPSK_OK;
+}
+
+// stage 2: T2[(r,b), (t,v)] = T1[(r,b), (s,w)] Od      (rows = R Nb)
+static int dense_stage2(mpsk_ctx* c, const mpsk_mposlice* H, int64_t rows, const double* T1, double* T2) {
+  const int d = H->d;
+  GemmArgs g2 = mk(T1, H->d_Od, T2, (int)rows, d * H->Wr, d * H->Wl, rows, (int64_t)d * H->Wl, rows);
+  g2.tag = 1;
+  HIPCHK(gemm_f64(g2, c->stream));
+  return MPSK_OK;
+}
+
+static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const double* GL, const double* GR,
+                     const double* x, double* y) {
+  HIPCHK(hipSetDevice(c->device));
+  const int d = H->d, Wl = H->Wl, Wr = H->Wr;
+  const size_t slab = (size_t)Dlo * Dr;               // one (s,w) / (t,v) column of the intermediates
+  if (int rc = ensure_ws(c, sizeof(double) * slab * d * (Wl + Wr))) return rc;
+  double* T1 = (double*)c->ws;
+  double* T2 = T1 + slab * d * Wl;
+  if (int rc = dense_stage1(c, H, Dlo, Dl, Dr, GL, x, T1)) return rc;
+  if (int rc = dense_stage2(c, H, (int64_t)slab, T1, T2)) return rc;
+  // stage 3: y[:, t, :] = sum_v T2[:, :, t, v] GR[v]    (batch over t; K-segments over v)
+  std::vector<int64_t> sa, sb;
+  for (int v = 0; v < Wr; ++v) if (H->col_used[v]) { sa.push_back((int64_t)v * d * slab); sb.push_back((int64_t)v * Dr * Dr); }
+  if (sa.empty()) { HIPCHK(zero_async(y, sizeof(double) * slab * d, c->stream)); return MPSK_OK; }
+  GemmArgs g3 = mk(T2, GR, y, Dlo, Dr, Dr, Dlo, Dr, (int64_t)Dlo * d);
+  g3.batch = d; g3.bsA = (int64_t)slab; g3.bsB = 0; g3.bsC = Dlo;
+  g3.tag = 1;
+  HIPCHK(gemm_segments(g3, sa, sb, c->stream));
+  return MPSK_OK;
+}
+
+// GLout[v][q,b] = sum GLin[w][p,a] A[a,s,b] O[w,t,s,v] Ab[p,t,q]
+static int transfer_left_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dr, int Dlb, int Drb, const double* GLin,
+                               const double* A, const double* Ab, double* GLout) {
+  const int d = H->d, Wl = H->Wl, Wr = H->Wr;
+  const size_t slab = (size_t)Dlb * Dr;
+  if (int rc = ensure_ws(c, sizeof(double) * slab * d * (Wl + Wr))) return rc;
+  double* T1 = (double*)c->ws;
+  double* T2 = T1 + slab * d * Wl;
+  if (int rc = dense_stage1(c, H, Dlb, Dl, Dr, GLin, A, T1)) return rc;
+  if (int rc = dense_stage2(c, H, (int64_t)slab, T1, T2)) return rc;
+  // GLout[v][q,b] = sum_t sum_p Ab[p,t,q] T2[(p,b), (t,v)]     (batch over v; K-segments over t)
+  std::vector<int64_t> sa, sb;
+  for (int t = 0; t < d; ++t) { sa.push_back((int64_t)t * Dlb); sb.push_back((int64_t)t * slab); }
+  GemmArgs g3 = mk(Ab, T2, GLout, Drb, Dr, Dlb, (int64_t)Dlb * d, Dlb, Drb, 1, 0);
+  g3.batch = Wr; g3.bsA = 0; g3.bsB = (int64_t)slab * d; g3.bsC = (int64_t)Drb * Dr;
+  HIPCHK(gemm_segments(g3, sa, sb, c->stream));
+  return MPSK_OK;
+}
+
 int mpsk_dAC(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
              const void* x, void* y) {
   REQUIRE(c && H && GL && GR && x && y, "NULL argument");
   REQUIRE(Dlo > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
   if (H->dtype == MPSK_C128)
     return dAC_c128(c, H, Dlo, Dl, Dr, (const double*)GL, (const double*)GR, nullptr, (const double*)x, (double*)y);
+  if (dense_route(H)) return dAC_dense(c, H, Dlo, Dl, Dr, (const double*)GL, (const double*)GR, (const double*)x, (double*)y);
   return dAC_impl(c, H, Dlo, Dl, Dr, GL, GR, x, 1, y);
 }
 
@@ -862,6 +1011,7 @@ int mpsk_hac_create_ex(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int
   h->mode = jordan ? 3 : (H->rc_nseg > 0 && t_rc <= t_mix) ? 1 : 0;
   if (const char* ev = getenv("MPSK_HAC_MODE"))
     h->mode = (ev[0] == '3' && jordan) ? 3 : (ev[0] == '1' && H->rc_nseg > 0) ? 1 : 0;
+  if (dense_route(H)) h->mode = 4;     // dense slice above the crossover (or MPSK_DENSE_ROUTE=1): GEMM route
   if (H->dtype == MPSK_C128) {
     // complex128: mix form; what is prepared once per site is the planar copy of the right environment (the B operand
     // of stage 3), so that an application converts only x
@@ -966,7 +1116,8 @@ int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
     if (nblk != 1) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_hac_apply: the blocked layout is implemented for MPSK_F64 only");
     return dAC_c128(c, H, Dlo, Dl, Dr, h->GL, h->GR, h->GRc, (const double*)x, (double*)y);
   }
-  if (h->mode == 0) return dAC_impl(c, H, Dlo, Dl, Dr, h->GL, h->GR, x, nblk, y);
+  if (h->mode == 0 || (h->mode == 4 && nblk != 1)) return dAC_impl(c, H, Dlo, Dl, Dr, h->GL, h->GR, x, nblk, y);
+  if (h->mode == 4) return dAC_dense(c, H, Dlo, Dl, Dr, h->GL, h->GR, (const double*)x, (double*)y);
   HIPCHK(hipSetDevice(c->device));
   if (h->mode == 3) {
     // y[:, t, :] = sum_k x[:, s_k, :] GRc0[(s_k, t)] + sum_k GLc[(s_k, t)] x[:, s_k, :]     (batch over t)
@@ -1148,6 +1299,8 @@ int mpsk_transfer_left(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl
   REQUIRE(Wl > 0 && d > 0 && Dl > 0 && Dr > 0 && Dlb > 0 && Drb > 0, "dimensions must be positive");
   if ((H ? H->dtype : c->dtype) == MPSK_C128)
     return transfer_left_c128(c, H, W, d, Dl, Dr, Dlb, Drb, (const double*)GLin, (const double*)A, (const double*)Ab, (double*)GLout);
+  if (dense_route(H))
+    return transfer_left_dense(c, H, Dl, Dr, Dlb, Drb, (const double*)GLin, (const double*)A, (const double*)Ab, (double*)GLout);
   const size_t slab = (size_t)Dlb * d * Dr;
   if (int rc = ensure_ws(c, sizeof(double) * slab * (Wl + (H ? Wr : 0)))) return rc;
   double* T1 = (double*)c->ws;
@@ -1185,7 +1338,11 @@ int mpsk_transfer_right(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int D
   GemmArgs g1 = mk((const double*)GRin, (const double*)Ab, U, Dr, Dlb * d, Drb, Dr, (int64_t)Dlb * d, Dr, 0, 1);
   g1.batch = Wr; g1.bsA = (int64_t)Dr * Drb; g1.bsB = 0; g1.bsC = (int64_t)slab;
   HIPCHK(gemm_f64(g1, c->stream));
-  if (H) {
+  if (H && dense_route(H)) {
+    // V[(b,p), (s,w)] = U[(b,p), (t,v)] Od^T   (U / V are already the two-index views the GEMM needs)
+    GemmArgs g2 = mk(U, H->d_Od, V, (int)plane, d * Wl, d * Wr, (int64_t)plane, (int64_t)d * Wl, (int64_t)plane, 0, 1);
+    HIPCHK(gemm_f64(g2, c->stream));
+  } else if (H) {
     SlabIndex ix{d, 1 << 30, (int64_t)plane, (int64_t)slab, 0, (int64_t)Dr};
     HIPCHK(mix_apply(H->bwd, U, ix, V, ix, Dr, Dlb, c->stream));
   }

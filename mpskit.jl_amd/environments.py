@@ -90,9 +90,13 @@ class MultipleEnvironments:
 
 
 def environments(psi, H, **kw):
-    """environments(psi, H)  (FinEnv.jl:41-70 / mpohaminfenv.jl:40-44 / multipleenv.jl:30-34)."""
+    """environments(psi, H)  (FinEnv.jl:41-70 / mpohaminfenv.jl:40-44 / multipleenv.jl:30-34; a DenseMPO:
+    permpoinfenv.jl:20-29, statmech.PerMPOInfEnv)."""
     from .states import FiniteMPS
     from .operators import LazySum
+    from .statmech import DenseMPO, PerMPOInfEnv
+    if isinstance(H, DenseMPO):
+        return PerMPOInfEnv(psi, H, **kw)
     if isinstance(H, LazySum):
         return MultipleEnvironments(H, [environments(psi, h, **kw) for h in H])
     if isinstance(psi, FiniteMPS):

@@ -1,0 +1,257 @@
+"""Boundary contraction of 2D tensor networks with the reference's API: DenseMPO (src/operators/densempo.jl:4-17),
+PerMPOInfEnv (src/environments/permpoinfenv.jl) and leading_boundary (src/algorithms/statmech/vumps.jl:15-92) for a
+single-row InfiniteMPS, plus the classical transfer tensors of the reference's test setup (test/setup.jl:78-130).
+
+Orchestration only: every matvec and transfer runs in libmpsk on dense MPO slices (mpsk_mposlice_create_dense, whose
+middle contraction is an fp64 MFMA GEMM).  The leading (:LM) eigensolves are the restarted Arnoldi of
+krylov.eigsolve_lm_real on the host."""
+from __future__ import annotations
+
+import math
+import time
+
+import numpy as np
+
+from . import krylov
+from .derivatives import MPO_ddAC, MPO_ddC
+from .states import InfiniteMPS
+
+
+class DenseMPO:
+    """Periodic list of real MPO tensors O[w, t(out), s(in), v] (densempo.jl:4-17): len, repeat, [i] (periodic)."""
+
+    def __init__(self, tensors):
+        if isinstance(tensors, np.ndarray):
+            tensors = [tensors]
+        opp = []
+        for t in tensors:
+            a = np.asarray(t)
+            if np.iscomplexobj(a):
+                if np.abs(a.imag).max(initial=0.0) > 0:
+                    raise NotImplementedError("DenseMPO: complex tensors are not supported (real fp64 only)")
+                a = a.real
+            if a.ndim != 4 or a.shape[1] != a.shape[2]:
+                raise ValueError(f"DenseMPO tensor must be [Wl, d, d, Wr], got {a.shape}")
+            opp.append(np.array(a, dtype=np.float64))
+        for i, a in enumerate(opp):
+            if a.shape[3] != opp[(i + 1) % len(opp)].shape[0]:
+                raise ValueError("DenseMPO: the right bond of each tensor must match the left bond of the next")
+        self.opp = opp
+        self._slices = {}
+
+    def __len__(self):
+        return len(self.opp)
+
+    def __getitem__(self, i):
+        return self.opp[i % len(self.opp)]
+
+    def __iter__(self):
+        return iter(self.opp)
+
+    def repeat(self, n):
+        return DenseMPO(self.opp * int(n))
+
+    @property
+    def d(self):
+        return self.opp[0].shape[1]
+
+    def slices(self, be):
+        """Device slices on backend `be` (built once per backend through be.mposlice_dense)."""
+        key = id(be)
+        if key not in self._slices:
+            self._slices[key] = (be, [be.mposlice_dense(o) for o in self.opp])
+        return self._slices[key][1]
+
+
+def _eig_lm(be, op, x0, tol, krylovdim, maxiter, ws=None):
+    """Leading eigenvector of `op` from x0.  KrylovKit's tolerance is an absolute residual norm; the transfer operators
+    here carry the partition function per tensor (kappa^(k^2) for a k x k cluster), so the tolerance is taken relative
+    to the operator's scale |op x0| / |x0|."""
+    y = op(x0)
+    scale = be.norm(y) / be.norm(x0)
+    return krylov.eigsolve_lm_real(be, op, x0, tol=tol * max(scale, 1e-300), krylovdim=krylovdim, maxiter=maxiter, ws=ws)
+
+
+class PerMPOInfEnv:
+    """Environments of a DenseMPO on a single-row InfiniteMPS with above == below (permpoinfenv.jl): lw[i] / rw[i] are the
+    left / right environments of site i in the slab layout (W, D, D), W = the MPO bond at that side of the site."""
+
+    def __init__(self, psi, mpo: DenseMPO, tol=1e-12, krylovdim=30, maxiter=100, rng=None):
+        if len(psi) % len(mpo) != 0:
+            raise ValueError(f"unit cell of the state ({len(psi)}) is not a multiple of the MPO's ({len(mpo)})")
+        self.be, self.opp = psi.be, mpo
+        self.tol, self.krylovdim, self.maxiter = tol, krylovdim, maxiter
+        self.rng = np.random.default_rng(0) if rng is None else rng
+        self.slices = mpo.slices(self.be)
+        self.ws = krylov.KrylovWorkspace(self.be)
+        self.lw = self.rw = None
+        self.dependency = None
+        self.recalculate(psi, tol)
+
+    def O(self, pos):
+        return self.slices[pos % len(self.slices)]
+
+    # ---- public ------------------------------------------------------------------------------
+    def recalculate(self, psi, tol=None):
+        """permpoinfenv.jl recalculate!: restart from the previous fixed points when the bond spaces are unchanged, from
+        random start vectors otherwise."""
+        tol = self.tol if tol is None else tol
+        n = len(psi)
+        old = self.dependency
+        same = (old is not None and len(old) == n and
+                all(a.shape == b.shape for a, b in zip(old.CR, psi.CR)))
+        if same:
+            L0, R0 = self.be.copy(self.lw[0]), self.be.copy(self.rw[n - 1])
+        else:
+            L0 = self._random(self.O(0).Wl, psi.AL[0].shape[0])
+            R0 = self._random(self.O(n - 1).Wr, psi.AR[n - 1].shape[2])
+        self.lw, self.rw = self._mixed_fixpoints(psi, L0, R0, tol)
+        self.dependency = psi
+        self.tol = tol
+        return self
+
+    def leftenv(self, pos, psi):
+        if self.dependency is not psi:
+            self.recalculate(psi)
+        return self.lw[pos % len(psi)]
+
+    def rightenv(self, pos, psi):
+        if self.dependency is not psi:
+            self.recalculate(psi)
+        return self.rw[pos % len(psi)]
+
+    def ddAC(self, pos, psi):
+        return MPO_ddAC(self.be, self.O(pos), self.leftenv(pos, psi), self.rightenv(pos, psi))
+
+    def ddC(self, pos, psi):
+        return MPO_ddC(self.be, self.leftenv(pos + 1, psi), self.rightenv(pos, psi))
+
+    # ---- helpers -------------------------------------------------------------------------------
+    def _random(self, W, D):
+        return self.be.upload(self.rng.standard_normal(W * D * D)).reshape(W, D, D)
+
+    def _mixed_fixpoints(self, psi, L0, R0, tol):  # permpoinfenv.jl:143-190 (one row)
+        be, n = self.be, len(psi)
+
+        def tl(v, out=None):
+            for i in range(n):
+                v = be.transfer_left(self.O(i), v, psi.AL[i], psi.AL[i])
+            return v if out is None else be.axpby(1.0, v, 0.0, out)
+
+        def tr(v, out=None):
+            for i in range(n - 1, -1, -1):
+                v = be.transfer_right(self.O(i), v, psi.AR[i], psi.AR[i])
+            return v if out is None else be.axpby(1.0, v, 0.0, out)
+
+        _, gl = _eig_lm(be, tl, L0, tol, self.krylovdim, self.maxiter, self.ws)
+        _, gr = _eig_lm(be, tr, R0, tol, self.krylovdim, self.maxiter, self.ws)
+        GL, GR = [None] * n, [None] * n
+        GL[0], GR[n - 1] = gl, gr
+        for i in range(1, n):
+            GL[i] = be.transfer_left(self.O(i - 1), GL[i - 1], psi.AL[i - 1], psi.AL[i - 1])
+        for i in range(n - 2, -1, -1):
+            GR[i] = be.transfer_right(self.O(i + 1), GR[i + 1], psi.AR[i + 1], psi.AR[i + 1])
+        # fix the normalisation: dot(C, dC(GL[col + 1], GR[col]) C) = 1 for every column (the eigenvectors' signs are
+        # arbitrary: a negative value flips the sign of GL[col + 1])
+        for col in range(n):
+            c = psi.CR[col]
+            lam = be.dot(c, be.dC(GL[(col + 1) % n], GR[col], c))
+            f = 1.0 / math.sqrt(abs(lam))
+            be.scal(math.copysign(f, lam), GL[(col + 1) % n])
+            be.scal(f, GR[col])
+        return GL, GR
+
+
+def environments(psi, mpo: DenseMPO, **kw):
+    """environments(psi::InfiniteMPS, opp::DenseMPO)  (permpoinfenv.jl:20-29)."""
+    return PerMPOInfEnv(psi, mpo, **kw)
+
+
+def calc_galerkin(psi, envs: PerMPOInfEnv, pos=None):
+    """|| (1 - AL AL^T) normalize(H_AC AC) ||, maximum over the unit cell when pos is None (toolbox.jl:26-38)."""
+    from .algorithms import _galerkin
+    locs = range(len(psi)) if pos is None else [pos]
+    return max(_galerkin(psi.be, envs.ddAC(loc, psi), psi.AC[loc], psi.AL[loc]) for loc in locs)
+
+
+def expectation_value(psi, mpo: DenseMPO, envs: PerMPOInfEnv | None = None):
+    """Per-site leading eigenvalue lambda_i = <AC_i, H_AC_i AC_i> on environments normalised per column
+    (expval.jl:156-172)."""
+    envs = environments(psi, mpo) if envs is None else envs
+    be = psi.be
+    out = np.zeros(len(psi))
+    for i in range(len(psi)):
+        ac = psi.AC[i]
+        out[i] = be.dot(ac, envs.ddAC(i, psi)(ac)) / be.dot(ac, ac)
+    return out
+
+
+def leading_boundary(psi, mpo: DenseMPO, alg=None, envs=None):
+    """leading_boundary(psi, opp, alg = VUMPS())  (statmech/vumps.jl:15-92): the leading boundary MPS of the column
+    transfer operator; returns (psi, envs, eps) with eps the Galerkin error."""
+    from .algorithms import VUMPS, updatetol, regauge, _log
+    alg = VUMPS() if alg is None else alg
+    be = psi.be
+    envs = environments(psi, mpo) if envs is None else envs
+    eps = calc_galerkin(psi, envs)
+    n = len(psi)
+    ws = krylov.KrylovWorkspace(be)
+    t0 = time.time()
+    history = []
+    for it in range(1, alg.maxiter + 1):
+        etol = updatetol(alg.eig_tol_min, alg.eig_tol_max, alg.eig_tol_factor, it, eps)
+        newAL = []
+        for loc in range(n):
+            _, AC = _eig_lm(be, envs.ddAC(loc, psi), psi.AC[loc], etol, alg.krylovdim, 100, ws)
+            _, C = _eig_lm(be, envs.ddC(loc, psi), psi.CR[loc], etol, alg.krylovdim, 100, ws)
+            newAL.append(regauge(be, AC, C))
+        gtol = updatetol(alg.gauge_tol_min, alg.gauge_tol_max, alg.gauge_tol_factor, it, eps)
+        psi = InfiniteMPS.from_AL(newAL, psi.CR[n - 1], tol=gtol, be=be)
+        envs.recalculate(psi, updatetol(alg.env_tol_min, alg.env_tol_max, alg.env_tol_factor, it, eps))
+        if alg.finalize is not None:
+            psi, envs = alg.finalize(it, psi, mpo, envs)
+        eps = calc_galerkin(psi, envs)
+        if alg.verbosity >= 3 or eps <= alg.tol or it == alg.maxiter:
+            lam = float(np.prod(expectation_value(psi, mpo, envs)))
+            history.append((it, lam, eps))
+            _log(alg, "VUMPS", it, lam, eps, t0)
+        if eps <= alg.tol:
+            break
+    envs.history = history
+    return psi, envs, eps
+
+
+# ---- models (test/setup.jl:78-130) --------------------------------------------------------------------------------
+
+def _ising_bond_tensor(beta):
+    """Square root of the bond Boltzmann matrix [[e^b, e^-b], [e^-b, e^b]] (ising_bond_tensor, test/setup.jl:78-83)."""
+    ev, vec = np.linalg.eigh(np.array([[math.exp(beta), math.exp(-beta)], [math.exp(-beta), math.exp(beta)]]))
+    return vec @ np.diag(np.sqrt(ev)) @ vec.T
+
+
+def classical_ising(beta=math.log(1.0 + math.sqrt(2.0)) / 2.0, cluster=1):
+    """Transfer tensor of the square-lattice Ising model: one spin per tensor, the square root of the bond Boltzmann
+    matrix on each leg (test/setup.jl:85-94).  cluster = k contracts a k x k patch into one tensor with chi = d = 2^k
+    (legs fused row by row / column by column); its leading eigenvalue per tensor is kappa^(k^2)."""
+    nt = _ising_bond_tensor(beta)
+    o = np.einsum("ia,ib,ic,id->abcd", nt, nt, nt, nt)         # delta tensor with a bond root on each leg [w,t,s,v]
+    k = int(cluster)
+    if k < 1:
+        raise ValueError("cluster must be >= 1")
+    row = o
+    for _ in range(k - 1):                                       # k tensors side by side: v of one = w of the next
+        row = np.einsum("atsv,vxyb->atxsyb", row, o)
+        row = row.reshape(2, row.shape[1] * 2, row.shape[3] * 2, 2)
+    out = row
+    for _ in range(k - 1):                                       # stack rows: t (out) of the lower = s (in) of the upper
+        out = np.einsum("atsv,bxtc->abxsvc", out, row)
+        W, X, S, V = out.shape[0] * 2, out.shape[2], out.shape[3], out.shape[4] * 2
+        out = out.reshape(W, X, S, V)
+    return DenseMPO(np.ascontiguousarray(out))
+
+
+def sixvertex(a=1.0, b=1.0, c=1.0):
+    """Six-vertex transfer tensor (test/setup.jl:124-130): the 4 x 4 weight matrix on (w t) x (v s)."""
+    m = np.array([[a, 0, 0, 0], [0, c, b, 0], [0, b, c, 0], [0, 0, 0, a]], dtype=np.float64)
+    t = m.reshape(2, 2, 2, 2, order="F")                          # t[i1, i2, i3, i4] = m[i1 + 2 i2, i3 + 2 i4]
+    return DenseMPO(np.ascontiguousarray(np.transpose(t, (0, 1, 3, 2))))   # permute ((1, 2), (4, 3))
