@@ -215,6 +215,38 @@ int mpsk_dC(mpsk_ctx* ctx, int W, int Dlo, int Dl, int Dr, const void* GL, const
 int mpsk_dAC2(mpsk_ctx* ctx, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dlo, int Dl, int Dr,
               const void* GL, const void* GR, const void* x2, void* y2);
 
+/* ---- bond expansion of a uniform state: src/algorithms/changebonds/optimalexpand.jl:16-67 --------------------------
+ * mpsk_dAC2_product == dd-AC2(i, psi, H, envs) * (AC[i] * AR[i+1])   optimalexpand.jl:22-23 (MPOHamiltonian) and :51-52
+ * (DenseMPO), derivatives.jl:119-158, WITHOUT forming the two-site tensor:
+ *   Y[(a,t1), (b,t2)] = sum GL[w][a,a'] AC[a',s1,m] O1[w,t1,s1,u] O2[u,t2,s2,v] AR[m,s2,b'] GR[v][b',b]
+ * factorised through the middle bond, Y = sum_u Lhalf[u] Rhalf[u] (each half = the first two stages of a one-site matvec
+ * with the inner MPO leg u open; the product is one GEMM launch with K = Wm Dm).  GL: Wl slabs [Dl, Dl]; GR: Wr slabs
+ * [Dr, Dr]; AC: [Dl, d1, Dm]; AR: [Dm, d2, Dr]; Y: [Dl, d1, Dr, d2] (the layout of mpsk_dAC2's result).  Both slice
+ * kinds; a dense slice above the crossover of mpsk_mposlice_create_dense contracts its MPO tensor as an fp64 MFMA GEMM,
+ * never as a slab mix.  Workspace: (Wl + Wm) d1 Dl Dm + (Wr + Wm) d2 Dm Dr doubles, no single intermediate above
+ * max(Wl, Wm, Wr) d Dmax^2.  MPSK_F64 only. */
+int mpsk_dAC2_product(mpsk_ctx* ctx, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dl, int Dm, int Dr,
+                      const void* GL, const void* GR, const void* AC, const void* AR, void* Y);
+/* mpsk_complement_tsvd == VL = leftnull(AL); VR = rightnull(AR); U, S, V = tsvd(VL' * Y * VR'; trunc = truncdim(k));
+ * (VL * U, S, V * VR)   optimalexpand.jl:25-32, randexpand.jl:24-31 -- without the null-space bases, because
+ * VL VL' = 1 - QL QL^T and VR' VR = 1 - QR^T QR.  Y: m x n (ldy); QL: m x pl, orthonormal columns; QR: pr x n,
+ * orthonormal rows (pl = 0 / pr = 0: no projector on that side, the pointer may be NULL).  Returns the
+ * *kept = min(k, m - pl, n - pr) leading singular triplets of X = (1 - QL QL^T) Y (1 - QR^T QR): U m x kept (ldu),
+ * S kept doubles, descending, Vt kept x n (ldvt >= kept).  kept = 0 is a valid answer (nothing is written).
+ *   S[j] = sigma_j(X) to 1e-10 S[0];  U^T U = 1, Vt Vt^T = 1, QL^T U = 0, Vt QR^T = 0 to 1e-12 BY CONSTRUCTION: after the
+ *   SVD both factors are projected on the complement and re-orthonormalised (QRpos / LQpos), twice; directions the SVD
+ *   cannot deliver (X = 0, rank(X) < kept) are completed inside the complement with S = 0.
+ * Method: min(m, n) <= 64: mpsk_tsvd of X.  Otherwise the truncated split of mpsk_tsplit followed by the SVD of the
+ * kept x kept core.  The split takes its checked subspace iteration only in svd mode 3 (mpsk_ctx_set_svd_mode), with
+ * r = k + max(64, k / 2) within 5/8 of min(m, n), and not while the ctx backs off after a stage that gave up; in every
+ * other case, and when the check fails, its full iteration runs on X (not mpsk_tsvd: the split needs the vectors of one
+ * side only).  mpsk_ctx_split_stats describes that split.  mpsk_ctx_complement_stats: calls with a non-empty complement /
+ * calls answered by the accepted subspace stage / all other calls (full iteration of the split, mpsk_tsvd of a small X,
+ * X = 0); any pointer may be NULL.  Synchronises.  MPSK_F64 only. */
+int mpsk_complement_tsvd(mpsk_ctx* ctx, int m, int n, const void* Y, int ldy, const void* QL, int ldql, int pl,
+                         const void* QR, int ldqr, int pr, int k, void* U, int ldu, void* S, void* Vt, int ldvt, int* kept);
+int mpsk_ctx_complement_stats(mpsk_ctx* ctx, long* n_calls, long* n_subspace, long* n_full);
+
 /* ---- transfer matrices / environment updates: src/transfermatrix/transfer.jl ---------------
  * mpsk_transfer_left == transfer_left(vec, ham::SparseMPOSlice, A, Ab)   transfer.jl:166-211
  *   GLout[v][q,b] = sum GLin[w][p,a] A[a,s,b] O[w,t,s,v] conj(Ab[p,t,q])

@@ -12,7 +12,7 @@ from .environments import FinEnv, MPOHamInfEnv, MultipleEnvironments, environmen
 from .derivatives import ddAC, ddAC2, ddC, MPO_ddAC, MPO_ddAC2, MPO_ddC  # noqa: F401,E402
 from .algorithms import (DMRG, DMRG2, VUMPS, IDMRG1, IDMRG2, TDVP, TDVP2, Arnoldi, find_groundstate, calc_galerkin,  # noqa: F401,E402
                          expectation_value, timestep, time_evolve)
-from .changebonds import changebonds, OptimalExpand, SvdCut  # noqa: F401,E402
+from .changebonds import changebonds, OptimalExpand, RandExpand, SvdCut  # noqa: F401,E402
 from .excitations import excitations, FiniteExcited, ProjectionOperator  # noqa: F401,E402
 from .quasiparticle import QuasiparticleAnsatz, LeftGaugedQP  # noqa: F401,E402
 from .toolbox import (variance, entropy, entanglement_spectrum, transfer_spectrum, marek_gap, correlation_length,  # noqa: F401,E402

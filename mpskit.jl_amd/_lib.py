@@ -110,6 +110,12 @@ SIGNATURES = {
     "mpsk_hac_eigsolve_fixed": [C.c_void_p, C.c_void_p, C.c_int, c_void_pp, C.c_void_p, C.c_void_p, C.c_void_p],
     "mpsk_vritz_dev": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mpsk_vlincomb_dev": [C.c_void_p, C.c_int64, C.c_int, c_void_pp, C.c_void_p, C.c_void_p],
+    "mpsk_dAC2_product": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                          C.c_void_p, C.c_void_p, C.c_void_p],
+    "mpsk_complement_tsvd": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                             C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                             C.POINTER(C.c_int)],
+    "mpsk_ctx_complement_stats": [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)],
 }
 # symbols without the (ctx, ...) -> int shape
 EXTRA_SYMBOLS = ["mpsk_version", "mpsk_last_error"]

@@ -298,6 +298,43 @@ class Backend:
               "mpsk_dAC2")
         return y
 
+    def dAC2_product(self, H1, H2, GL: DTensor, GR: DTensor, AC: DTensor, AR: DTensor, out: DTensor = None):
+        """mpsk_dAC2_product: H_AC2 applied to the product AC[a,s1,m] AR[m,s2,b], factorised through the middle bond
+        (the two-site tensor is never formed).  Returns Y[Dl, d1, Dr, d2]."""
+        Dl, d1, Dm = AC.shape
+        Dm2, d2, Dr = AR.shape
+        assert Dm2 == Dm and GL.shape == (H1.Wl, Dl, Dl) and GR.shape == (H2.Wr, Dr, Dr) and d1 == H1.d and d2 == H2.d, \
+            (GL.shape, GR.shape, AC.shape, AR.shape)
+        y = self.empty(Dl, d1, Dr, d2) if out is None else out
+        check(self.lib.mpsk_dAC2_product(self.ctx, H1.handle, H2.handle, Dl, Dm, Dr, GL.ptr, GR.ptr, AC.ptr, AR.ptr, y.ptr),
+              "mpsk_dAC2_product")
+        return y
+
+    def complement_tsvd(self, Y: DTensor, QL: DTensor, QR: DTensor, k: int):
+        """mpsk_complement_tsvd: the k leading singular triplets of (1 - QL QL^T) Y (1 - QR^T QR); Y (m, n), QL (m, pl)
+        with orthonormal columns or None, QR (pr, n) with orthonormal rows or None.  Returns (U (m, kept), S (kept,),
+        Vt (kept, n), kept); kept = 0: (None, None, None, 0)."""
+        m, n = Y.shape
+        pl = 0 if QL is None else QL.shape[1]
+        pr = 0 if QR is None else QR.shape[0]
+        kk = max(0, min(int(k), m - pl, n - pr))
+        U, S, Vt = self.empty(m, kk), self.empty(kk), self.empty(kk, n)
+        kept = C.c_int(-1)
+        check(self.lib.mpsk_complement_tsvd(self.ctx, m, n, Y.ptr, m, None if QL is None else QL.ptr, m, pl,
+                                            None if QR is None else QR.ptr, max(pr, 1), pr, int(k), U.ptr, m, S.ptr, Vt.ptr,
+                                            max(kk, 1), C.byref(kept)), "mpsk_complement_tsvd")
+        assert kept.value == kk, (kept.value, kk)
+        if kk == 0:
+            return None, None, None, 0
+        return U, S, Vt, kk
+
+    def complement_stats(self):
+        """mpsk_complement_tsvd calls: {"calls", "subspace" (answered by the accepted subspace stage), "full" (all others: full
+        iteration of the split, mpsk_tsvd of a small X, X = 0)}"""
+        a, b, c = C.c_long(), C.c_long(), C.c_long()
+        check(self.lib.mpsk_ctx_complement_stats(self.ctx, C.byref(a), C.byref(b), C.byref(c)), "mpsk_ctx_complement_stats")
+        return {"calls": a.value, "subspace": b.value, "full": c.value}
+
     def transfer_left(self, H, GLin: DTensor, A: DTensor, Ab: DTensor, out: DTensor = None, cplx=False):
         if cplx or getattr(H, "cplx", False):
             Dl, d, Dr = A.shape[0] // 2, A.shape[1], A.shape[2]

@@ -69,6 +69,11 @@ struct mpsk_mposlice {
   bool dense = false;
   double* d_Od = nullptr;
   mutable std::map<std::pair<int64_t, int64_t>, int64_t*> dtab;
+  // right half of mpsk_dAC2_product: OdR = O as a column-major [d Wr, d Wl] matrix, rows (s,v), columns (t,w) (the physical
+  // input and the RIGHT MPO leg are contracted, the left leg stays open); dtabR: stage-1 offset tables [2][Wr d] for
+  // z = s + d v (A offset s P into the site tensor, B offset v Q into the right environment)
+  double* d_OdR = nullptr;
+  mutable std::map<std::pair<int64_t, int64_t>, int64_t*> dtabR;
 };
 
 struct PoolBuf { void* p; size_t bytes; bool used; hipStream_t last = nullptr; hipEvent_t ev = nullptr; bool ev_set = false; };
@@ -124,6 +129,13 @@ struct mpsk_ctx {
   bool on_side = false;         // mpsk_ctx_side_begin .. mpsk_ctx_side_end: `stream` and `stream2` are swapped
   std::map<std::pair<const mpsk_mposlice*, const mpsk_mposlice*>, MixPlan> pair_plans;
   std::vector<PoolBuf> pool;    // device buffers of prepared operators (mpsk_hac), reused across site visits
+  // bond expansion (mpsk_dAC2_product / mpsk_complement_tsvd): batch offset tables of the K = Wm Dm product keyed by their
+  // strides; operands of the complement SVD in a buffer of their own (the factorizations inside size and use c->ws
+  // themselves); calls / calls answered by the accepted subspace stage / all other calls (full iteration, small X, X = 0)
+  std::map<std::vector<int64_t>, int64_t*> prod_tabs;
+  void* exws = nullptr;
+  size_t exws_bytes = 0;
+  long n_compl = 0, n_compl_sub = 0, n_compl_full = 0;
 };
 
 // prepared effective Hamiltonian of one site (MPO_ddAC of derivatives.jl:11-15: built once, applied by every Krylov step)
@@ -210,6 +222,8 @@ int mpsk_ctx_destroy(mpsk_ctx* c) {
   if (c->h_flags) (void)hipHostFree(c->h_flags);
   if (c->ws2) (void)hipFree(c->ws2);
   if (c->ws3) (void)hipFree(c->ws3);
+  if (c->exws) (void)hipFree(c->exws);
+  for (auto& kv : c->prod_tabs) (void)hipFree(kv.second);
   for (int i = 0; i < 4; ++i) if (c->cxws[i]) (void)hipFree(c->cxws[i]);
   for (int i = 1; i < 3; ++i)
     if (c->xstreams[i]) { (void)hipStreamSynchronize(c->xstreams[i]); gemm_release_stream(c->xstreams[i]); (void)hipStreamDestroy(c->xstreams[i]); }
@@ -465,6 +479,13 @@ static int mposlice_build(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l
     s->dense = true;
     if (hipMalloc(&s->d_Od, sizeof(double) * od.size()) != hipSuccess) { mpsk_mposlice_destroy(s); return fail(MPSK_ERR_NOMEM, "dense MPO hipMalloc failed"); }
     HIPCHK(hipMemcpy(s->d_Od, od.data(), sizeof(double) * od.size(), hipMemcpyHostToDevice));
+    for (int v = 0; v < Wr; ++v)
+      for (int t = 0; t < d; ++t)
+        for (int w = 0; w < Wl; ++w)
+          for (int si = 0; si < d; ++si)
+            od[(si + (size_t)d * v) + (size_t)d * Wr * (t + (size_t)d * w)] = s->O(w, t, si, v);
+    if (hipMalloc(&s->d_OdR, sizeof(double) * od.size()) != hipSuccess) { mpsk_mposlice_destroy(s); return fail(MPSK_ERR_NOMEM, "dense MPO hipMalloc failed"); }
+    HIPCHK(hipMemcpy(s->d_OdR, od.data(), sizeof(double) * od.size(), hipMemcpyHostToDevice));
   }
   *out = s;
   return MPSK_OK;
@@ -502,7 +523,9 @@ int mpsk_mposlice_destroy(mpsk_mposlice* s) {
   mix_plan_destroy(&s->jr);
   mix_plan_destroy(&s->jl);
   if (s->d_Od) (void)hipFree(s->d_Od);
+  if (s->d_OdR) (void)hipFree(s->d_OdR);
   for (auto& kv : s->dtab) (void)hipFree(kv.second);
+  for (auto& kv : s->dtabR) (void)hipFree(kv.second);
   delete s;
   return MPSK_OK;
 }
@@ -2776,6 +2799,300 @@ int mpsk_vcopy(mpsk_ctx* c, int64_t n, const void* x, void* y) {
 int mpsk_vzero(mpsk_ctx* c, int64_t n, void* x) {
   REQUIRE(c && x, "NULL argument");
   HIPCHK(hipMemsetAsync(x, 0, sizeof(double) * n, c->stream));
+  return MPSK_OK;
+}
+
+// --------------------------------------------------------------------------------------------
+// bond expansion of a uniform state (changebonds/optimalexpand.jl:16-67, changebonds.jl:13-38)
+// --------------------------------------------------------------------------------------------
+// mpsk_dAC2_product: H_AC2 applied to the PRODUCT AC[a,s1,m] AR[m,s2,b].  The two-site tensor is never formed: the
+// contraction factorises through the middle bond m and the middle MPO leg u,
+//   Lh[(a,t1), (u,m)] = sum GL[w][a,a'] AC[a',s1,m] O1[w,t1,s1,u]        (stages 1 + 2 of the one-site matvec)
+//   Rh[(u,m), (b,t2)] = sum O2[u,t2,s2,v] AR[m,s2,b'] GR[v][b',b]        (the same from the right, left MPO leg open)
+//   Y [(a,t1), (b,t2)] = sum_(u,m) Lh Rh                                   (ONE launch, K = Wm Dm as Wm K-segments,
+//                                                                          batched over (t1,t2) with offset tables)
+// Each half keeps the layout its slice kind produces (slab mix: [a,t1,m] slabs per u / [m,t2,b] slabs per u; dense GEMM
+// route: [(a,m), (t1,u)] / [(m,b), (t2,u)]); the product only needs the (t, u) strides and the leading dimension of each.
+// Intermediates: Wl d1 Dl Dm, Wm d1 Dl Dm, Wr d2 Dm Dr, Wm d2 Dm Dr doubles.
+struct HalfView { const double* p; int64_t st, su, ld; };    // operand of (t, u) at p + t st + u su, leading dimension ld
+
+static int product_tab(mpsk_ctx* c, int d1, int d2, int64_t sa, int64_t sb, int64_t sc1, int64_t sc2, const int64_t** out,
+                       bool* even) {
+  std::vector<int64_t> key{d1, d2, sa, sb, sc1, sc2};
+  *even = sa % 2 == 0 && sb % 2 == 0;
+  auto it = c->prod_tabs.find(key);
+  if (it != c->prod_tabs.end()) { *out = it->second; return MPSK_OK; }
+  const int nz = d1 * d2;
+  std::vector<int64_t> h((size_t)3 * nz);
+  for (int z = 0; z < nz; ++z) {
+    const int t1 = z % d1, t2 = z / d1;
+    h[z] = t1 * sa; h[nz + z] = t2 * sb; h[2 * nz + z] = t1 * sc1 + t2 * sc2;
+  }
+  int64_t* p = nullptr;
+  if (hipMalloc(&p, sizeof(int64_t) * h.size()) != hipSuccess) return fail(MPSK_ERR_NOMEM, "product offset table hipMalloc failed");
+  if (hipMemcpy(p, h.data(), sizeof(int64_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(MPSK_ERR_HIP, "product offset table upload failed");
+  }
+  c->prod_tabs.emplace(key, p);
+  *out = p;
+  return MPSK_OK;
+}
+
+// device table [2][Wr d]: tab[z] = s P, tab[Wr d + z] = v Q for z = s + d v (stage-1 batch offsets of the site tensor / GR)
+static int dense_tab_right(const mpsk_mposlice* H, int64_t P, int64_t Q, const int64_t** out) {
+  auto key = std::make_pair(P, Q);
+  auto it = H->dtabR.find(key);
+  if (it != H->dtabR.end()) { *out = it->second; return MPSK_OK; }
+  const int nz = H->Wr * H->d;
+  std::vector<int64_t> h((size_t)2 * nz);
+  for (int z = 0; z < nz; ++z) { h[z] = (int64_t)(z % H->d) * P; h[nz + z] = (int64_t)(z / H->d) * Q; }
+  int64_t* p = nullptr;
+  if (hipMalloc(&p, sizeof(int64_t) * h.size()) != hipSuccess) return fail(MPSK_ERR_NOMEM, "dense offset table hipMalloc failed");
+  if (hipMemcpy(p, h.data(), sizeof(int64_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(MPSK_ERR_HIP, "dense offset table upload failed");
+  }
+  H->dtabR.emplace(key, p);
+  *out = p;
+  return MPSK_OK;
+}
+
+// left half: T1 (scratch, Wl d Dl Dm) and L2 (result, Wm d Dl Dm)
+static int half_left(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dm, const double* GL, const double* AC, double* T1,
+                     double* L2, HalfView* v) {
+  const int d = H->d;
+  if (dense_route(H)) {
+    const int64_t col = (int64_t)Dl * Dm;
+    if (int rc = dense_stage1(c, H, Dl, Dl, Dm, GL, AC, T1)) return rc;          // T1[(a,m), (s,w)]
+    if (int rc = dense_stage2(c, H, col, T1, L2)) return rc;                     // L2[(a,m), (t,u)]
+    *v = HalfView{L2, col, col * d, Dl};
+    return MPSK_OK;
+  }
+  const int64_t slab = (int64_t)Dl * d * Dm;
+  GemmArgs g1 = mk(GL, AC, T1, Dl, d * Dm, Dl, Dl, Dl, Dl);                       // T1[w] = GL[w] AC
+  g1.batch = H->Wl; g1.bsA = (int64_t)Dl * Dl; g1.bsB = 0; g1.bsC = slab;
+  g1.tag = 1;
+  HIPCHK(gemm_f64(g1, c->stream));
+  SlabIndex ix{d, 1 << 30, (int64_t)Dl, slab, 0, (int64_t)Dl * d};
+  HIPCHK(mix_apply(H->fwd, T1, ix, L2, ix, Dl, Dm, c->stream));                  // L2[u][a,t,m]
+  *v = HalfView{L2, Dl, slab, (int64_t)Dl * d};
+  return MPSK_OK;
+}
+
+// right half: T1 (scratch, Wr d Dm Dr) and R2 (result, Wm d Dm Dr)
+static int half_right(mpsk_ctx* c, const mpsk_mposlice* H, int Dm, int Dr, const double* AR, const double* GR, double* T1,
+                      double* R2, HalfView* v) {
+  const int d = H->d;
+  if (dense_route(H)) {
+    const int64_t col = (int64_t)Dm * Dr;
+    const int64_t* tab = nullptr;
+    if (int rc = dense_tab_right(H, Dm, (int64_t)Dr * Dr, &tab)) return rc;
+    GemmArgs g1 = mk(AR, GR, T1, Dm, Dr, Dr, (int64_t)Dm * d, Dr, Dm);           // T1[(m,b), (s,v)] = AR[:,s,:] GR[v]
+    g1.batch = H->Wr * d; g1.bsC = col;
+    g1.tabA = tab; g1.tabB = tab + (size_t)H->Wr * d;
+    g1.tabs_even = Dm % 2 == 0 && ((int64_t)Dr * Dr) % 2 == 0;
+    g1.tag = 1;
+    HIPCHK(gemm_f64(g1, c->stream));
+    GemmArgs g2 = mk(T1, H->d_OdR, R2, (int)col, d * H->Wl, d * H->Wr, col, (int64_t)d * H->Wr, col);   // R2[(m,b), (t,u)]
+    g2.tag = 1;
+    HIPCHK(gemm_f64(g2, c->stream));
+    *v = HalfView{R2, col, col * d, Dm};
+    return MPSK_OK;
+  }
+  const int64_t slab = (int64_t)Dm * d * Dr;
+  GemmArgs g1 = mk(AR, GR, T1, Dm * d, Dr, Dr, (int64_t)Dm * d, Dr, (int64_t)Dm * d);   // T1[v][(m,s), b] = AR GR[v]
+  g1.batch = H->Wr; g1.bsA = 0; g1.bsB = (int64_t)Dr * Dr; g1.bsC = slab;
+  g1.tag = 1;
+  HIPCHK(gemm_f64(g1, c->stream));
+  SlabIndex ix{d, 1 << 30, (int64_t)Dm, slab, 0, (int64_t)Dm * d};
+  HIPCHK(mix_apply(H->rgt, T1, ix, R2, ix, Dm, Dr, c->stream));                  // R2[u][m,t,b]
+  *v = HalfView{R2, Dm, slab, (int64_t)Dm * d};
+  return MPSK_OK;
+}
+
+int mpsk_dAC2_product(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dl, int Dm, int Dr, const void* GL,
+                      const void* GR, const void* AC, const void* AR, void* Y) {
+  REQUIRE(c && H1 && H2 && GL && GR && AC && AR && Y, "NULL argument");
+  REQUIRE(H1->Wr == H2->Wl, "MPO bond dimensions of the two slices do not match");
+  REQUIRE(Dl > 0 && Dm > 0 && Dr > 0, "dimensions must be positive");
+  REQUIRE(H1->dtype == MPSK_F64 && H2->dtype == MPSK_F64, "MPSK_F64 slices only");
+  HIPCHK(hipSetDevice(c->device));
+  const int d1 = H1->d, d2 = H2->d, Wl = H1->Wl, Wm = H1->Wr, Wr = H2->Wr;
+  const auto ev = [](size_t v) { return (v + 1) & ~(size_t)1; };
+  const size_t l1 = ev((size_t)Wl * d1 * Dl * Dm), l2 = ev((size_t)Wm * d1 * Dl * Dm);
+  const size_t r1 = ev((size_t)Wr * d2 * Dm * Dr), r2 = ev((size_t)Wm * d2 * Dm * Dr);
+  if (int rc = ensure_ws(c, sizeof(double) * (l1 + l2 + r1 + r2))) return rc;
+  double* TL = (double*)c->ws;
+  double* L2 = TL + l1;
+  double* TR = L2 + l2;
+  double* R2 = TR + r1;
+  HalfView hl, hr;
+  if (int rc = half_left(c, H1, Dl, Dm, (const double*)GL, (const double*)AC, TL, L2, &hl)) return rc;
+  if (int rc = half_right(c, H2, Dm, Dr, (const double*)AR, (const double*)GR, TR, R2, &hr)) return rc;
+  // Y[a,t1,b,t2] = sum_u sum_m Lh(t1,u)[a,m] Rh(t2,u)[m,b]
+  const int64_t plane = (int64_t)Dl * d1 * Dr;
+  std::vector<int64_t> sa, sb;
+  for (int u = 0; u < Wm; ++u)
+    if (H1->col_used[u] && H2->row_used[u]) { sa.push_back(u * hl.su); sb.push_back(u * hr.su); }
+  if (sa.empty()) { HIPCHK(zero_async(Y, sizeof(double) * plane * d2, c->stream)); return MPSK_OK; }
+  const int64_t* tab = nullptr;
+  bool even = false;
+  if (int rc = product_tab(c, d1, d2, hl.st, hr.st, Dl, plane, &tab, &even)) return rc;
+  GemmArgs g = mk(hl.p, hr.p, (double*)Y, Dl, Dr, Dm, hl.ld, hr.ld, (int64_t)Dl * d1);
+  g.batch = d1 * d2;
+  g.tabA = tab; g.tabB = tab + (size_t)d1 * d2; g.tabC = tab + (size_t)2 * d1 * d2;
+  g.tabs_even = even ? 1 : 0;
+  g.tag = 1;
+  HIPCHK(gemm_segments(g, sa, sb, c->stream));
+  return MPSK_OK;
+}
+
+// mpsk_complement_tsvd: the k leading singular triplets of X = (1 - QL QL^T) Y (1 - QR^T QR) without null-space bases
+// (NL NL' = 1 - AL AL', NR' NR = 1 - AR' AR in optimalexpand.jl:22-29).  X is formed with four thin GEMMs; the triplets come
+// from the checked subspace iteration of the truncated split (tsplit_f64: X ~ A C B, kept subspace verified against X
+// itself or the full iteration taken) followed by the small SVD C = Uc S Vc, U = A Uc, Vt = Vc B.  min(m, n) <= 64: the
+// full SVD of X.  The complement condition is then imposed, not inherited: U <- QRpos((1 - QL QL^T) U), twice, and the
+// same with LQpos from the right, which also completes directions the SVD left empty (X of rank < kept, X = 0).
+static int ex_scratch(mpsk_ctx* c, size_t bytes, double** out) {
+  if (c->exws_bytes < bytes) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->exws) HIPCHK(hipFree(c->exws));
+    c->exws = nullptr; c->exws_bytes = 0;
+    if (hipMalloc(&c->exws, bytes) != hipSuccess) return fail(MPSK_ERR_NOMEM, "mpsk_complement_tsvd: workspace hipMalloc failed");
+    c->exws_bytes = bytes;
+  }
+  *out = (double*)c->exws;
+  return MPSK_OK;
+}
+
+int mpsk_complement_tsvd(mpsk_ctx* c, int m, int n, const void* Y, int ldy, const void* QL, int ldql, int pl, const void* QR,
+                         int ldqr, int pr, int k, void* U, int ldu, void* S, void* Vt, int ldvt, int* kept) {
+  REQUIRE(c && Y && kept, "NULL argument");
+  REQUIRE(c->dtype == MPSK_F64, "MPSK_F64 only");
+  REQUIRE(m > 0 && n > 0 && ldy >= m && k >= 0, "bad dimensions");
+  REQUIRE(pl >= 0 && pl <= m && pr >= 0 && pr <= n, "pl / pr out of range");
+  REQUIRE((pl == 0 || (QL && ldql >= m)) && (pr == 0 || (QR && ldqr >= pr)), "QL / QR missing or leading dimension too small");
+  const int kk = std::min(k, std::min(m - pl, n - pr));
+  *kept = kk;
+  if (kk <= 0) { *kept = 0; return MPSK_OK; }
+  REQUIRE(U && S && Vt && ldu >= m && ldvt >= kk, "U / S / Vt missing or leading dimension too small");
+  REQUIRE(!c->pend.active && !c->on_side, "not accepted inside a side-stream section / with a deferred factorization pending");
+  HIPCHK(hipSetDevice(c->device));
+  const auto ev = [](size_t v) { return (v + 1) & ~(size_t)1; };
+  const int nn = std::min(m, n);
+  const bool small = nn <= 64;
+  const int kf = small ? nn : kk;                       // columns of the factor buffers
+  const size_t x_d = ev((size_t)m * n);
+  const size_t tp_d = ev(std::max(std::max((size_t)pl * n, (size_t)m * pr), std::max((size_t)pl * kk, (size_t)kk * pr)) + 2);
+  const size_t a_d = ev((size_t)m * kf), b_d = ev((size_t)kf * n), c_d = ev((size_t)kf * kf), s_d = ev((size_t)nn);
+  double* base = nullptr;
+  if (int rc = ex_scratch(c, sizeof(double) * (x_d + tp_d + 2 * a_d + 2 * b_d + 4 * c_d + 2 * s_d), &base)) return rc;
+  double* X = base;
+  double* TP = X + x_d;
+  double* Af = TP + tp_d;            // left factor of the split / U of the small SVD
+  double* Ut = Af + a_d;             // QRpos output
+  double* Bf = Ut + a_d;             // right factor / Vt of the small SVD
+  double* Vtt = Bf + b_d;            // LQpos output
+  double* Cc = Vtt + b_d;            // core of the split
+  double* Uc = Cc + c_d;
+  double* Vc = Uc + c_d;
+  double* Rt = Vc + c_d;             // triangular factors of the re-orthonormalisations (discarded)
+  double* Ss = Rt + c_d;
+  double* S2 = Ss + s_d;
+  hipStream_t st = c->stream;
+  ++c->n_compl;
+  // X = (1 - QL QL^T) Y (1 - QR^T QR)
+  HIPCHK(hipMemcpy2DAsync(X, sizeof(double) * m, Y, sizeof(double) * ldy, sizeof(double) * m, n, hipMemcpyDeviceToDevice, st));
+  if (pl > 0) {
+    GemmArgs g1 = mk((const double*)QL, X, TP, pl, n, m, ldql, m, pl, 1, 0);
+    HIPCHK(gemm_f64(g1, st));
+    GemmArgs g2 = mk((const double*)QL, TP, X, m, n, pl, ldql, pl, m);
+    g2.alpha = -1.0; g2.beta = 1.0;
+    HIPCHK(gemm_f64(g2, st));
+  }
+  if (pr > 0) {
+    GemmArgs g1 = mk(X, (const double*)QR, TP, m, pr, n, m, ldqr, m, 0, 1);
+    HIPCHK(gemm_f64(g1, st));
+    GemmArgs g2 = mk(TP, (const double*)QR, X, m, n, pr, m, ldqr, m);
+    g2.alpha = -1.0; g2.beta = 1.0;
+    HIPCHK(gemm_f64(g2, st));
+  }
+  double mx = 0.0;
+  {
+    unsigned long long* d_mx = (unsigned long long*)c->d_partial;
+    unsigned long long h_mx = 0;
+    HIPCHK(hipMemsetAsync(d_mx, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(split_absmax_kernel, dim3(1024), dim3(256), 0, st, (const double*)X, (int64_t)m, m, n, d_mx);
+    HIPCHK(hipMemcpyAsync(&h_mx, d_mx, sizeof(h_mx), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::memcpy(&mx, &h_mx, sizeof(double));
+  }
+  int have = 0;                      // triplets delivered by the SVD; the rest is completed below
+  if (mx == 0.0 || !std::isfinite(mx)) {
+    REQUIRE(mx == 0.0, "Y is not finite");
+    ++c->n_compl_full;
+  } else if (small) {
+    int kf2 = 0; double dn = 0.0;
+    if (int rc = tsvd_f64(c, m, n, X, m, Af, m, Ss, Bf, nn, 0, 0.0, &kf2, &dn)) return rc;
+    have = std::min(kk, kf2);
+    ++c->n_compl_full;
+    HIPCHK(hipMemcpy2DAsync(U, sizeof(double) * ldu, Af, sizeof(double) * m, sizeof(double) * m, have, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpy2DAsync(Vt, sizeof(double) * ldvt, Bf, sizeof(double) * nn, sizeof(double) * have, n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(S, Ss, sizeof(double) * have, hipMemcpyDeviceToDevice, st));
+  } else {
+    int ks = 0, k2 = 0; double dn = 0.0;
+    if (int rc = tsplit_f64(c, m, n, X, m, kk, 0.0, Af, m, Cc, kk, Bf, kk, Ss, &ks, &dn)) return rc;
+    if (c->last_split_path == 1) ++c->n_compl_sub; else ++c->n_compl_full;
+    REQUIRE(ks >= 1 && ks <= kk, "split returned an unexpected rank");
+    if (int rc = tsvd_f64(c, ks, ks, Cc, kk, Uc, ks, S2, Vc, ks, 0, 0.0, &k2, &dn)) return rc;
+    have = std::min(ks, k2);
+    GemmArgs gu = mk(Af, Uc, (double*)U, m, have, ks, m, ks, ldu);
+    HIPCHK(gemm_f64(gu, st));
+    GemmArgs gv = mk(Vc, Bf, (double*)Vt, have, n, ks, ks, kk, ldvt);
+    HIPCHK(gemm_f64(gv, st));
+    HIPCHK(hipMemcpyAsync(S, S2, sizeof(double) * have, hipMemcpyDeviceToDevice, st));
+  }
+  if (have < kk) {                   // directions the SVD did not deliver: random, singular value 0
+    const int r = kk - have;
+    hipLaunchKernelGGL(split_fill_kernel, dim3(256), dim3(256), 0, st, Ut, (int64_t)m * r, 0x5eedu);
+    HIPCHK(hipMemcpy2DAsync((double*)U + (size_t)have * ldu, sizeof(double) * ldu, Ut, sizeof(double) * m, sizeof(double) * m, r,
+                            hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(split_fill_kernel, dim3(256), dim3(256), 0, st, Vtt, (int64_t)r * n, 0xfeedu);
+    HIPCHK(hipMemcpy2DAsync((double*)Vt + have, sizeof(double) * ldvt, Vtt, sizeof(double) * r, sizeof(double) * r, n,
+                            hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemsetAsync((double*)S + have, 0, sizeof(double) * r, st));
+  }
+  // the complement condition and the isometry, by construction
+  for (int round = 0; round < 2; ++round) {
+    if (pl > 0) {
+      GemmArgs g1 = mk((const double*)QL, (const double*)U, TP, pl, kk, m, ldql, ldu, pl, 1, 0);
+      HIPCHK(gemm_f64(g1, st));
+      GemmArgs g2 = mk((const double*)QL, TP, (double*)U, m, kk, pl, ldql, pl, ldu);
+      g2.alpha = -1.0; g2.beta = 1.0;
+      HIPCHK(gemm_f64(g2, st));
+    }
+    if (int rc = qrpos_f64(c, m, kk, U, ldu, Ut, m, Rt, kk)) return rc;
+    HIPCHK(hipMemcpy2DAsync(U, sizeof(double) * ldu, Ut, sizeof(double) * m, sizeof(double) * m, kk, hipMemcpyDeviceToDevice, st));
+    if (pr > 0) {
+      GemmArgs g1 = mk((const double*)Vt, (const double*)QR, TP, kk, pr, n, ldvt, ldqr, kk, 0, 1);
+      HIPCHK(gemm_f64(g1, st));
+      GemmArgs g2 = mk(TP, (const double*)QR, (double*)Vt, kk, n, pr, kk, ldqr, ldvt);
+      g2.alpha = -1.0; g2.beta = 1.0;
+      HIPCHK(gemm_f64(g2, st));
+    }
+    if (int rc = lqpos_f64(c, kk, n, Vt, ldvt, Rt, kk, Vtt, kk)) return rc;
+    HIPCHK(hipMemcpy2DAsync(Vt, sizeof(double) * ldvt, Vtt, sizeof(double) * kk, sizeof(double) * kk, n, hipMemcpyDeviceToDevice, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return MPSK_OK;
+}
+
+int mpsk_ctx_complement_stats(mpsk_ctx* c, long* n_calls, long* n_subspace, long* n_full) {
+  REQUIRE(c, "ctx is NULL");
+  if (n_calls) *n_calls = c->n_compl;
+  if (n_subspace) *n_subspace = c->n_compl_sub;
+  if (n_full) *n_full = c->n_compl_full;
   return MPSK_OK;
 }
 

@@ -113,9 +113,16 @@ class MPOHamInfEnv:
     def __init__(self, psi, H, tol=1e-12, maxiter=100, rng=None):
         self.be = psi.be
         self.H, self.tol, self.maxiter = H, tol, maxiter
+        self.rng = np.random.default_rng(0) if rng is None else rng
+        self._start(psi)
+        self.ws = krylov.KrylovWorkspace(self.be)
+        self._cache = {}
+        self.recalculate(psi, tol)
+
+    def _start(self, psi):
+        """random start environments in the bond spaces of psi (mpohaminfenv.jl:40-44)"""
+        be, H, rng = self.be, self.H, self.rng
         n, odim = len(psi), H.odim
-        be = self.be
-        rng = np.random.default_rng(0) if rng is None else rng
         self.lw = [[be.upload(np.transpose(rng.random((H[s].chil[i], psi.AL[s].shape[0], psi.AL[s].shape[0])), (1, 2, 0)))
                     for s in range(n)] for i in range(odim)]
         self.rw = [[be.upload(np.transpose(rng.random((H[s].chir[i], psi.AR[s].shape[2], psi.AR[s].shape[2])), (1, 2, 0)))
@@ -124,13 +131,14 @@ class MPOHamInfEnv:
             for s in range(n):
                 self.lw[i][s] = DTensor(self.lw[i][s].buf, (H[s].chil[i],) + self.lw[i][s].shape[:2])
                 self.rw[i][s] = DTensor(self.rw[i][s].buf, (H[s].chir[i],) + self.rw[i][s].shape[:2])
-        self.ws = krylov.KrylovWorkspace(be)
-        self._cache = {}
-        self.recalculate(psi, tol)
 
     # ---- public ------------------------------------------------------------------------------
     def recalculate(self, psi, tol=None):
         tol = self.tol if tol is None else tol
+        n = len(psi)
+        if len(self.lw[0]) != n or any(self.lw[0][s].shape[1] != psi.AL[s].shape[0] or
+                                       self.rw[0][s].shape[1] != psi.AR[s].shape[2] for s in range(n)):
+            self._start(psi)                     # the bond spaces changed (changebonds): the old solutions do not fit
         self._calclw(psi, tol)
         self._calcrw(psi, tol)
         self.dependency = psi
