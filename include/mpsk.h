@@ -259,6 +259,23 @@ int mpsk_transfer_left(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, int 
                        int Drb, const void* GLin, const void* A, const void* Ab, void* GLout);
 int mpsk_transfer_right(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb,
                         int Drb, const void* A, const void* Ab, const void* GRin, void* GRout);
+/* The transfers with flags.  MPSK_TRANSFER_CANONICAL: the caller guarantees that level 0 of GLin (mpsk_transfer_left_ex) /
+ * level W-1 of GRin (mpsk_transfer_right_ex) is the identity and that A == Ab is an isometry on the contracted side
+ * (sum_{p,t} A[p,t,q] A[p,t,b] = delta_qb, resp. sum_{t,b} A[a,t,b] A[p,t,b] = delta_ap) -- the environment update of a finite
+ * chain in canonical form (FinEnv).  For a real slice in Jordan form (see mpsk_hac_create_ex) given with A and Ab the same
+ * pointer, the identity level of the result is then WRITTEN (exactly the identity, Dr x Dr resp. Dl x Dl), the interior
+ * levels come from the C (resp. B) blocks applied to A in one elementwise pass, and the finished level from the fold of
+ * mpsk_hac mode 3 applied to A: no stage-1 GEMM on any level, 2 d n D^3 + 2 d (W-1) D^3 flops instead of 4 d W D^3
+ * (Heisenberg: 24 D^3 instead of 40 D^3).  Everything else -- flag not set, slices with A blocks, dense-MPO slices,
+ * MPSK_C128, H == NULL, A != Ab -- is mpsk_transfer_left / mpsk_transfer_right bit for bit; so is every call under
+ * environment MPSK_TRANSFER_MODE=0.  Workspace: d^2 D^2 + (W-1) d Dl Dr doubles.  MPSK_HAC_CHECK=1 (debug, synchronises):
+ * a canonical-route call whose input identity level or Gram matrix of A is off by more than 1e-10 fails with
+ * MPSK_ERR_INVALID. */
+enum { MPSK_TRANSFER_CANONICAL = 1 };
+int mpsk_transfer_left_ex(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
+                          const void* GLin, const void* A, const void* Ab, int flags, void* GLout);
+int mpsk_transfer_right_ex(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
+                           const void* A, const void* Ab, const void* GRin, int flags, void* GRout);
 /* regularize!(v, lvec, rvec)   src/transfermatrix/transfermatrix.jl:70-76
  *   v[w] -= <lvec^T, v[w]> * rvec  for each of the W slabs [D1, D2]; lvec: [D2, D1]; rvec: [D1, D2] */
 int mpsk_regularize(mpsk_ctx* ctx, int W, int D1, int D2, void* v, const void* lvec, const void* rvec);

@@ -335,7 +335,9 @@ class Backend:
         check(self.lib.mpsk_ctx_complement_stats(self.ctx, C.byref(a), C.byref(b), C.byref(c)), "mpsk_ctx_complement_stats")
         return {"calls": a.value, "subspace": b.value, "full": c.value}
 
-    def transfer_left(self, H, GLin: DTensor, A: DTensor, Ab: DTensor, out: DTensor = None, cplx=False):
+    def transfer_left(self, H, GLin: DTensor, A: DTensor, Ab: DTensor, out: DTensor = None, cplx=False, canonical=False):
+        """mpsk_transfer_left; canonical=True promises that level 0 of GLin is the identity and that A (== Ab) is a left
+        isometry (MPSK_TRANSFER_CANONICAL): a real Jordan-form slice then takes the 24 D^3 route of mpsk_transfer_left_ex."""
         if cplx or getattr(H, "cplx", False):
             Dl, d, Dr = A.shape[0] // 2, A.shape[1], A.shape[2]
             Dlb, Drb = Ab.shape[0] // 2, Ab.shape[2]
@@ -356,11 +358,23 @@ class Backend:
         W = GLin.shape[0]
         Wout = H.Wr if H is not None else W
         y = self.empty(Wout, Drb, Dr) if out is None else out
+        if canonical and H is not None:
+            check(self.lib.mpsk_transfer_left_ex(self.ctx, H.handle, W, d, Dl, Dr, Dlb, Drb, GLin.ptr, A.ptr, Ab.ptr, 1, y.ptr),
+                  "mpsk_transfer_left_ex")
+            return y
         check(self.lib.mpsk_transfer_left(self.ctx, H.handle if H is not None else None, W, d, Dl, Dr, Dlb, Drb,
                                           GLin.ptr, A.ptr, Ab.ptr, y.ptr), "mpsk_transfer_left")
         return y
 
-    def transfer_right(self, H, GRin: DTensor, A: DTensor, Ab: DTensor, out: DTensor = None, cplx=False):
+    def transfer_left_ex(self, H, GLin: DTensor, A: DTensor, Ab: DTensor, canonical: bool = False, out: DTensor = None):
+        """mpsk_transfer_left_ex (real tensors); its presence tells FinEnv that the backend has the canonical route."""
+        return self.transfer_left(H, GLin, A, Ab, out=out, canonical=canonical)
+
+    def transfer_right_ex(self, H, GRin: DTensor, A: DTensor, Ab: DTensor, canonical: bool = False, out: DTensor = None):
+        return self.transfer_right(H, GRin, A, Ab, out=out, canonical=canonical)
+
+    def transfer_right(self, H, GRin: DTensor, A: DTensor, Ab: DTensor, out: DTensor = None, cplx=False, canonical=False):
+        """mpsk_transfer_right; canonical=True: level W-1 of GRin is the identity and A (== Ab) is a right isometry."""
         if cplx or getattr(H, "cplx", False):
             Dl, d, Dr = A.shape[0] // 2, A.shape[1], A.shape[2]
             Dlb, Drb = Ab.shape[0] // 2, Ab.shape[2]
@@ -381,6 +395,10 @@ class Backend:
         W = GRin.shape[0]
         Wout = H.Wl if H is not None else W
         y = self.empty(Wout, Dl, Dlb) if out is None else out
+        if canonical and H is not None:
+            check(self.lib.mpsk_transfer_right_ex(self.ctx, H.handle, W, d, Dl, Dr, Dlb, Drb, A.ptr, Ab.ptr, GRin.ptr, 1, y.ptr),
+                  "mpsk_transfer_right_ex")
+            return y
         check(self.lib.mpsk_transfer_right(self.ctx, H.handle if H is not None else None, W, d, Dl, Dr, Dlb, Drb,
                                            A.ptr, Ab.ptr, GRin.ptr, y.ptr), "mpsk_transfer_right")
         return y

@@ -61,6 +61,15 @@ struct mpsk_mposlice {
   MixPlan jr, jl;                  // out slab p <- in slab v of GR / w of GL
   std::vector<int> jr_p, jl_p;
   int jr_nseg = 0, jl_nseg = 0;
+  // canonical transfers (mpsk_transfer_left_ex / mpsk_transfer_right_ex on a Jordan-form slice): elementwise plans whose
+  // only input is the site tensor, in slab s = A[:, s, :]
+  //   tl: out slab t + d (v - 1) <- O[0,t,s,v]      v = 1 .. Wr-2 (C blocks), and v = Wr-1 (D block) when tl_dblock
+  //   tr: out slab t + d (w - 1) <- O[w,t,s,Wr-1]   w = 1 .. Wl-2 (B blocks)
+  // jtabL / jtabR: device segment tables [2][d][nseg] of the fold application (A offsets, B offsets), one per shape seen
+  MixPlan tl, tr;
+  bool tl_dblock = false;
+  mutable std::map<int64_t, int64_t*> jtabL;                          // key Dl
+  mutable std::map<std::pair<int64_t, int64_t>, int64_t*> jtabR;      // key (Dl, Dr)
   double O(int w, int t, int s, int v) const { return Ofull[w + (size_t)Wl * (t + d * (s + (size_t)d * v))]; }
   // dense slice (mpsk_mposlice_create_dense): stage 2 of dAC / the transfers is the fp64 GEMM
   //   T2[:, (t,v)] = T1[:, (s,w)] Od[(s,w), (t,v)]  on intermediates whose K index (s,w) has ONE stride;
@@ -466,6 +475,18 @@ static int mposlice_build(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l
       HIPCHK(mix_plan_create(jr, d * d, Wr, &s->jr));
       HIPCHK(mix_plan_create(jl, d * d, Wl, &s->jl));
       s->jordan = s->jr_nseg > 0 && s->jl_nseg > 0;
+      if (s->jordan) {
+        std::vector<MixTerm> tl, tr;
+        for (int t = 0; t < d; ++t)
+          for (int si = 0; si < d; ++si) {
+            for (int v = 1; v < Wr; ++v)
+              if (s->O(0, t, si, v) != 0.0) { tl.push_back({t + d * (v - 1), si, s->O(0, t, si, v)}); if (v == Wr - 1) s->tl_dblock = true; }
+            for (int w = 1; w < Wl - 1; ++w)
+              if (s->O(w, t, si, Wr - 1) != 0.0) tr.push_back({t + d * (w - 1), si, s->O(w, t, si, Wr - 1)});
+          }
+        HIPCHK(mix_plan_create(tl, d * (Wr - (s->tl_dblock ? 1 : 2)), d, &s->tl));
+        HIPCHK(mix_plan_create(tr, d * (Wl - 2), d, &s->tr));
+      }
     }
   }
   if (dense) {
@@ -522,6 +543,10 @@ int mpsk_mposlice_destroy(mpsk_mposlice* s) {
   mix_plan_destroy(&s->rc);
   mix_plan_destroy(&s->jr);
   mix_plan_destroy(&s->jl);
+  mix_plan_destroy(&s->tl);
+  mix_plan_destroy(&s->tr);
+  for (auto& kv : s->jtabL) (void)hipFree(kv.second);
+  for (auto& kv : s->jtabR) (void)hipFree(kv.second);
   if (s->d_Od) (void)hipFree(s->d_Od);
   if (s->d_OdR) (void)hipFree(s->d_OdR);
   for (auto& kv : s->dtab) (void)hipFree(kv.second);
@@ -1313,6 +1338,181 @@ int mpsk_dAC2(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int
 // --------------------------------------------------------------------------------------------
 // transfers
 // --------------------------------------------------------------------------------------------
+// ---- canonical transfers of a Jordan-form slice (mpsk_transfer_left_ex / mpsk_transfer_right_ex) ----------------------
+// With level 0 of GLin the identity and A = Ab a left isometry (sum_{p,t} A[p,t,q] A[p,t,b] = delta_qb) the levels of
+//   GLout[v][q,b] = sum GLin[w][p,a] A[a,s,b] O[w,t,s,v] A[p,t,q]
+// decouple, because a Jordan-form O feeds v < W-1 from level 0 alone:
+//   v = 0          GLout[0] = A^T A = 1                                                   written, not computed
+//   0 < v < W-1    GLout[v] = A^T T2[v],  T2[v][:,t,:] = sum_s O[0,t,s,v] A[:,s,:]        one elementwise pass, no stage 1
+//   v = W-1        GLout[W-1] = A^T T,    T[:,t,:] = sum_s GLc[(s,t)] A[:,s,:] + sum_s O[0,t,s,W-1] A[:,s,:]
+// with GLc the left fold of mpsk_hac mode 3 (hac_jordan_prepare), applied by the per-batch-table GEMM of that mode.  T is
+// the last slab of T2, so ONE batched TN GEMM produces the levels 1 .. W-1.  Heisenberg: 8 D^3 (fold) + 16 D^3 instead of
+// 20 D^3 + 20 D^3.  transfer_right is the mirror image: level W-1 is the identity, 0 < w < W-1 come from the B blocks
+// alone, X[w][:,t,:] = sum_s O[w,t,s,W-1] A[:,s,:], level 0 from the right fold, X[0][:,t,:] = sum_s A[:,s,:] GRc0[(s,t)]
+// (start level, C blocks and the D block), and GRout[w][a,p] = sum_{t,b} X[w][a,t,b] A[p,t,b] is one batched NT GEMM.
+// MPSK_TRANSFER_MODE=0 keeps the dense three-stage route (A/B runs).
+static size_t up32(size_t n) { return (n + 31) & ~(size_t)31; }      // 256-B aligned parts of the workspace
+
+static bool transfer_canonical_ok(const mpsk_mposlice* H, int flags, const void* A, const void* Ab, int Dl, int Dr,
+                                  int Dlb, int Drb) {
+  if (!(flags & MPSK_TRANSFER_CANONICAL) || !H || !H->jordan || H->dtype != MPSK_F64 || dense_route(H)) return false;
+  if (A != Ab || Dl != Dlb || Dr != Drb) return false;
+  const char* ev = getenv("MPSK_TRANSFER_MODE");
+  return !(ev && ev[0] == '0');
+}
+
+static bool hac_check_on() { const char* ev = getenv("MPSK_HAC_CHECK"); return ev && ev[0] == '1'; }
+
+// MPSK_HAC_CHECK=1 (debug, synchronises): the promises behind MPSK_TRANSFER_CANONICAL -- the identity level of the input
+// environment (n x n at G) and the isometry of A on the contracted side (Gram matrix through c->ws) -- hold to 1e-10
+static int transfer_canonical_check(mpsk_ctx* c, const char* who, const double* G, int n, const double* A, int d, int Dl,
+                                    int Dr, bool left) {
+  double dg = 0.0, da = 0.0;
+  if (int rc = identity_deviation(c, G, n, &dg)) return rc;
+  const int m = left ? Dr : Dl;
+  if (int rc = ensure_ws(c, sizeof(double) * (size_t)m * m)) return rc;
+  double* gram = (double*)c->ws;
+  if (left) {        // A^T A over (p, t)
+    GemmArgs g = mk(A, A, gram, Dr, Dr, Dl * d, (int64_t)Dl * d, (int64_t)Dl * d, Dr, 1, 0);
+    HIPCHK(gemm_f64(g, c->stream));
+  } else {           // A A^T over (t, b)
+    std::vector<int64_t> sa;
+    for (int t = 0; t < d; ++t) sa.push_back((int64_t)t * Dl);
+    GemmArgs g = mk(A, A, gram, Dl, Dl, Dr, (int64_t)Dl * d, (int64_t)Dl * d, Dl, 0, 1);
+    HIPCHK(gemm_segments(g, sa, sa, c->stream));
+  }
+  if (int rc = identity_deviation(c, gram, m, &da)) return rc;
+  if (!(dg <= 1e-10 && da <= 1e-10)) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "MPSK_HAC_CHECK: %s is not canonical (max|G[identity level] - I| = %.3e, max|%s - I| = %.3e)",
+             who, dg, left ? "A^T A" : "A A^T", da);
+    return fail(MPSK_ERR_INVALID, msg);
+  }
+  return MPSK_OK;
+}
+
+// device segment tables [2][d][nseg] of the fold applications, cached on the slice per shape
+static int jordan_tab(const mpsk_mposlice* H, bool left, int Dl, int Dr, const int64_t** out) {
+  if (left) { auto it = H->jtabL.find(Dl); if (it != H->jtabL.end()) { *out = it->second; return MPSK_OK; } }
+  else { auto it = H->jtabR.find({Dl, Dr}); if (it != H->jtabR.end()) { *out = it->second; return MPSK_OK; } }
+  const int d = H->d, n = left ? H->jl_nseg : H->jr_nseg;
+  const std::vector<int>& plist = left ? H->jl_p : H->jr_p;
+  const int64_t tL = (int64_t)Dl * d * Dl, tR = (int64_t)Dr * d * Dr;
+  std::vector<int64_t> h((size_t)2 * d * n);
+  for (int t = 0; t < d; ++t)
+    for (int k = 0; k < n; ++k) {
+      const int p = plist[(size_t)t * n + k], si = p % d, tt = p / d;
+      if (left) { h[(size_t)t * n + k] = tt * tL + (int64_t)si * Dl; h[(size_t)(d + t) * n + k] = (int64_t)si * Dl; }      // GLc[(s,tt)], A[:,s,:]
+      else { h[(size_t)t * n + k] = (int64_t)si * Dl; h[(size_t)(d + t) * n + k] = tt * tR + (int64_t)si * Dr; }          // A[:,s,:], GRc0[(s,tt)]
+    }
+  int64_t* p = nullptr;
+  if (hipMalloc(&p, sizeof(int64_t) * h.size()) != hipSuccess) return fail(MPSK_ERR_NOMEM, "transfer segment table hipMalloc failed");
+  if (hipMemcpy(p, h.data(), sizeof(int64_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(MPSK_ERR_HIP, "transfer segment table upload failed");
+  }
+  if (left) H->jtabL.emplace(Dl, p); else H->jtabR.emplace(std::make_pair((int64_t)Dl, (int64_t)Dr), p);
+  *out = p;
+  return MPSK_OK;
+}
+
+static int transfer_left_canonical(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dr, const double* GLin, const double* A,
+                                   double* GLout) {
+  const int d = H->d, Wr = H->Wr, n2 = H->jl_nseg;
+  if (hac_check_on())
+    if (int rc = transfer_canonical_check(c, "mpsk_transfer_left_ex", GLin, Dl, A, d, Dl, Dr, true)) return rc;
+  const size_t slab = (size_t)Dl * d * Dr;                  // one level of T2
+  const int64_t tL = (int64_t)Dl * d * Dl;                  // one t-group of GLc
+  const size_t nL = up32((size_t)d * tL);
+  if (int rc = ensure_ws(c, sizeof(double) * (nL + slab * (Wr - 1)))) return rc;
+  const int64_t* tab = nullptr;
+  if (int rc = jordan_tab(H, true, Dl, Dr, &tab)) return rc;
+  double* GLc = (double*)c->ws;
+  double* T2 = GLc + nL;                                    // slab v - 1 for v = 1 .. Wr-1
+  double* T = T2 + slab * (Wr - 2);
+  // GLc[(s,t)] = sum_{w>0} O[w,t,s,W-1] GLin[w]
+  SlabIndex il{1 << 30, 1, (int64_t)Dl * Dl, 0, 0, (int64_t)Dl}, ol{d, 1 << 30, (int64_t)Dl, tL, 0, (int64_t)d * Dl};
+  HIPCHK(mix_apply(H->jl, GLin, il, GLc, ol, Dl, Dl, c->stream));
+  // T2[v][:,t,:] = sum_s O[0,t,s,v] A[:,s,:]     (the D-block part of T included when the slice has one)
+  SlabIndex ia{1 << 30, 1, (int64_t)Dl, 0, 0, (int64_t)Dl * d}, ot{d, 1 << 30, (int64_t)Dl, (int64_t)slab, 0, (int64_t)Dl * d};
+  HIPCHK(mix_apply(H->tl, A, ia, T2, ot, Dl, Dr, c->stream));
+  // T[:,t,:] (+)= sum_k GLc[(s_k,t)] A[:,s_k,:]     (batch over t)
+  GemmArgs g = mk(GLc, A, T, Dl, Dr, Dl, (int64_t)Dl * d, (int64_t)Dl * d, (int64_t)Dl * d);
+  g.batch = d; g.bsA = 0; g.bsB = 0; g.bsC = (int64_t)Dl;
+  g.beta = H->tl_dblock ? 1.0 : 0.0;
+  g.nseg = n2; g.zsegA = tab; g.zsegB = tab + (size_t)d * n2;
+  g.tabs_even = Dl % 2 == 0;
+  g.tag = 1;
+  HIPCHK(gemm_f64(g, c->stream));
+  HIPCHK(identity_slab(GLout, Dr, c->stream));
+  // GLout[v][q,b] = sum_{(p,t)} A[(p,t),q] T2[v][(p,t),b]     v = 1 .. Wr-1
+  GemmArgs g3 = mk(A, T2, GLout + (size_t)Dr * Dr, Dr, Dr, Dl * d, (int64_t)Dl * d, (int64_t)Dl * d, Dr, 1, 0);
+  g3.batch = Wr - 1; g3.bsA = 0; g3.bsB = (int64_t)slab; g3.bsC = (int64_t)Dr * Dr;
+  HIPCHK(gemm_f64(g3, c->stream));
+  return MPSK_OK;
+}
+
+static int transfer_right_canonical(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dr, const double* A, const double* GRin,
+                                    double* GRout) {
+  const int d = H->d, Wl = H->Wl, Wr = H->Wr, n1 = H->jr_nseg;
+  if (hac_check_on())
+    if (int rc = transfer_canonical_check(c, "mpsk_transfer_right_ex", GRin + (size_t)(Wr - 1) * Dr * Dr, Dr, A, d, Dl, Dr, false))
+      return rc;
+  const size_t slab = (size_t)Dl * d * Dr;                  // one level of X
+  const int64_t tR = (int64_t)Dr * d * Dr;                  // one t-group of GRc0
+  const size_t nR = up32((size_t)d * tR);
+  if (int rc = ensure_ws(c, sizeof(double) * (nR + slab * (Wl - 1)))) return rc;
+  const int64_t* tab = nullptr;
+  if (int rc = jordan_tab(H, false, Dl, Dr, &tab)) return rc;
+  double* GRc = (double*)c->ws;
+  double* X = GRc + nR;                                     // slab w for w = 0 .. Wl-2
+  // GRc0[(s,t)] = sum_v O[0,t,s,v] GRin[v]
+  SlabIndex ir{1 << 30, 1, (int64_t)Dr * Dr, 0, 0, (int64_t)Dr}, orr{d, 1 << 30, (int64_t)Dr, tR, 0, (int64_t)d * Dr};
+  HIPCHK(mix_apply(H->jr, GRin, ir, GRc, orr, Dr, Dr, c->stream));
+  // X[w][:,t,:] = sum_s O[w,t,s,W-1] A[:,s,:]     w = 1 .. Wl-2
+  SlabIndex ia{1 << 30, 1, (int64_t)Dl, 0, 0, (int64_t)Dl * d}, ox{d, 1 << 30, (int64_t)Dl, (int64_t)slab, 0, (int64_t)Dl * d};
+  HIPCHK(mix_apply(H->tr, A, ia, X + slab, ox, Dl, Dr, c->stream));
+  // X[0][:,t,:] = sum_k A[:,s_k,:] GRc0[(s_k,t)]     (batch over t)
+  GemmArgs g = mk(A, GRc, X, Dl, Dr, Dr, (int64_t)Dl * d, (int64_t)Dr * d, (int64_t)Dl * d);
+  g.batch = d; g.bsA = 0; g.bsB = 0; g.bsC = (int64_t)Dl;
+  g.nseg = n1; g.zsegA = tab; g.zsegB = tab + (size_t)d * n1;
+  g.tabs_even = Dl % 2 == 0 && Dr % 2 == 0;
+  g.tag = 1;
+  HIPCHK(gemm_f64(g, c->stream));
+  HIPCHK(identity_slab(GRout + (size_t)(Wl - 1) * Dl * Dl, Dl, c->stream));
+  // GRout[w][a,p] = sum_t sum_b X[w][a,t,b] A[p,t,b]     w = 0 .. Wl-2
+  std::vector<int64_t> sa;
+  for (int t = 0; t < d; ++t) sa.push_back((int64_t)t * Dl);
+  GemmArgs g3 = mk(X, A, GRout, Dl, Dl, Dr, (int64_t)Dl * d, (int64_t)Dl * d, Dl, 0, 1);
+  g3.batch = Wl - 1; g3.bsA = (int64_t)slab; g3.bsB = 0; g3.bsC = (int64_t)Dl * Dl;
+  HIPCHK(gemm_segments(g3, sa, sa, c->stream));
+  return MPSK_OK;
+}
+
+int mpsk_transfer_left_ex(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
+                          const void* GLin, const void* A, const void* Ab, int flags, void* GLout) {
+  REQUIRE(c && GLin && A && Ab && GLout, "NULL argument");
+  REQUIRE((flags & ~MPSK_TRANSFER_CANONICAL) == 0, "unknown flags");
+  if (transfer_canonical_ok(H, flags, A, Ab, Dl, Dr, Dlb, Drb)) {
+    REQUIRE(Dl > 0 && Dr > 0, "dimensions must be positive");
+    HIPCHK(hipSetDevice(c->device));
+    return transfer_left_canonical(c, H, Dl, Dr, (const double*)GLin, (const double*)A, (double*)GLout);
+  }
+  return mpsk_transfer_left(c, H, W, d, Dl, Dr, Dlb, Drb, GLin, A, Ab, GLout);
+}
+
+int mpsk_transfer_right_ex(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
+                           const void* A, const void* Ab, const void* GRin, int flags, void* GRout) {
+  REQUIRE(c && GRin && A && Ab && GRout, "NULL argument");
+  REQUIRE((flags & ~MPSK_TRANSFER_CANONICAL) == 0, "unknown flags");
+  if (transfer_canonical_ok(H, flags, A, Ab, Dl, Dr, Dlb, Drb)) {
+    REQUIRE(Dl > 0 && Dr > 0, "dimensions must be positive");
+    HIPCHK(hipSetDevice(c->device));
+    return transfer_right_canonical(c, H, Dl, Dr, (const double*)A, (const double*)GRin, (double*)GRout);
+  }
+  return mpsk_transfer_right(c, H, W, d, Dl, Dr, Dlb, Drb, A, Ab, GRin, GRout);
+}
+
 int mpsk_transfer_left(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
                        const void* GLin, const void* A, const void* Ab, void* GLout) {
   REQUIRE(c && GLin && A && Ab && GLout, "NULL argument");

@@ -160,6 +160,20 @@ hipError_t copy_strided(const double* src, int64_t srs, int64_t scs, double* dst
   return hipGetLastError();
 }
 
+// G = identity (n x n, contiguous): the level a canonical transfer knows without computing it
+__global__ __launch_bounds__(256) void identity_slab_kernel(double* __restrict__ G, int n) {
+  const int64_t total = (int64_t)n * n;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x)
+    G[e] = (e % n == e / n) ? 1.0 : 0.0;
+}
+hipError_t identity_slab(double* G, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  int64_t nb = ((int64_t)n * n + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(identity_slab_kernel, dim3((unsigned)nb), dim3(256), 0, s, G, n);
+  return hipGetLastError();
+}
+
 // -------------------------------------------------------------------------------------------
 // vector kernels
 // -------------------------------------------------------------------------------------------

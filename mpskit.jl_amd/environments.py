@@ -42,6 +42,14 @@ class FinEnv:
         self.ldeps = [None] * L
         self.rdeps = [None] * L
         self.n_transfers = 0
+        self.canonical = True          # MultipleEnvironments switches it off for the terms of a sum
+
+    def _canonical(self, psi):
+        """the condition ddAC uses for mode 3: a plain FinEnv on a real state keeps level 0 of every left environment and
+        level W-1 of every right environment the identity, and AL / AR are isometries -- the promise behind the canonical
+        route of mpsk_transfer_left_ex / mpsk_transfer_right_ex.  Subclasses and backends without that entry: dense."""
+        return (self.canonical and type(self) is FinEnv and not getattr(psi, "cplx", False)
+                and hasattr(self.be, "transfer_left_ex"))
 
     def rightenv(self, ind, psi):  # FinEnv.jl:114-129
         L = len(psi)
@@ -51,9 +59,10 @@ class FinEnv:
                 a = i
                 break
         if a is not None:
+            kw = {"canonical": True} if self._canonical(psi) else {}
             for j in range(a, ind, -1):
                 ar = psi.AR(j)
-                self.rightenvs[j] = self.be.transfer_right(self.opp[j], self.rightenvs[j + 1], ar, ar)
+                self.rightenvs[j] = self.be.transfer_right(self.opp[j], self.rightenvs[j + 1], ar, ar, **kw)
                 self.rdeps[j] = ar
                 self.n_transfers += 1
         return self.rightenvs[ind + 1]
@@ -65,9 +74,10 @@ class FinEnv:
                 a = i
                 break
         if a is not None:
+            kw = {"canonical": True} if self._canonical(psi) else {}
             for j in range(a, ind):
                 al = psi.AL(j)
-                self.leftenvs[j + 1] = self.be.transfer_left(self.opp[j], self.leftenvs[j], al, al)
+                self.leftenvs[j + 1] = self.be.transfer_left(self.opp[j], self.leftenvs[j], al, al, **kw)
                 self.ldeps[j] = al
                 self.n_transfers += 1
         return self.leftenvs[ind]
@@ -82,6 +92,9 @@ class MultipleEnvironments:
 
     def __init__(self, H, envs):
         self.H, self.envs = H, list(envs)
+        for e in self.envs:                  # the terms of a sum keep the dense transfers (as ddAC keeps their dense operator)
+            if isinstance(e, FinEnv):
+                e.canonical = False
 
     def recalculate(self, psi, tol=None):
         for e in self.envs:
