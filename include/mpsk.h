@@ -215,6 +215,32 @@ int mpsk_dC(mpsk_ctx* ctx, int W, int Dlo, int Dl, int Dr, const void* GL, const
 int mpsk_dAC2(mpsk_ctx* ctx, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dlo, int Dl, int Dr,
               const void* GL, const void* GR, const void* x2, void* y2);
 
+/* ---- projections on the tangent space of ANOTHER state: derivatives.jl:210-226 (ac_proj / ac2_proj), the site step of
+ * approximate (src/algorithms/approximate/fvomps.jl).  The tensors of the state ABOVE are contracted with environments whose
+ * bra legs belong to the state BELOW, so both environments are rectangular:
+ *   GL: Wl slabs [Dlo, Dl]  (Dlo = left bond of the state below, Dl = of the state above)
+ *   GR: Wr slabs [Dr, Dro]  column-major, slab stride Dr Dro  (Dr = right bond of the state above, Dro = of the state below)
+ * mpsk_dAC_proj == ac_proj:  y[p,t,q] = sum GL[w][p,a] x[a,s,b] O[w,t,s,v] GR[v][b,q],  x: [Dl, d, Dr], y: [Dlo, d, Dro].
+ *   Every route of mpsk_dAC: sparse slices (slab mix), dense slices above the crossover of mpsk_mposlice_create_dense
+ *   (stage 2 as one MFMA GEMM; MPSK_DENSE_ROUTE honoured), MPSK_C128 slices (interleaved complex operands, planar copy of GR
+ *   in the workspace).  The order of contraction is fixed, left first: 2 Wl d Dlo Dl Dr + 2 Wr d Dlo Dr Dro flops; workspace
+ *   Dlo d Dr (Wl + Wr) doubles (twice that, plus the planes of x and GR, for complex).  Dro == Dr is mpsk_dAC bit for bit. */
+int mpsk_dAC_proj(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR,
+                  const void* x, void* y);
+/* mpsk_dAC2_proj == ac2_proj applied to the two factors of the state above, AC [Dl, d1, Dm] and AR [Dm, d2, Dr] (as
+ * mpsk_dAC2_product takes them); Y: [Dlo, d1, Dro, d2] (the layout of mpsk_dAC2's result).
+ *   MPSK_F64: factorised through the middle bond, Y = sum_u Lhalf[u] Rhalf[u] with Lhalf[u] [Dlo, d1, Dm] and Rhalf[u]
+ *   [Dm, d2, Dro] (the half contractions of mpsk_dAC2_product, shared with it), the product ONE GEMM launch with K = Wm Dm.
+ *   The two-site tensor of the state above is never formed:
+ *     flops ~ 2 Wl d1 Dlo Dl Dm + 2 Wr d2 Dm Dr Dro + 2 Wm d1 d2 Dlo Dro Dm   -- no D_above^3 d^2 term.
+ *   Both slice kinds; workspace (Wl + Wm) d1 Dlo Dm + (Wr + Wm) d2 Dm Dro doubles.
+ *   MPSK_C128: theta = AC AR (2 Dl d1 Dr d2 doubles) is built with d2 complex GEMMs in the ctx's expansion scratch -- the
+ *   buffer mpsk_complement_tsvd uses for its operands, grown on demand, separate from the workspace -- and the rectangular
+ *   form of the complex mpsk_dAC2 route runs on it (sparse slices; interleaved complex operands): workspace
+ *   2 (Dl d1 Dr d2 + Wr Dr Dro) + 2 Dlo d1 Dr d2 (Wl + Wr) doubles, plus 4 Dl d1 Dm doubles of GEMM scratch. */
+int mpsk_dAC2_proj(mpsk_ctx* ctx, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dlo, int Dl, int Dm, int Dr, int Dro,
+                   const void* GL, const void* GR, const void* AC, const void* AR, void* Y);
+
 /* ---- bond expansion of a uniform state: src/algorithms/changebonds/optimalexpand.jl:16-67 --------------------------
  * mpsk_dAC2_product == dd-AC2(i, psi, H, envs) * (AC[i] * AR[i+1])   optimalexpand.jl:22-23 (MPOHamiltonian) and :51-52
  * (DenseMPO), derivatives.jl:119-158, WITHOUT forming the two-site tensor:
@@ -361,6 +387,10 @@ int mpsk_copy2d(mpsk_ctx* ctx, int rows, int cols, const void* src, int64_t lds,
  * KrylovKit needs these of the iterate type (quasiparticle_state.jl:357-411 is the in-repo example). */
 int mpsk_vdot(mpsk_ctx* ctx, int64_t n, const void* x, const void* y, double* host_out);
 int mpsk_vnrm2(mpsk_ctx* ctx, int64_t n, const void* x, double* host_out);
+/* host_out[0] = |x - y|^2, host_out[1] = |x|^2 in ONE pass over both vectors (one launch + the final reduction of
+ * mpsk_vdot; synchronises like it): norm(AC' - AC) / norm(AC') of fvomps.jl:66, taken on every site visit of approximate.
+ * Follows mpsk_ctx_set_dtype: under MPSK_C128 n counts complex elements.  x == y gives exactly 0. */
+int mpsk_vdiff_nrm2(mpsk_ctx* ctx, int64_t n, const void* x, const void* y, double* host_out);
 int mpsk_vaxpby(mpsk_ctx* ctx, int64_t n, double alpha, const void* x, double beta, void* y);
 int mpsk_vscal(mpsk_ctx* ctx, int64_t n, double alpha, void* x);
 /* y = (I (x) J) x, J = [[0,-1],[1,0]], on interleaved row pairs of a tensor whose first dimension is even: the

@@ -310,6 +310,33 @@ class Backend:
               "mpsk_dAC2_product")
         return y
 
+    def dAC_proj(self, H, GL: DTensor, GR: DTensor, x: DTensor, out: DTensor = None):
+        """mpsk_dAC_proj (ac_proj): the matvec with rectangular environments, GL (Wl, Dlo, Dl) and GR (Wr, Dr, Dro); x is
+        [Dl, d, Dr], the result [Dlo, d, Dro].  A complex slice takes interleaved operands (doubled first dimensions)."""
+        m = 2 if getattr(H, "cplx", False) else 1
+        Dlx, d, Dr = x.shape
+        Wl, Dlo, Dl = GL.shape
+        Wr, Dr2, Dro = GR.shape
+        assert Dlx == m * Dl and Dr2 == m * Dr and Wl == H.Wl and Wr == H.Wr and d == H.d, (GL.shape, GR.shape, x.shape)
+        y = self.empty(Dlo, d, Dro) if out is None else out
+        check(self.lib.mpsk_dAC_proj(self.ctx, H.handle, Dlo // m, Dl, Dr, Dro, GL.ptr, GR.ptr, x.ptr, y.ptr), "mpsk_dAC_proj")
+        return y
+
+    def dAC2_proj(self, H1, H2, GL: DTensor, GR: DTensor, AC: DTensor, AR: DTensor, out: DTensor = None):
+        """mpsk_dAC2_proj (ac2_proj) on the two factors of the state above, AC [Dl, d1, Dm] and AR [Dm, d2, Dr], with
+        GL (Wl, Dlo, Dl) and GR (Wr, Dr, Dro).  Returns Y[Dlo, d1, Dro, d2]; the two-site tensor is not formed (fp64)."""
+        m = 2 if getattr(H1, "cplx", False) else 1
+        Dlx, d1, Dm = AC.shape
+        Dmx, d2, Dr = AR.shape
+        Wl, Dlo, Dl = GL.shape
+        Wr, Dr2, Dro = GR.shape
+        assert (Dlx == m * Dl and Dmx == m * Dm and Dr2 == m * Dr and Wl == H1.Wl and Wr == H2.Wr and d1 == H1.d
+                and d2 == H2.d), (GL.shape, GR.shape, AC.shape, AR.shape)
+        y = self.empty(Dlo, d1, Dro, d2) if out is None else out
+        check(self.lib.mpsk_dAC2_proj(self.ctx, H1.handle, H2.handle, Dlo // m, Dl, Dm, Dr, Dro, GL.ptr, GR.ptr, AC.ptr,
+                                      AR.ptr, y.ptr), "mpsk_dAC2_proj")
+        return y
+
     def complement_tsvd(self, Y: DTensor, QL: DTensor, QR: DTensor, k: int):
         """mpsk_complement_tsvd: the k leading singular triplets of (1 - QL QL^T) Y (1 - QR^T QR); Y (m, n), QL (m, pl)
         with orthonormal columns or None, QR (pr, n) with orthonormal rows or None.  Returns (U (m, kept), S (kept,),
@@ -642,6 +669,14 @@ class Backend:
         out = C.c_double()
         check(self.lib.mpsk_vnrm2(self.ctx, x.size, x.ptr, C.byref(out)), "mpsk_vnrm2")
         return out.value
+
+    def vdiff_nrm2(self, x: DTensor, y: DTensor):
+        """mpsk_vdiff_nrm2: (|x - y|^2, |x|^2) from one pass over both vectors (interleaved complex tensors: the same sums
+        over their doubles)."""
+        assert x.size == y.size, (x.shape, y.shape)
+        out = (C.c_double * 2)()
+        check(self.lib.mpsk_vdiff_nrm2(self.ctx, x.size, x.ptr, y.ptr, out), "mpsk_vdiff_nrm2")
+        return out[0], out[1]
 
     def axpby(self, alpha, x: DTensor, beta, y: DTensor):
         check(self.lib.mpsk_vaxpby(self.ctx, x.size, float(alpha), x.ptr, float(beta), y.ptr), "mpsk_vaxpby")

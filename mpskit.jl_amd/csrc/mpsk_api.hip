@@ -625,12 +625,14 @@ static hipError_t cx_planes(const double* z, size_t n, double* re, double* im, h
 }
 static size_t ev2(size_t v) { return (v + 1) & ~(size_t)1; }
 
-// GRp: planar copy of GR ([re plane | im plane], each Wr Dr Dr doubles) if the caller has one (prepared operator), else null
-static int dAC_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const double* GL, const double* GR,
-                    const double* GRp, const double* x, double* y) {   // GRp planes are ev2(Wr Dr Dr) doubles apart
+// GRp: planar copy of GR ([re plane | im plane], each Wr Dr Dro doubles) if the caller has one (prepared operator), else null.
+// Dro: columns of the GR slabs [Dr, Dro] = last dimension of y (the square matvec passes Dro = Dr; mpsk_dAC_proj the bond
+// dimension of the state below).
+static int dAC_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const double* GL, const double* GR,
+                    const double* GRp, const double* x, double* y) {   // GRp planes are ev2(Wr Dr Dro) doubles apart
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
-  const size_t nx = (size_t)Dl * d * Dr, nG = (size_t)Wr * Dr * Dr, slab = (size_t)2 * Dlo * d * Dr;
+  const size_t nx = (size_t)Dl * d * Dr, nG = (size_t)Wr * Dr * Dro, slab = (size_t)2 * Dlo * d * Dr;
   const size_t o_g = 2 * ev2(nx), o_t1 = o_g + (GRp ? 0 : 2 * ev2(nG)), o_t2 = o_t1 + slab * Wl;
   if (int rc = ensure_ws(c, sizeof(double) * (o_t2 + slab * Wr))) return rc;
   double* xp = (double*)c->ws;
@@ -652,9 +654,9 @@ static int dAC_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   std::vector<int> sj;
   for (int v = 0; v < Wr; ++v)
     if (H->col_used[v])
-      for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)v * slab); sb.push_back((int64_t)(pl * gplane + (size_t)v * Dr * Dr)); sj.push_back(pl); }
-  if (sa.empty()) { HIPCHK(zero_async(y, sizeof(double) * slab, c->stream)); return MPSK_OK; }
-  GemmArgs g3 = mk(T2, gr, y, 2 * Dlo * d, Dr, Dr, (int64_t)2 * Dlo * d, Dr, (int64_t)2 * Dlo * d);
+      for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)v * slab); sb.push_back((int64_t)(pl * gplane + (size_t)v * Dr * Dro)); sj.push_back(pl); }
+  if (sa.empty()) { HIPCHK(zero_async(y, sizeof(double) * 2 * Dlo * d * Dro, c->stream)); return MPSK_OK; }
+  GemmArgs g3 = mk(T2, gr, y, 2 * Dlo * d, Dro, Dr, (int64_t)2 * Dlo * d, Dr, (int64_t)2 * Dlo * d);
   g3.cplx = 1;
   HIPCHK(gemm_segments(g3, sa, sb, c->stream, &sj));
   return MPSK_OK;
@@ -687,12 +689,13 @@ static int dC_c128(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, const double* GL
 
 static int pair_plan(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, const MixPlan** out);
 
-static int dAC2_c128(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dlo, int Dl, int Dr,
+// x2: [Dl, d1, Dr, d2]; GR: Wr slabs [Dr, Dro]; y2: [Dlo, d1, Dro, d2] (Dro = Dr: mpsk_dAC2)
+static int dAC2_c128(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dlo, int Dl, int Dr, int Dro,
                      const double* GL, const double* GR, const double* x2, double* y2) {
   HIPCHK(hipSetDevice(c->device));
   const int d1 = H1->d, d2 = H2->d, Wl = H1->Wl, Wr = H2->Wr;
-  const size_t nx = (size_t)Dl * d1 * Dr * d2, nG = (size_t)Wr * Dr * Dr;
-  const size_t plane = (size_t)2 * Dlo * d1 * Dr, slab = plane * d2;
+  const size_t nx = (size_t)Dl * d1 * Dr * d2, nG = (size_t)Wr * Dr * Dro;
+  const size_t plane = (size_t)2 * Dlo * d1 * Dr, slab = plane * d2, oplane = (size_t)2 * Dlo * d1 * Dro;
   const size_t o_g = 2 * ev2(nx), o_t1 = o_g + 2 * ev2(nG), o_t2 = o_t1 + slab * Wl;
   if (int rc = ensure_ws(c, sizeof(double) * (o_t2 + slab * Wr))) return rc;
   double* xp = (double*)c->ws;
@@ -713,10 +716,10 @@ static int dAC2_c128(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* 
   std::vector<int> sj;
   for (int v = 0; v < Wr; ++v)
     if (H2->col_used[v])
-      for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)v * slab); sb.push_back((int64_t)(pl * ev2(nG) + (size_t)v * Dr * Dr)); sj.push_back(pl); }
-  if (sa.empty()) { HIPCHK(zero_async(y2, sizeof(double) * slab, c->stream)); return MPSK_OK; }
-  GemmArgs g3 = mk(T2, g, y2, 2 * Dlo * d1, Dr, Dr, (int64_t)2 * Dlo * d1, Dr, (int64_t)2 * Dlo * d1);
-  g3.batch = d2; g3.bsA = (int64_t)plane; g3.bsB = 0; g3.bsC = (int64_t)plane; g3.cplx = 1;
+      for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)v * slab); sb.push_back((int64_t)(pl * ev2(nG) + (size_t)v * Dr * Dro)); sj.push_back(pl); }
+  if (sa.empty()) { HIPCHK(zero_async(y2, sizeof(double) * oplane * d2, c->stream)); return MPSK_OK; }
+  GemmArgs g3 = mk(T2, g, y2, 2 * Dlo * d1, Dro, Dr, (int64_t)2 * Dlo * d1, Dr, (int64_t)2 * Dlo * d1);
+  g3.batch = d2; g3.bsA = (int64_t)plane; g3.bsB = 0; g3.bsC = (int64_t)oplane; g3.cplx = 1;
   HIPCHK(gemm_segments(g3, sa, sb, c->stream, &sj));
   return MPSK_OK;
 }
@@ -788,7 +791,8 @@ static int transfer_right_c128(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d
 
 // x may be given in `nblk` row blocks (block q = rows [q Dl/nblk, (q+1) Dl/nblk) as a contiguous [Dl/nblk, d, Dr]
 // tensor): the blocks become K-segments of the stage-1 GEMM, nothing is re-interleaved (mpsk_dAC_blocked).
-static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
+// GR: Wr slabs [Dr, Dro], y: [Dlo, d, Dro]; the square matvec is Dro = Dr.
+static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR,
                     const void* x, int nblk, void* y) {
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
@@ -809,9 +813,9 @@ static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   HIPCHK(mix_apply(H->fwd, T1, ix, T2, ix, Dlo, Dr, c->stream));
   // stage 3: y = sum_v T2[v] * GR[v]   (K-segments over v)
   std::vector<int64_t> sa, sb;
-  for (int v = 0; v < Wr; ++v) if (H->col_used[v]) { sa.push_back((int64_t)v * slab); sb.push_back((int64_t)v * Dr * Dr); }
-  if (sa.empty()) { HIPCHK(zero_async(y, sizeof(double) * slab, c->stream)); return MPSK_OK; }
-  GemmArgs g3 = mk(T2, (const double*)GR, (double*)y, Dlo * d, Dr, Dr, (int64_t)Dlo * d, Dr, (int64_t)Dlo * d);
+  for (int v = 0; v < Wr; ++v) if (H->col_used[v]) { sa.push_back((int64_t)v * slab); sb.push_back((int64_t)v * Dr * Dro); }
+  if (sa.empty()) { HIPCHK(zero_async(y, sizeof(double) * Dlo * d * Dro, c->stream)); return MPSK_OK; }
+  GemmArgs g3 = mk(T2, (const double*)GR, (double*)y, Dlo * d, Dro, Dr, (int64_t)Dlo * d, Dr, (int64_t)Dlo * d);
   g3.tag = 1;
   HIPCHK(gemm_segments(g3, sa, sb, c->stream));
   return MPSK_OK;
@@ -880,7 +884,7 @@ static int dense_stage2(mpsk_ctx* c, const mpsk_mposlice* H, int64_t rows, const
   return MPSK_OK;
 }
 
-static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const double* GL, const double* GR,
+static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const double* GL, const double* GR,
                      const double* x, double* y) {
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
@@ -892,9 +896,9 @@ static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int D
   if (int rc = dense_stage2(c, H, (int64_t)slab, T1, T2)) return rc;
   // stage 3: y[:, t, :] = sum_v T2[:, :, t, v] GR[v]    (batch over t; K-segments over v)
   std::vector<int64_t> sa, sb;
-  for (int v = 0; v < Wr; ++v) if (H->col_used[v]) { sa.push_back((int64_t)v * d * slab); sb.push_back((int64_t)v * Dr * Dr); }
-  if (sa.empty()) { HIPCHK(zero_async(y, sizeof(double) * slab * d, c->stream)); return MPSK_OK; }
-  GemmArgs g3 = mk(T2, GR, y, Dlo, Dr, Dr, Dlo, Dr, (int64_t)Dlo * d);
+  for (int v = 0; v < Wr; ++v) if (H->col_used[v]) { sa.push_back((int64_t)v * d * slab); sb.push_back((int64_t)v * Dr * Dro); }
+  if (sa.empty()) { HIPCHK(zero_async(y, sizeof(double) * Dlo * d * Dro, c->stream)); return MPSK_OK; }
+  GemmArgs g3 = mk(T2, GR, y, Dlo, Dro, Dr, Dlo, Dr, (int64_t)Dlo * d);
   g3.batch = d; g3.bsA = (int64_t)slab; g3.bsB = 0; g3.bsC = Dlo;
   g3.tag = 1;
   HIPCHK(gemm_segments(g3, sa, sb, c->stream));
@@ -925,9 +929,9 @@ int mpsk_dAC(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const
   REQUIRE(c && H && GL && GR && x && y, "NULL argument");
   REQUIRE(Dlo > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
   if (H->dtype == MPSK_C128)
-    return dAC_c128(c, H, Dlo, Dl, Dr, (const double*)GL, (const double*)GR, nullptr, (const double*)x, (double*)y);
-  if (dense_route(H)) return dAC_dense(c, H, Dlo, Dl, Dr, (const double*)GL, (const double*)GR, (const double*)x, (double*)y);
-  return dAC_impl(c, H, Dlo, Dl, Dr, GL, GR, x, 1, y);
+    return dAC_c128(c, H, Dlo, Dl, Dr, Dr, (const double*)GL, (const double*)GR, nullptr, (const double*)x, (double*)y);
+  if (dense_route(H)) return dAC_dense(c, H, Dlo, Dl, Dr, Dr, (const double*)GL, (const double*)GR, (const double*)x, (double*)y);
+  return dAC_impl(c, H, Dlo, Dl, Dr, Dr, GL, GR, x, 1, y);
 }
 
 int mpsk_dAC_blocked(mpsk_ctx* c, const mpsk_mposlice* H, int nblk, int Dlo, int Dl, int Dr, const void* GL,
@@ -937,9 +941,21 @@ int mpsk_dAC_blocked(mpsk_ctx* c, const mpsk_mposlice* H, int nblk, int Dlo, int
   REQUIRE(nblk >= 1 && nblk <= MAXSEG && Dl % nblk == 0, "nblk must divide Dl (and be <= 32)");
   if (H->dtype == MPSK_C128) {
     if (nblk != 1) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_dAC_blocked: the blocked layout is implemented for MPSK_F64 only");
-    return dAC_c128(c, H, Dlo, Dl, Dr, (const double*)GL, (const double*)GR, nullptr, (const double*)xblk, (double*)y);
+    return dAC_c128(c, H, Dlo, Dl, Dr, Dr, (const double*)GL, (const double*)GR, nullptr, (const double*)xblk, (double*)y);
   }
-  return dAC_impl(c, H, Dlo, Dl, Dr, GL, GR, xblk, nblk, y);
+  return dAC_impl(c, H, Dlo, Dl, Dr, Dr, GL, GR, xblk, nblk, y);
+}
+
+// ac_proj (derivatives.jl:210-217): the matvec with a rectangular right environment, GR slabs [Dr, Dro] (ket leg of the
+// state above, bra leg of the state below).  Same three routes as mpsk_dAC with N = Dro in stage 3.
+int mpsk_dAC_proj(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR,
+                  const void* x, void* y) {
+  REQUIRE(c && H && GL && GR && x && y, "NULL argument");
+  REQUIRE(Dlo > 0 && Dl > 0 && Dr > 0 && Dro > 0, "dimensions must be positive");
+  if (H->dtype == MPSK_C128)
+    return dAC_c128(c, H, Dlo, Dl, Dr, Dro, (const double*)GL, (const double*)GR, nullptr, (const double*)x, (double*)y);
+  if (dense_route(H)) return dAC_dense(c, H, Dlo, Dl, Dr, Dro, (const double*)GL, (const double*)GR, (const double*)x, (double*)y);
+  return dAC_impl(c, H, Dlo, Dl, Dr, Dro, GL, GR, x, 1, y);
 }
 
 // ---- prepared operator ---------------------------------------------------------------------------
@@ -1162,10 +1178,10 @@ int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
   REQUIRE(nblk >= 1 && nblk <= MAXSEG && Dl % nblk == 0, "nblk must divide Dl (and be <= 32)");
   if (h->mode == 2) {
     if (nblk != 1) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_hac_apply: the blocked layout is implemented for MPSK_F64 only");
-    return dAC_c128(c, H, Dlo, Dl, Dr, h->GL, h->GR, h->GRc, (const double*)x, (double*)y);
+    return dAC_c128(c, H, Dlo, Dl, Dr, Dr, h->GL, h->GR, h->GRc, (const double*)x, (double*)y);
   }
-  if (h->mode == 0 || (h->mode == 4 && nblk != 1)) return dAC_impl(c, H, Dlo, Dl, Dr, h->GL, h->GR, x, nblk, y);
-  if (h->mode == 4) return dAC_dense(c, H, Dlo, Dl, Dr, h->GL, h->GR, (const double*)x, (double*)y);
+  if (h->mode == 0 || (h->mode == 4 && nblk != 1)) return dAC_impl(c, H, Dlo, Dl, Dr, Dr, h->GL, h->GR, x, nblk, y);
+  if (h->mode == 4) return dAC_dense(c, H, Dlo, Dl, Dr, Dr, h->GL, h->GR, (const double*)x, (double*)y);
   HIPCHK(hipSetDevice(c->device));
   if (h->mode == 3) {
     // y[:, t, :] = sum_k x[:, s_k, :] GRc0[(s_k, t)] + sum_k GLc[(s_k, t)] x[:, s_k, :]     (batch over t)
@@ -1309,7 +1325,7 @@ int mpsk_dAC2(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int
   REQUIRE(Dlo > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
   REQUIRE(H1->dtype == H2->dtype, "the two slices have different scalar types");
   if (H1->dtype == MPSK_C128)
-    return dAC2_c128(c, H1, H2, Dlo, Dl, Dr, (const double*)GL, (const double*)GR, (const double*)x2, (double*)y2);
+    return dAC2_c128(c, H1, H2, Dlo, Dl, Dr, Dr, (const double*)GL, (const double*)GR, (const double*)x2, (double*)y2);
   HIPCHK(hipSetDevice(c->device));
   const int d1 = H1->d, d2 = H2->d, Wl = H1->Wl, Wr = H2->Wr;
   const size_t plane = (size_t)Dlo * d1 * Dr;      // one s2-plane
@@ -2855,6 +2871,18 @@ int mpsk_vnrm2(mpsk_ctx* c, int64_t n, const void* x, double* host_out) {
   return MPSK_OK;
 }
 
+// host_out = {|x - y|^2, |x|^2} in one pass over both vectors: the convergence measure norm(AC' - AC) / norm(AC') of a
+// variational-approximation site visit (fvomps.jl:66).  MPSK_C128 (ctx dtype): n counts complex elements.
+int mpsk_vdiff_nrm2(mpsk_ctx* c, int64_t n, const void* x, const void* y, double* host_out) {
+  REQUIRE(c && x && y && host_out, "NULL argument");
+  REQUIRE(n > 0, "bad n");
+  REQUIRE(((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0), "operands must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(vec_diff_nrm2((const double*)x, (const double*)y, c->dtype == MPSK_C128 ? 2 * n : n, c->d_scal, c->d_partial,
+                       c->stream));
+  return fetch_scalars(c, 2, host_out);
+}
+
 int mpsk_vgs_step(mpsk_ctx* c, int64_t n, int k, const void* const* xs, void* y, double* host_out) {
   REQUIRE(c && xs && y && host_out, "NULL argument");
   REQUIRE(k > 0 && k <= MAXK && n > 0, "bad k or n");
@@ -3058,40 +3086,41 @@ static int dense_tab_right(const mpsk_mposlice* H, int64_t P, int64_t Q, const i
   return MPSK_OK;
 }
 
-// left half: T1 (scratch, Wl d Dl Dm) and L2 (result, Wm d Dl Dm)
-static int half_left(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dm, const double* GL, const double* AC, double* T1,
-                     double* L2, HalfView* v) {
+// left half: T1 (scratch, Wl d Dlo Dm) and L2 (result, Wm d Dlo Dm).  GL: Wl slabs [Dlo, Dl] (Dlo = Dl: mpsk_dAC2_product;
+// mpsk_dAC2_proj: the bond dimension of the state below)
+static int half_left(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dm, const double* GL, const double* AC,
+                     double* T1, double* L2, HalfView* v) {
   const int d = H->d;
   if (dense_route(H)) {
-    const int64_t col = (int64_t)Dl * Dm;
-    if (int rc = dense_stage1(c, H, Dl, Dl, Dm, GL, AC, T1)) return rc;          // T1[(a,m), (s,w)]
+    const int64_t col = (int64_t)Dlo * Dm;
+    if (int rc = dense_stage1(c, H, Dlo, Dl, Dm, GL, AC, T1)) return rc;         // T1[(a,m), (s,w)]
     if (int rc = dense_stage2(c, H, col, T1, L2)) return rc;                     // L2[(a,m), (t,u)]
-    *v = HalfView{L2, col, col * d, Dl};
+    *v = HalfView{L2, col, col * d, Dlo};
     return MPSK_OK;
   }
-  const int64_t slab = (int64_t)Dl * d * Dm;
-  GemmArgs g1 = mk(GL, AC, T1, Dl, d * Dm, Dl, Dl, Dl, Dl);                       // T1[w] = GL[w] AC
-  g1.batch = H->Wl; g1.bsA = (int64_t)Dl * Dl; g1.bsB = 0; g1.bsC = slab;
+  const int64_t slab = (int64_t)Dlo * d * Dm;
+  GemmArgs g1 = mk(GL, AC, T1, Dlo, d * Dm, Dl, Dlo, Dl, Dlo);                    // T1[w] = GL[w] AC
+  g1.batch = H->Wl; g1.bsA = (int64_t)Dlo * Dl; g1.bsB = 0; g1.bsC = slab;
   g1.tag = 1;
   HIPCHK(gemm_f64(g1, c->stream));
-  SlabIndex ix{d, 1 << 30, (int64_t)Dl, slab, 0, (int64_t)Dl * d};
-  HIPCHK(mix_apply(H->fwd, T1, ix, L2, ix, Dl, Dm, c->stream));                  // L2[u][a,t,m]
-  *v = HalfView{L2, Dl, slab, (int64_t)Dl * d};
+  SlabIndex ix{d, 1 << 30, (int64_t)Dlo, slab, 0, (int64_t)Dlo * d};
+  HIPCHK(mix_apply(H->fwd, T1, ix, L2, ix, Dlo, Dm, c->stream));                 // L2[u][a,t,m]
+  *v = HalfView{L2, Dlo, slab, (int64_t)Dlo * d};
   return MPSK_OK;
 }
 
-// right half: T1 (scratch, Wr d Dm Dr) and R2 (result, Wm d Dm Dr)
-static int half_right(mpsk_ctx* c, const mpsk_mposlice* H, int Dm, int Dr, const double* AR, const double* GR, double* T1,
-                      double* R2, HalfView* v) {
+// right half: T1 (scratch, Wr d Dm Dro) and R2 (result, Wm d Dm Dro).  GR: Wr slabs [Dr, Dro] (Dro = Dr: mpsk_dAC2_product)
+static int half_right(mpsk_ctx* c, const mpsk_mposlice* H, int Dm, int Dr, int Dro, const double* AR, const double* GR,
+                      double* T1, double* R2, HalfView* v) {
   const int d = H->d;
   if (dense_route(H)) {
-    const int64_t col = (int64_t)Dm * Dr;
+    const int64_t col = (int64_t)Dm * Dro;
     const int64_t* tab = nullptr;
-    if (int rc = dense_tab_right(H, Dm, (int64_t)Dr * Dr, &tab)) return rc;
-    GemmArgs g1 = mk(AR, GR, T1, Dm, Dr, Dr, (int64_t)Dm * d, Dr, Dm);           // T1[(m,b), (s,v)] = AR[:,s,:] GR[v]
+    if (int rc = dense_tab_right(H, Dm, (int64_t)Dr * Dro, &tab)) return rc;
+    GemmArgs g1 = mk(AR, GR, T1, Dm, Dro, Dr, (int64_t)Dm * d, Dr, Dm);          // T1[(m,b), (s,v)] = AR[:,s,:] GR[v]
     g1.batch = H->Wr * d; g1.bsC = col;
     g1.tabA = tab; g1.tabB = tab + (size_t)H->Wr * d;
-    g1.tabs_even = Dm % 2 == 0 && ((int64_t)Dr * Dr) % 2 == 0;
+    g1.tabs_even = Dm % 2 == 0 && ((int64_t)Dr * Dro) % 2 == 0;
     g1.tag = 1;
     HIPCHK(gemm_f64(g1, c->stream));
     GemmArgs g2 = mk(T1, H->d_OdR, R2, (int)col, d * H->Wl, d * H->Wr, col, (int64_t)d * H->Wr, col);   // R2[(m,b), (t,u)]
@@ -3100,14 +3129,49 @@ static int half_right(mpsk_ctx* c, const mpsk_mposlice* H, int Dm, int Dr, const
     *v = HalfView{R2, col, col * d, Dm};
     return MPSK_OK;
   }
-  const int64_t slab = (int64_t)Dm * d * Dr;
-  GemmArgs g1 = mk(AR, GR, T1, Dm * d, Dr, Dr, (int64_t)Dm * d, Dr, (int64_t)Dm * d);   // T1[v][(m,s), b] = AR GR[v]
-  g1.batch = H->Wr; g1.bsA = 0; g1.bsB = (int64_t)Dr * Dr; g1.bsC = slab;
+  const int64_t slab = (int64_t)Dm * d * Dro;
+  GemmArgs g1 = mk(AR, GR, T1, Dm * d, Dro, Dr, (int64_t)Dm * d, Dr, (int64_t)Dm * d);  // T1[v][(m,s), b] = AR GR[v]
+  g1.batch = H->Wr; g1.bsA = 0; g1.bsB = (int64_t)Dr * Dro; g1.bsC = slab;
   g1.tag = 1;
   HIPCHK(gemm_f64(g1, c->stream));
   SlabIndex ix{d, 1 << 30, (int64_t)Dm, slab, 0, (int64_t)Dm * d};
-  HIPCHK(mix_apply(H->rgt, T1, ix, R2, ix, Dm, Dr, c->stream));                  // R2[u][m,t,b]
+  HIPCHK(mix_apply(H->rgt, T1, ix, R2, ix, Dm, Dro, c->stream));                 // R2[u][m,t,b]
   *v = HalfView{R2, Dm, slab, (int64_t)Dm * d};
+  return MPSK_OK;
+}
+
+// The factorised two-site contraction for GL slabs [Dlo, Dl] and GR slabs [Dr, Dro]: Y[Dlo, d1, Dro, d2].  mpsk_dAC2_product
+// is the square case (Dlo = Dl, Dro = Dr), mpsk_dAC2_proj the projection on another state's tangent space.
+static int dAC2_factorised(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dlo, int Dl, int Dm, int Dr,
+                           int Dro, const void* GL, const void* GR, const void* AC, const void* AR, void* Y) {
+  HIPCHK(hipSetDevice(c->device));
+  const int d1 = H1->d, d2 = H2->d, Wl = H1->Wl, Wm = H1->Wr, Wr = H2->Wr;
+  const auto ev = [](size_t v) { return (v + 1) & ~(size_t)1; };
+  const size_t l1 = ev((size_t)Wl * d1 * Dlo * Dm), l2 = ev((size_t)Wm * d1 * Dlo * Dm);
+  const size_t r1 = ev((size_t)Wr * d2 * Dm * Dro), r2 = ev((size_t)Wm * d2 * Dm * Dro);
+  if (int rc = ensure_ws(c, sizeof(double) * (l1 + l2 + r1 + r2))) return rc;
+  double* TL = (double*)c->ws;
+  double* L2 = TL + l1;
+  double* TR = L2 + l2;
+  double* R2 = TR + r1;
+  HalfView hl, hr;
+  if (int rc = half_left(c, H1, Dlo, Dl, Dm, (const double*)GL, (const double*)AC, TL, L2, &hl)) return rc;
+  if (int rc = half_right(c, H2, Dm, Dr, Dro, (const double*)AR, (const double*)GR, TR, R2, &hr)) return rc;
+  // Y[a,t1,b,t2] = sum_u sum_m Lh(t1,u)[a,m] Rh(t2,u)[m,b]
+  const int64_t plane = (int64_t)Dlo * d1 * Dro;
+  std::vector<int64_t> sa, sb;
+  for (int u = 0; u < Wm; ++u)
+    if (H1->col_used[u] && H2->row_used[u]) { sa.push_back(u * hl.su); sb.push_back(u * hr.su); }
+  if (sa.empty()) { HIPCHK(zero_async(Y, sizeof(double) * plane * d2, c->stream)); return MPSK_OK; }
+  const int64_t* tab = nullptr;
+  bool even = false;
+  if (int rc = product_tab(c, d1, d2, hl.st, hr.st, Dlo, plane, &tab, &even)) return rc;
+  GemmArgs g = mk(hl.p, hr.p, (double*)Y, Dlo, Dro, Dm, hl.ld, hr.ld, (int64_t)Dlo * d1);
+  g.batch = d1 * d2;
+  g.tabA = tab; g.tabB = tab + (size_t)d1 * d2; g.tabC = tab + (size_t)2 * d1 * d2;
+  g.tabs_even = even ? 1 : 0;
+  g.tag = 1;
+  HIPCHK(gemm_segments(g, sa, sb, c->stream));
   return MPSK_OK;
 }
 
@@ -3117,35 +3181,7 @@ int mpsk_dAC2_product(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice*
   REQUIRE(H1->Wr == H2->Wl, "MPO bond dimensions of the two slices do not match");
   REQUIRE(Dl > 0 && Dm > 0 && Dr > 0, "dimensions must be positive");
   REQUIRE(H1->dtype == MPSK_F64 && H2->dtype == MPSK_F64, "MPSK_F64 slices only");
-  HIPCHK(hipSetDevice(c->device));
-  const int d1 = H1->d, d2 = H2->d, Wl = H1->Wl, Wm = H1->Wr, Wr = H2->Wr;
-  const auto ev = [](size_t v) { return (v + 1) & ~(size_t)1; };
-  const size_t l1 = ev((size_t)Wl * d1 * Dl * Dm), l2 = ev((size_t)Wm * d1 * Dl * Dm);
-  const size_t r1 = ev((size_t)Wr * d2 * Dm * Dr), r2 = ev((size_t)Wm * d2 * Dm * Dr);
-  if (int rc = ensure_ws(c, sizeof(double) * (l1 + l2 + r1 + r2))) return rc;
-  double* TL = (double*)c->ws;
-  double* L2 = TL + l1;
-  double* TR = L2 + l2;
-  double* R2 = TR + r1;
-  HalfView hl, hr;
-  if (int rc = half_left(c, H1, Dl, Dm, (const double*)GL, (const double*)AC, TL, L2, &hl)) return rc;
-  if (int rc = half_right(c, H2, Dm, Dr, (const double*)AR, (const double*)GR, TR, R2, &hr)) return rc;
-  // Y[a,t1,b,t2] = sum_u sum_m Lh(t1,u)[a,m] Rh(t2,u)[m,b]
-  const int64_t plane = (int64_t)Dl * d1 * Dr;
-  std::vector<int64_t> sa, sb;
-  for (int u = 0; u < Wm; ++u)
-    if (H1->col_used[u] && H2->row_used[u]) { sa.push_back(u * hl.su); sb.push_back(u * hr.su); }
-  if (sa.empty()) { HIPCHK(zero_async(Y, sizeof(double) * plane * d2, c->stream)); return MPSK_OK; }
-  const int64_t* tab = nullptr;
-  bool even = false;
-  if (int rc = product_tab(c, d1, d2, hl.st, hr.st, Dl, plane, &tab, &even)) return rc;
-  GemmArgs g = mk(hl.p, hr.p, (double*)Y, Dl, Dr, Dm, hl.ld, hr.ld, (int64_t)Dl * d1);
-  g.batch = d1 * d2;
-  g.tabA = tab; g.tabB = tab + (size_t)d1 * d2; g.tabC = tab + (size_t)2 * d1 * d2;
-  g.tabs_even = even ? 1 : 0;
-  g.tag = 1;
-  HIPCHK(gemm_segments(g, sa, sb, c->stream));
-  return MPSK_OK;
+  return dAC2_factorised(c, H1, H2, Dl, Dl, Dm, Dr, Dr, GL, GR, AC, AR, Y);
 }
 
 // mpsk_complement_tsvd: the k leading singular triplets of X = (1 - QL QL^T) Y (1 - QR^T QR) without null-space bases
@@ -3159,11 +3195,33 @@ static int ex_scratch(mpsk_ctx* c, size_t bytes, double** out) {
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->exws) HIPCHK(hipFree(c->exws));
     c->exws = nullptr; c->exws_bytes = 0;
-    if (hipMalloc(&c->exws, bytes) != hipSuccess) return fail(MPSK_ERR_NOMEM, "mpsk_complement_tsvd: workspace hipMalloc failed");
+    if (hipMalloc(&c->exws, bytes) != hipSuccess) return fail(MPSK_ERR_NOMEM, "bond expansion / two-site projection: scratch hipMalloc failed");
     c->exws_bytes = bytes;
   }
   *out = (double*)c->exws;
   return MPSK_OK;
+}
+
+// ac2_proj (derivatives.jl:218-226).  MPSK_F64: the factorised contraction above, the two-site tensor of the state above
+// is never formed.  MPSK_C128: theta = AC AR is built in a scratch buffer of its own (d2 complex GEMMs, one per physical
+// index of the right site) and the rectangular form of the complex two-site matvec runs on it.
+int mpsk_dAC2_proj(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dlo, int Dl, int Dm, int Dr, int Dro,
+                   const void* GL, const void* GR, const void* AC, const void* AR, void* Y) {
+  REQUIRE(c && H1 && H2 && GL && GR && AC && AR && Y, "NULL argument");
+  REQUIRE(H1->Wr == H2->Wl, "MPO bond dimensions of the two slices do not match");
+  REQUIRE(Dlo > 0 && Dl > 0 && Dm > 0 && Dr > 0 && Dro > 0, "dimensions must be positive");
+  REQUIRE(H1->dtype == H2->dtype, "the two slices have different scalar types");
+  if (H1->dtype == MPSK_F64) return dAC2_factorised(c, H1, H2, Dlo, Dl, Dm, Dr, Dro, GL, GR, AC, AR, Y);
+  HIPCHK(hipSetDevice(c->device));
+  const int d1 = H1->d, d2 = H2->d;
+  const size_t plane = (size_t)2 * Dl * d1 * Dr;                 // doubles of one s2-plane of theta[Dl, d1, Dr, d2]
+  double* theta = nullptr;
+  if (int rc = ex_scratch(c, sizeof(double) * plane * d2, &theta)) return rc;
+  for (int s2 = 0; s2 < d2; ++s2)                                // theta[:, :, :, s2] = AC . AR[:, s2, :]
+    if (int rc = gemm_c128(c, 0, 0, Dl * d1, Dr, Dm, 1.0, AC, (int64_t)Dl * d1, (const double*)AR + (size_t)2 * s2 * Dm,
+                           (int64_t)Dm * d2, 0.0, theta + plane * s2, (int64_t)Dl * d1))
+      return rc;
+  return dAC2_c128(c, H1, H2, Dlo, Dl, Dr, Dro, (const double*)GL, (const double*)GR, theta, (double*)Y);
 }
 
 int mpsk_complement_tsvd(mpsk_ctx* c, int m, int n, const void* Y, int ldy, const void* QL, int ldql, int pl, const void* QR,

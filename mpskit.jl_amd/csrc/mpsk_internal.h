@@ -126,6 +126,8 @@ hipError_t identity_slab(double* G, int n, hipStream_t s);   // G[n, n] (contigu
 constexpr int MPSK_DOT_SCRATCH = 32 * 1024;     // up to 32 dots x DOT_BLOCKS partial sums (the long fused Gram-Schmidt passes)
 hipError_t vec_multidot(const double* const* xs, int k, const double* y, int64_t n, double* d_out,
                         double* d_partial, hipStream_t s);
+// d_out = {|x - y|^2, |x|^2}: one pass over both vectors + the final reduction of vec_multidot
+hipError_t vec_diff_nrm2(const double* x, const double* y, int64_t n, double* d_out, double* d_partial, hipStream_t s);
 hipError_t vec_axpby(double a, const double* x, double b, double* y, int64_t n, hipStream_t s);
 hipError_t vec_times_i(const double* x, double* y, int64_t n, hipStream_t s);
 hipError_t vec_scal(double a, double* x, int64_t n, hipStream_t s);

@@ -274,6 +274,39 @@ hipError_t vec_multidot(const double* const* xs, int k, const double* y, int64_t
   return hipGetLastError();
 }
 
+// partial[b] = block b's share of |x - y|^2, partial[DOT_BLOCKS + b] = its share of |x|^2: both sums of the convergence
+// measure of a variational-approximation site visit from ONE read of x and y (same grid and element order as multidot_kernel)
+__global__ __launch_bounds__(256) void diff_nrm2_kernel(const double* __restrict__ x, const double* __restrict__ y, int64_t n,
+                                                        double* __restrict__ partial) {
+  __shared__ double sh[4 * 2];
+  double acc[2] = {0.0, 0.0};
+  const int64_t n2 = n >> 1;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n2; e += (int64_t)gridDim.x * blockDim.x) {
+    const d2 xv = *reinterpret_cast<const d2*>(x + 2 * e);
+    const d2 yv = *reinterpret_cast<const d2*>(y + 2 * e);
+    const double d0 = xv.x - yv.x, d1 = xv.y - yv.y;
+    acc[0] += d0 * d0 + d1 * d1;
+    acc[1] += xv.x * xv.x + xv.y * xv.y;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const double dl = x[n - 1] - y[n - 1];
+    acc[0] += dl * dl;
+    acc[1] += x[n - 1] * x[n - 1];
+  }
+  block_sum<2>(acc, sh);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = acc[0];
+    partial[DOT_BLOCKS + blockIdx.x] = acc[1];
+  }
+}
+
+hipError_t vec_diff_nrm2(const double* x, const double* y, int64_t n, double* d_out, double* d_partial, hipStream_t s) {
+  const int nb = dot_grid(n);
+  hipLaunchKernelGGL(diff_nrm2_kernel, dim3(nb), dim3(256), 0, s, x, y, n, d_partial);
+  hipLaunchKernelGGL(dot_final_kernel, dim3(2), dim3(256), 0, s, d_partial, nb, d_out);
+  return hipGetLastError();
+}
+
 // ---- fused passes of the twice-iterated classical Gram-Schmidt step -------------------------------------------------
 // y <- y + sign * sum_j coefs[j] xs[j]  AND, in the same pass over memory, either the NVEC dots <xs[j], y_new>
 // (NORM == false: the second-round coefficients) or <y_new, y_new> (NORM == true: the squared norm of the remainder).

@@ -87,6 +87,87 @@ class FinEnv:
         self.rdeps[ind] = None
 
 
+def _start_env_pair(be: Backend, chis, D1, D2, active_level):
+    """_start_env for two states: W slabs [D1, D2], the (rectangular) identity on the active level (FinEnv.jl:48-66 with
+    l_LL / r_RR the trivial edge of a finite chain; D1 = D2 = 1 for the chains FiniteMPS.random builds)."""
+    W = sum(chis)
+    host = np.zeros((W, D1, D2))
+    off = 0
+    for i, chi in enumerate(chis):
+        if i == active_level:
+            host[off:off + chi] = np.eye(D1, D2)
+        off += chi
+    t = be.upload(np.transpose(host, (1, 2, 0)))
+    return DTensor(t.buf, (W, D1, D2))
+
+
+class FinEnvPair(FinEnv):
+    """environments(below, (O, above)) / environments(below, above)  (FinEnv.jl:21-99): the environments of <below| O |above>.
+    GL[w] is [D_below, D_above], GR[v] is [D_above, D_below]; an update is one mixed transfer with the ket tensor of `above`
+    and the bra tensor of `below`.  Only `below` is tracked (FinEnv.jl:115,132): `above` is assumed not to change.
+    O: MPOHamiltonian (right boundary on level odim - 1), SparseMPO (level 0, FinEnv.jl:61), a finite dense MPO (DenseMPO
+    or a list of L tensors [Wl, d, d, Wr] with edge dimensions 1, FinEnv.jl:72-81) or None (plain overlap, :91-99)."""
+
+    def __init__(self, below, O, above):
+        from .operators import SparseMPO
+        from .statmech import DenseMPO
+        be = self.be = below.be
+        L = len(below)
+        if len(above) != L:
+            raise ValueError(f"the two states have different lengths ({L} != {len(above)})")
+        self.H, self.above = O, above
+        edge = lambda psi: (psi.ARs[L - 1] if psi.ARs[L - 1] is not None else psi.AL(L - 1)).shape[2]
+        Db0, Da0, DbL, DaL = below.AL(0).shape[0], above.AL(0).shape[0], edge(below), edge(above)
+        if O is None:
+            self.opp, chil, chir, ract = [None] * L, [1], [1], 0
+        elif isinstance(O, (DenseMPO, list, tuple)):
+            ts = [np.asarray(O[i], dtype=float) for i in range(L)]
+            if len(O) != L or ts[0].shape[0] != 1 or ts[-1].shape[3] != 1:
+                raise ValueError("a finite dense MPO needs one tensor per site and edge dimensions 1")
+            mk = be.mposlice_dense if hasattr(be, "mposlice_dense") else \
+                (lambda o: be.mposlice(1, o.shape[1], [o.shape[0]], [o.shape[3]], {(0, 0): o}))
+            self.opp, chil, chir, ract = [mk(o) for o in ts], [1], [1], 0
+        else:
+            self.opp = [O[i] for i in range(L)]
+            chil, chir = self.opp[0].chil, self.opp[L - 1].chir
+            ract = 0 if isinstance(O, SparseMPO) else O.odim - 1
+        self.leftenvs = [_start_env_pair(be, chil, Db0, Da0, 0)] + [None] * L
+        self.rightenvs = [None] * L + [_start_env_pair(be, chir, DaL, DbL, ract)]
+        self.ldeps = [None] * L
+        self.rdeps = [None] * L
+        self.n_transfers = 0
+        self.canonical = False
+
+    def rightenv(self, ind, psi):  # FinEnv.jl:114-129
+        L = len(psi)
+        a = None
+        for i in range(L - 1, ind, -1):
+            if psi.AR(i) is not self.rdeps[i]:
+                a = i
+                break
+        if a is not None:
+            for j in range(a, ind, -1):
+                ar = psi.AR(j)
+                self.rightenvs[j] = self.be.transfer_right(self.opp[j], self.rightenvs[j + 1], self.above.AR(j), ar)
+                self.rdeps[j] = ar
+                self.n_transfers += 1
+        return self.rightenvs[ind + 1]
+
+    def leftenv(self, ind, psi):  # FinEnv.jl:131-145
+        a = None
+        for i in range(0, ind):
+            if psi.AL(i) is not self.ldeps[i]:
+                a = i
+                break
+        if a is not None:
+            for j in range(a, ind):
+                al = psi.AL(j)
+                self.leftenvs[j + 1] = self.be.transfer_left(self.opp[j], self.leftenvs[j], self.above.AL(j), al)
+                self.ldeps[j] = al
+                self.n_transfers += 1
+        return self.leftenvs[ind]
+
+
 class MultipleEnvironments:
     """MultipleEnvironments (src/environments/multipleenv.jl:1-62): one environment object per LazySum term."""
 
@@ -108,6 +189,9 @@ def environments(psi, H, **kw):
     from .states import FiniteMPS
     from .operators import LazySum
     from .statmech import DenseMPO, PerMPOInfEnv
+    if isinstance(psi, FiniteMPS) and isinstance(H, (tuple, FiniteMPS)):       # FinEnv.jl:21-23, :91-99
+        O, above = H if isinstance(H, tuple) else (None, H)
+        return FinEnvPair(psi, O, above)
     if isinstance(H, DenseMPO):
         return PerMPOInfEnv(psi, H, **kw)
     if isinstance(H, LazySum):

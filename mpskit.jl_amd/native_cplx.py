@@ -11,6 +11,7 @@ right of it right-orthonormal), which is all the one-site algorithms need --
     find_groundstate (DMRG2, dmrg.jl:80-137) ->  dmrg2_sweep   (mpsk_dAC2 complex, mpsk_tsplit under MPSK_C128)
     timestep (TDVP, tdvp.jl:61-94)           ->  tdvp_step
     timestep (TDVP2, tdvp.jl:113-146)        ->  tdvp2_step
+    approximate (fvomps.jl:11-87)            ->  approximate   (mpsk_dAC_proj / mpsk_dAC2_proj complex, NativeFinEnvPair)
 The lazy-gauge FiniteMPS of states.py (all drivers, two-site algorithms, infinite systems, excitations) stays on the embedded
 representation; the Krylov solvers are shared (real inner products on the 2n doubles of an interleaved vector are all a
 Hermitian Lanczos / Arnoldi iteration needs, and multiplication by i is mpsk_vtimes_i)."""
@@ -395,6 +396,142 @@ def tdvp2_step(psi: NativeFiniteMPS, H, envs: NativeFinEnv, t, dt, alg, trunc_di
         if i != 1:
             psi.A[i - 1] = _integrate_embedded(be, _HAC(be, envs, i - 1), psi.A[i - 1], bwd, alg, ws)
     return psi, envs
+
+
+# ---- approximate on interleaved storage (approximate.jl:1-27, fvomps.jl:1-87) -----------------------------------------------
+
+def _boundary_pair(be, chis, D1, D2, active):
+    """_boundary for two states: slabs [D1, D2], the (rectangular) identity on the active level."""
+    blocks = []
+    for i, chi in enumerate(chis):
+        b = np.zeros((D1, chi, D2), dtype=np.complex128)
+        if i == active:
+            b[:, :, :] = np.eye(D1, D2)[:, None, :]
+        blocks.append(b)
+    return be.upload_env_c(blocks)
+
+
+class NativeFinEnvPair:
+    """Pair form of NativeFinEnv (FinEnv.jl:21-70 with `above`): environments of <below| O |above> as interleaved complex
+    slabs, GL[j] (W, 2 D_below, D_above) left of site j and GR[j] (W, 2 D_above, D_below) right of site j - 1.  It keeps its
+    own copy of `above` and moves that copy's centre together with the centre of `below`, so that at centre c the copy
+    holds AL (sites < c), AC (site c) and AR (sites > c) of the state above.  O: a SparseMPO (real or complex; right
+    boundary on level 0, FinEnv.jl:61), a ComplexMPOHamiltonian or a real MPOHamiltonian (level odim - 1); real slices get
+    complex twins."""
+
+    def __init__(self, below: NativeFiniteMPS, O, above: NativeFiniteMPS):
+        from .operators import SparseMPO
+        be = self.be = below.be
+        L = self.L = len(below)
+        if len(above) != L:
+            raise ValueError(f"the two states have different lengths ({L} != {len(above)})")
+        native = isinstance(O, ComplexMPOHamiltonian) or (isinstance(O, SparseMPO) and O.cplx)
+        self.opp = [O[i] if native else HalfEmbeddedOp._cslice(be, O[i]) for i in range(L)]
+        ract = 0 if isinstance(O, SparseMPO) else O.odim - 1
+        self.above = above.copy()
+        self.above.move_center(below.center)
+        self.GL = [_boundary_pair(be, self.opp[0].chil, below.dims(0)[0], above.dims(0)[0], 0)] + [None] * L
+        self.GR = [None] * L + [_boundary_pair(be, self.opp[L - 1].chir, above.dims(L - 1)[2], below.dims(L - 1)[2], ract)]
+        self.n_transfers = 0
+        c = below.center
+        for j in range(L - 1, c, -1):
+            self.extend_right(below, j)
+        for j in range(0, c):
+            self.extend_left(below, j)
+
+    def extend_left(self, psi, j):
+        self.GL[j + 1] = self.be.transfer_left(self.opp[j], self.GL[j], self.above.A[j], psi.A[j])
+        self.n_transfers += 1
+
+    def extend_right(self, psi, j):
+        self.GR[j] = self.be.transfer_right(self.opp[j], self.GR[j + 1], self.above.A[j], psi.A[j])
+        self.n_transfers += 1
+
+    def move_center(self, psi, pos):
+        """move the centre of `psi` and of the copy of `above` to pos, one site at a time, with one mixed transfer each"""
+        while psi.center < pos:
+            j = psi.center
+            psi._shift_right(j)
+            self.above._shift_right(j)
+            self.extend_left(psi, j)
+        while psi.center > pos:
+            j = psi.center
+            psi._shift_left(j)
+            self.above._shift_left(j)
+            self.extend_right(psi, j)
+
+
+def _rel_diff(be, x: DTensor, y: DTensor):
+    """norm(x - y) / norm(x) of two interleaved tensors (mpsk_vdiff_nrm2 on their doubles)"""
+    d2, n2 = be.vdiff_nrm2(x, y)
+    return float(np.sqrt(max(d2, 0.0) / n2))
+
+
+def approximate(psi0: NativeFiniteMPS, toapprox, alg, envs: NativeFinEnvPair = None):
+    """approximate(psi0, (O, above), DMRG(...) | DMRG2(...)) on interleaved complex states (fvomps.jl:11-87): every site visit
+    is one mpsk_dAC_proj / mpsk_dAC2_proj under MPSK_C128, one complex gauge step and one mixed transfer.  O may be the
+    complex SparseMPO of a real-time make_time_mpo.  Returns (psi, envs, eps) with eps of the last sweep as in the
+    reference; the eps of every sweep is kept in envs.history."""
+    from .algorithms import DMRG, DMRG2
+    O, above = toapprox
+    be, L = psi0.be, len(psi0)
+    psi = psi0.copy()
+    psi.move_center(0)
+    if envs is None:
+        envs = NativeFinEnvPair(psi, O, above)
+    else:
+        envs.move_center(psi, 0)
+    ab, opp = envs.above, envs.opp
+    if isinstance(alg, DMRG2):
+        trunc_err = alg.trunc_err if alg.trunc_dim <= 0 else 0.0
+
+        def visit(pos, forward):
+            envs.move_center(psi, pos)
+            y = be.dAC2_proj(opp[pos], opp[pos + 1], envs.GL[pos], envs.GR[pos + 2], ab.A[pos], ab.A[pos + 1])
+            Dl2, d1, Dr, d2 = y.shape
+            al, c, arm, _, _ = _split(be, y.reshape(Dl2 * d1, Dr * d2), alg.trunc_dim, trunc_err)
+            k = c.shape[1]
+            old = _two_site(be, psi.A[pos], psi.A[pos + 1])
+            rec = be.gemm_c(be.gemm_c(al, c), arm)                                       # al * c * ar
+            e = _rel_diff(be, old, DTensor(rec.buf, old.shape))
+            ar = be.empty(2 * k, d2, Dr)                                                 # ar[k, s2, b] = arm[k, (b, s2)]
+            for s2 in range(d2):
+                be.copy2d(2 * k, Dr, arm.ptr + 8 * s2 * 2 * k * Dr, 2 * k, ar.ptr + 8 * s2 * 2 * k, 2 * k * d2)
+            if forward:                                                                  # centre moves to pos + 1
+                psi.A[pos] = al.reshape(Dl2, d1, k)
+                psi.A[pos + 1] = be.gemm_c(c, ar.reshape(2 * k, d2 * Dr)).reshape(2 * k, d2, Dr)
+                psi.center = pos + 1
+                ab._shift_right(pos)
+                envs.extend_left(psi, pos)
+            else:                                                                        # centre stays at pos
+                psi.A[pos] = be.gemm_c(al, c).reshape(Dl2, d1, k)
+                psi.A[pos + 1] = ar
+                envs.extend_right(psi, pos + 1)
+            return e
+        order = [(p, True) for p in range(0, L - 1)] + [(p, False) for p in range(L - 3, -1, -1)]
+    elif isinstance(alg, DMRG):
+        def visit(pos, forward):
+            envs.move_center(psi, pos)
+            new = be.dAC_proj(opp[pos], envs.GL[pos], envs.GR[pos + 1], ab.A[pos])
+            e = _rel_diff(be, new, psi.A[pos])
+            psi.A[pos] = new
+            return e
+        order = [(p, True) for p in range(0, L - 1)] + [(p, False) for p in range(L - 1, 0, -1)]
+    else:
+        raise TypeError(f"approximate on interleaved states takes DMRG or DMRG2, not {type(alg).__name__}")
+    eps, history = 2 * alg.tol, []
+    for it in range(1, alg.maxiter + 1):
+        eps = 0.0
+        for pos, forward in order:
+            eps = max(eps, visit(pos, forward))
+        history.append((it, eps))
+        if alg.verbosity >= 3:
+            print(f"[ Info: approximate {type(alg).__name__} (interleaved complex) {it:3d}:\terr = {eps:.10e}", flush=True)
+        if eps < alg.tol:
+            break
+    envs.move_center(psi, 0)
+    envs.history = history
+    return psi, envs, eps
 
 
 # ---- the reference's entry points on interleaved states (same algorithm objects as algorithms.py) ---------------------------

@@ -144,6 +144,61 @@ class MPOHamiltonian:
         return self._energy_slices[key]
 
 
+class SparseMPO:
+    """SparseMPO (src/operators/sparsempo/sparsempo.jl): a periodic list of block-sparse slices WITHOUT the corner convention
+    of MPOHamiltonian -- what make_time_mpo returns.  On a finite chain both boundary vectors select level 0
+    (FinEnv.jl:57-63).  `data[site]` = {(i, j): scalar | d x d | [chi_i, d, d, chi_j]}; stored real unless a block has an
+    imaginary part (`cplx`; such an operator is applied by native_cplx.approximate).  Device slices are built on first
+    use, so the operator itself needs no GPU."""
+
+    def __init__(self, data, d, be: Backend | None = None, chis=None):
+        if isinstance(data, dict):
+            data = [data]
+        self.be, self.d, self.period = be, int(d), len(data)
+        self.odim = 1 + max(max(i, j) for blk in data for (i, j) in blk)
+        self.cplx = any(np.iscomplexobj(v) and np.abs(np.imag(v)).max() > 0 for blk in data for v in blk.values())
+        self.data = []
+        for blk in data:
+            out = {}
+            for (i, j), v in blk.items():
+                if not np.isscalar(v):
+                    v = np.asarray(v) if self.cplx else np.asarray(np.real(v), dtype=float)
+                    v = v[None, :, :, None] if v.ndim == 2 else v
+                    if np.abs(v).max() == 0:
+                        continue
+                elif v == 0:
+                    continue
+                elif not self.cplx:
+                    v = float(np.real(v))
+                out[(i, j)] = v
+            self.data.append(out)
+        if chis is None:
+            chis = [[1] * self.odim for _ in range(self.period + 1)]
+            for s, blk in enumerate(self.data):
+                for (i, j), v in blk.items():
+                    if not np.isscalar(v):
+                        chis[s][i], chis[s + 1][j] = v.shape[0], v.shape[3]
+            for i in range(self.odim):
+                chis[0][i] = chis[self.period][i] = max(chis[0][i], chis[self.period][i])
+        self.chis = chis
+        self._slices = None
+
+    @property
+    def slices(self):
+        if self._slices is None:
+            be = self.be = default_backend() if self.be is None else self.be
+            kw = {"cplx": True} if self.cplx else {}
+            self._slices = [be.mposlice(self.odim, self.d, self.chis[s], self.chis[s + 1], blk, **kw)
+                            for s, blk in enumerate(self.data)]
+        return self._slices
+
+    def __getitem__(self, i):
+        return self.slices[i % self.period]
+
+    def __len__(self):
+        return self.period
+
+
 def _mpo_product_data(srcA, srcB, d):
     """SparseMPO product b * a (src/operators/sparsempo/sparsempo.jl:232-264): a is applied first.  srcX[s] = (blocks, chil,
     chir).  New level (i, k) -> i + odim_a * k with dimension chi_a[i] * chi_b[k] (a's index fastest)."""
