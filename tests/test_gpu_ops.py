@@ -465,8 +465,11 @@ def test_tsvd_graded_and_rank_deficient_preconditioned(be):
                                           (1032, 520, 1040, 0, 0),     # ragged -> unaligned kernel, linear tile order
                                           (4096, 64, 64, 0, 0)])       # tall skinny (SVD update shape)
 def test_gemm_large_paths(be, M, N, K, tA, tB):
-    """Every launch-path of the GEMM core (split-K + fixup, XCD-rectangle tile map, unaligned loaders) against
-    numpy at sizes that trigger it; also with the remap / split switched off via the environment-free knobs."""
+    """Launch paths of the GEMM core (split-K + fixup when the cost model picks it, XCD-rectangle tile map, unaligned
+    loaders) against numpy at sizes that trigger them, on the automatic tile and with the 64x64 and 128x128 tiles forced
+    (a forced tile takes no split).  The remap and the split are NOT switched off here: MPSK_XCDGRID, MPSK_SPLITK and
+    MPSK_SPLITK_F are read once when the library loads, so tests/test_gpu_gemm_tiles.py covers them -- and the 128x64 /
+    64x128 tiles -- in child processes."""
     rng = np.random.default_rng(M + 3 * N + 7 * K)
     A = rng.standard_normal((K, M) if tA else (M, K))
     B = rng.standard_normal((N, K) if tB else (K, N))
