@@ -55,7 +55,8 @@
  *       embedded A and the interleaved B: 8 M N K flops, the complex optimum.
  *    The remaining entry points (mpsk_qrpos2, mpsk_qrlq_pair, Krylov vector helpers, mpsk_regularize) are fp64 only and
  *    ignore the ctx dtype: a complex host runs its vector arithmetic on the 2n doubles of an interleaved vector (real
- *    inner products suffice for the Hermitian Lanczos solvers).
+ *    inner products suffice for the Hermitian Lanczos solvers).  Solvers that need a Krylov space over the complex
+ *    numbers (GMRES with a complex shift) use the mpsk_v*_c forms at the end of this header.
  */
 #ifndef MPSK_H
 #define MPSK_H
@@ -193,10 +194,25 @@ int mpsk_hac_create(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int 
  * Slices with A blocks (longer-range MPOs), complex slices and every other case keep the mode mpsk_hac_create picks.
  * Environment MPSK_HAC_CHECK=1 (debug, synchronises): a mode-3 candidate whose max|GL[0] - I| or max|GR[W-1] - I|
  * exceeds 1e-10 fails with MPSK_ERR_INVALID.  mpsk_hac_info: mode 3, nslabs = folded slabs (2 d^2). */
-enum { MPSK_HAC_CANONICAL = 1 };
+enum { MPSK_HAC_CANONICAL = 1, MPSK_HAC_CANONICAL_C128 = 2 };
+/* MPSK_HAC_CANONICAL_C128: the same operator for a COMPLEX slice (MPSK_HAC_CANONICAL keeps its meaning and is still ignored
+ * for complex slices).  Conditions: the slice is in Jordan form with exactly real identity corners (the complex twin of a
+ * real Jordan-form slice, or one with complex B / C / D blocks), Dlo == Dl, and GL[0], GR[W-1] are identities -- checked on
+ * the device at create time (one synchronisation; tolerance 1e-10).  The folds GRc0 / GLc are then built once, in complex
+ * arithmetic, and an application is two launches on the complex GEMM family, 16 d^2 D^3 real flops (Heisenberg: 64 D^3
+ * against the 160 D^3 of mode 2); mpsk_hac_info reports mode 3.  If a condition fails the operator is what
+ * mpsk_hac_create prepares (mode 2), except under MPSK_HAC_CHECK=1, where non-canonical environments fail with
+ * MPSK_ERR_INVALID as for the real mode.  The environments of the correction vector of a propagator sweep are its case
+ * (src/algorithms/propagator/corvector.jl:52,66). */
 int mpsk_hac_create_ex(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
                        int flags, mpsk_hac** out);
 int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y);
+/* y = a0 x + a1 (H_AC x): the shifted operator KrylovKit's linsolve(H_AC, b, x0, alg, a0, a1) applies, as the dynamical-DMRG
+ * site solves call it (src/algorithms/propagator/corvector.jl:68 with a0 = -z, :123 with a0 = |z|^2).  a0, a1: (re, im)
+ * pairs; the imaginary parts are ignored for MPSK_F64 operators.  Every mode of mpsk_hac_apply, through mpsk_hac_apply
+ * itself (same launches, same bits) followed by ONE fused vector pass over x and y; a0 = 0, a1 = 1 is mpsk_hac_apply bit
+ * for bit.  x and y must not alias; a0 != 0 needs Dlo == Dl and nblk == 1. */
+int mpsk_hac_apply_axpby(mpsk_hac* h, const double* a1, const void* x, int nblk, const double* a0, void* y);
 /* Fixed-budget smallest-real eigensolve with the prepared operator in ONE call: V[0] = x0 / |x0|, m Krylov steps (apply,
  * CGS2 + normalise), Ritz step of the projected matrix on the device, y = normalised Ritz vector -- fixedpoint(H_AC, AC, :SR,
  * Arnoldi(; krylovdim = m, maxiter = 1)) of dmrg.jl:36 without a convergence test and without a host synchronisation.
@@ -432,6 +448,21 @@ int mpsk_vnormalize_dev(mpsk_ctx* ctx, int64_t n, const void* x, void* y, void* 
 int mpsk_vritz_dev(mpsk_ctx* ctx, int m, int stride, const void* dev_slot, void* dev_coef, void* dev_info);
 int mpsk_vlincomb_dev(mpsk_ctx* ctx, int64_t n, int k, const void* const* xs, const void* dev_coefs, void* y);
 int mpsk_vnrm2_dev(mpsk_ctx* ctx, int64_t n, const void* x, void* dev_out);
+/* Complex forms of the protocol, for Krylov spaces over the complex numbers: the GMRES of a correction-vector site solve
+ * with complex z (corvector.jl:68: KrylovKit's linsolve on a ComplexF64 tensor, inner = conj(x) . y).  Vectors are
+ * interleaved complex128, 16-byte aligned, n counts COMPLEX elements, complex scalars are (re, im) pairs.
+ *   mpsk_vdotc       : host_out[0..2) = conj(x) . y
+ *   mpsk_vaxpby_c    : y = alpha x + beta y   (beta = 0: y is not read)
+ *   mpsk_vorth_step_c: mpsk_vorth_step with complex coefficients: CGS2 of y against xs[0..k), k <= 32, then y <- y / ||y||;
+ *                      host_h[2j], host_h[2j + 1] = coefficient on xs[j] (conj(xs[j]) . y, both rounds), *host_beta = ||y||;
+ *                      one host sync
+ *   mpsk_vlincomb_c  : y = sum_j coefs[j] xs[j], host_coefs = 2k doubles; asynchronous like mpsk_vlincomb
+ * Reductions take a fixed order (per-thread partial sums, wavefront reduction, one final reduction launch, no atomics):
+ * results are bit-identical from run to run. */
+int mpsk_vdotc(mpsk_ctx* ctx, int64_t n, const void* x, const void* y, double* host_out);
+int mpsk_vaxpby_c(mpsk_ctx* ctx, int64_t n, const double* alpha, const void* x, const double* beta, void* y);
+int mpsk_vorth_step_c(mpsk_ctx* ctx, int64_t n, int k, const void* const* xs, void* y, double* host_h, double* host_beta);
+int mpsk_vlincomb_c(mpsk_ctx* ctx, int64_t n, int k, const void* const* xs, const double* host_coefs, void* y);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,11 @@ SIGNATURES = {
     "mpsk_dAC2_proj": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mpsk_vdiff_nrm2": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, c_double_p],
+    "mpsk_hac_apply_axpby": [C.c_void_p, c_double_p, C.c_void_p, C.c_int, c_double_p, C.c_void_p],
+    "mpsk_vdotc": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, c_double_p],
+    "mpsk_vaxpby_c": [C.c_void_p, C.c_int64, c_double_p, C.c_void_p, c_double_p, C.c_void_p],
+    "mpsk_vorth_step_c": [C.c_void_p, C.c_int64, C.c_int, c_void_pp, C.c_void_p, c_double_p, c_double_p],
+    "mpsk_vlincomb_c": [C.c_void_p, C.c_int64, C.c_int, c_void_pp, c_double_p, C.c_void_p],
 }
 # symbols without the (ctx, ...) -> int shape
 EXTRA_SYMBOLS = ["mpsk_version", "mpsk_last_error"]

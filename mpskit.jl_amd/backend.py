@@ -257,10 +257,12 @@ class Backend:
         keeps GL / GR alive and releases the device-side object when it is garbage collected."""
         return PreparedHAC(self, H, GL, GR)
 
-    def hac_create_ex(self, H, GL: DTensor, GR: DTensor, canonical: bool = False):
+    def hac_create_ex(self, H, GL: DTensor, GR: DTensor, canonical: bool = False, canonical_c128: bool = False):
         """mpsk_hac_create_ex: as hac_create; canonical=True promises that level 0 of GL and level W-1 of GR are
-        identities (MPSK_HAC_CANONICAL), which lets a real Jordan-form slice take the 16 D^3 operator (mode 3)."""
-        return PreparedHAC(self, H, GL, GR, flags=1 if canonical else 0)
+        identities (MPSK_HAC_CANONICAL), which lets a real Jordan-form slice take the 16 D^3 operator (mode 3).
+        canonical_c128=True (MPSK_HAC_CANONICAL_C128) asks for the same operator on a complex slice; the library checks
+        the identities itself and keeps mode 2 when they do not hold."""
+        return PreparedHAC(self, H, GL, GR, flags=(1 if canonical else 0) | (2 if canonical_c128 else 0))
 
     def dC(self, GL: DTensor, GR: DTensor, c: DTensor, out: DTensor = None, cplx=False):
         if cplx:
@@ -802,6 +804,42 @@ class Backend:
         check(self.lib.mpsk_vlincomb(self.ctx, y.size, len(xs), self._ptrs(xs), cf, y.ptr), "mpsk_vlincomb")
         return y
 
+    # ---- complex forms on interleaved vectors (mpsk_v*_c; sizes in complex elements = half the doubles) ------------
+    @staticmethod
+    def _c2(z):
+        z = complex(z)
+        return (C.c_double * 2)(z.real, z.imag)
+
+    def dotc(self, x: DTensor, y: DTensor):
+        """conj(x) . y of two interleaved complex tensors (mpsk_vdotc)."""
+        assert x.size == y.size and x.size % 2 == 0, (x.shape, y.shape)
+        out = (C.c_double * 2)()
+        check(self.lib.mpsk_vdotc(self.ctx, x.size // 2, x.ptr, y.ptr, out), "mpsk_vdotc")
+        return complex(out[0], out[1])
+
+    def axpby_c(self, alpha, x: DTensor, beta, y: DTensor):
+        """y = alpha x + beta y with complex scalars (mpsk_vaxpby_c)."""
+        assert x.size == y.size and x.size % 2 == 0, (x.shape, y.shape)
+        check(self.lib.mpsk_vaxpby_c(self.ctx, x.size // 2, self._c2(alpha), x.ptr, self._c2(beta), y.ptr), "mpsk_vaxpby_c")
+        return y
+
+    def orth_step_c(self, xs, y: DTensor):
+        """orth_step in complex arithmetic (mpsk_vorth_step_c): returns (h[k] complex = X^H y, beta)."""
+        k = len(xs)
+        out = (C.c_double * (2 * k))()
+        beta = C.c_double()
+        check(self.lib.mpsk_vorth_step_c(self.ctx, y.size // 2, k, self._ptrs(xs), y.ptr, out, C.byref(beta)),
+              "mpsk_vorth_step_c")
+        return np.array(out[:]).view(np.complex128).copy(), beta.value
+
+    def lincomb_c(self, xs, coefs, out: DTensor = None):
+        """out = sum_j coefs[j] xs[j] with complex coefficients (mpsk_vlincomb_c)."""
+        y = self.empty(xs[0].shape) if out is None else out
+        flat = np.ascontiguousarray(np.asarray(coefs, dtype=np.complex128)[:len(xs)]).view(np.float64)
+        cf = (C.c_double * (2 * len(xs)))(*flat)
+        check(self.lib.mpsk_vlincomb_c(self.ctx, y.size // 2, len(xs), self._ptrs(xs), cf, y.ptr), "mpsk_vlincomb_c")
+        return y
+
 
 class PreparedHAC:
     """Owner of an mpsk_hac handle (include/mpsk.h): `apply(x, out, nblk)` is one matvec."""
@@ -833,6 +871,16 @@ class PreparedHAC:
         assert x.shape == (m * self.Dl, self.d, self.Dr), (x.shape, (m * self.Dl, self.d, self.Dr))
         y = self.be.empty(m * self.Dlo, self.d, self.Dr) if out is None else out
         check(self.be.lib.mpsk_hac_apply(self.handle, x.ptr, int(nblk), y.ptr), "mpsk_hac_apply")
+        return y
+
+    def apply_axpby(self, a1, x: DTensor, a0, out: DTensor = None, nblk=1):
+        """out = a0 x + a1 (H x) (mpsk_hac_apply_axpby): the shifted operator of a linear solve.  Complex scalars for a
+        complex operator; a real operator takes their real parts."""
+        m = 2 if self.cplx else 1
+        assert x.shape == (m * self.Dl, self.d, self.Dr), (x.shape, (m * self.Dl, self.d, self.Dr))
+        y = self.be.empty(m * self.Dlo, self.d, self.Dr) if out is None else out
+        check(self.be.lib.mpsk_hac_apply_axpby(self.handle, Backend._c2(a1), x.ptr, int(nblk), Backend._c2(a0), y.ptr),
+              "mpsk_hac_apply_axpby")
         return y
 
     def eigsolve_fixed(self, x0: DTensor, m: int, vecs, scal: DTensor, out: DTensor, first_image: DTensor = None):

@@ -435,14 +435,17 @@ static int mposlice_build(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l
     for (int t = 0; t < d; ++t) if (per_t[t] > s->rc_nseg) s->rc_nseg = per_t[t];
     HIPCHK(mix_plan_create(rc, (int)s->rc_w.size(), s->Wr, &s->rc));
   }
-  if (!cx && odim >= 2 && chi_l[0] == 1 && chi_r[0] == 1 && chi_l[odim - 1] == 1 && chi_r[odim - 1] == 1) {
+  // (complex slices: the same form with complex C / B / D blocks and exactly real identity corners; they feed the complex
+  // mode 3 of mpsk_hac_create_ex, MPSK_HAC_CANONICAL_C128, and nothing else)
+  if (odim >= 2 && chi_l[0] == 1 && chi_r[0] == 1 && chi_l[odim - 1] == 1 && chi_r[odim - 1] == 1) {
     const int Wl = s->Wl, Wr = s->Wr;
     bool ok = true;
     for (int t = 0; t < d && ok; ++t)
       for (int si = 0; si < d && ok; ++si) {
-        ok = s->O(0, t, si, 0) == (t == si ? 1.0 : 0.0) && s->O(Wl - 1, t, si, Wr - 1) == (t == si ? 1.0 : 0.0);
+        ok = s->O(0, t, si, 0) == (t == si ? 1.0 : 0.0) && s->O(Wl - 1, t, si, Wr - 1) == (t == si ? 1.0 : 0.0) &&
+             s->Oi(0, t, si, 0) == 0.0 && s->Oi(Wl - 1, t, si, Wr - 1) == 0.0;
         for (int v = 0; v < Wr - 1 && ok; ++v)
-          for (int w = 1; w < Wl && ok; ++w) ok = s->O(w, t, si, v) == 0.0;
+          for (int w = 1; w < Wl && ok; ++w) ok = s->O(w, t, si, v) == 0.0 && s->Oi(w, t, si, v) == 0.0;
       }
     if (ok) {
       std::vector<MixTerm> jr, jl;
@@ -451,9 +454,13 @@ static int mposlice_build(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l
         for (int si = 0; si < d; ++si) {
           const int p = si + d * t;
           for (int v = 0; v < Wr; ++v)
-            if (s->O(0, t, si, v) != 0.0) { jr.push_back({p, v, s->O(0, t, si, v)}); r_used[p] = 1; }
+            if (s->O(0, t, si, v) != 0.0 || s->Oi(0, t, si, v) != 0.0) {
+              jr.push_back({p, v, s->O(0, t, si, v), s->Oi(0, t, si, v)}); r_used[p] = 1;
+            }
           for (int w = 1; w < Wl; ++w)
-            if (s->O(w, t, si, Wr - 1) != 0.0) { jl.push_back({p, w, s->O(w, t, si, Wr - 1)}); l_used[p] = 1; }
+            if (s->O(w, t, si, Wr - 1) != 0.0 || s->Oi(w, t, si, Wr - 1) != 0.0) {
+              jl.push_back({p, w, s->O(w, t, si, Wr - 1), s->Oi(w, t, si, Wr - 1)}); l_used[p] = 1;
+            }
         }
       // per-t slab lists, padded with an empty slab of the family (one exists whenever a list is shorter than the longest)
       auto lists = [&](const std::vector<char>& used, std::vector<int>& out, int& nseg) {
@@ -475,7 +482,7 @@ static int mposlice_build(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l
       HIPCHK(mix_plan_create(jr, d * d, Wr, &s->jr));
       HIPCHK(mix_plan_create(jl, d * d, Wl, &s->jl));
       s->jordan = s->jr_nseg > 0 && s->jl_nseg > 0;
-      if (s->jordan) {
+      if (s->jordan && !cx) {
         std::vector<MixTerm> tl, tr;
         for (int t = 0; t < d; ++t)
           for (int si = 0; si < d; ++si) {
@@ -1043,7 +1050,7 @@ int mpsk_hac_create(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
 int mpsk_hac_create_ex(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
                        int flags, mpsk_hac** out) {
   REQUIRE(c && H && GL && GR && out, "NULL argument");
-  REQUIRE((flags & ~MPSK_HAC_CANONICAL) == 0, "unknown flags");
+  REQUIRE((flags & ~(MPSK_HAC_CANONICAL | MPSK_HAC_CANONICAL_C128)) == 0, "unknown flags");
   REQUIRE(Dlo > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
@@ -1080,6 +1087,49 @@ int mpsk_hac_create_ex(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int
     // complex128: mix form; what is prepared once per site is the planar copy of the right environment (the B operand
     // of stage 3), so that an application converts only x
     h->mode = 2;
+    // MPSK_HAC_CANONICAL_C128: the Jordan-form operator for a complex slice.  The conditions of the real mode 3, and the
+    // identities are CHECKED here (two small launches, one synchronisation per prepared operator): a candidate whose
+    // GL[0] or GR[W-1] is off by more than 1e-10 keeps mode 2 (MPSK_HAC_CHECK=1: fails, as the real mode does).
+    bool jc = (flags & MPSK_HAC_CANONICAL_C128) && H->jordan && Dlo == Dl;
+    if (jc) {
+      const int nbk = 100;
+      double dl = 0.0, dr = 0.0;
+      HIPCHK(identity_dev_c((const double*)GL, Dl, c->d_scal, nbk, c->stream));
+      HIPCHK(identity_dev_c((const double*)GR + (size_t)(Wr - 1) * 2 * Dr * Dr, Dr, c->d_scal + nbk, nbk, c->stream));
+      HIPCHK(hipMemcpyAsync(c->h_scal, c->d_scal, sizeof(double) * 2 * nbk, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      for (int i = 0; i < nbk; ++i) { dl = std::max(dl, c->h_scal[i]); dr = std::max(dr, c->h_scal[nbk + i]); }
+      if (!(dl <= 1e-10 && dr <= 1e-10)) {
+        if (getenv("MPSK_HAC_CHECK") && getenv("MPSK_HAC_CHECK")[0] == '1') {
+          delete h;
+          char msg[160];
+          snprintf(msg, sizeof(msg), "MPSK_HAC_CHECK: environments are not canonical (max|GL[0] - I| = %.3e, max|GR[W-1] - I| = %.3e)", dl, dr);
+          return fail(MPSK_ERR_INVALID, msg);
+        }
+        jc = false;
+      }
+    }
+    if (jc) {
+      // folded slabs p = s + d t, contiguous: GRc0[p] [Dr, Dr] as two planes (the B operand of x GRc0), GLc[p] [Dlo, Dl]
+      // interleaved (the A operand of GLc x); the interleaved fold of GR is staged behind them in the same buffer
+      h->mode = 3;
+      const size_t nR = (size_t)d * d * Dr * Dr, nL = (size_t)d * d * Dlo * Dl;
+      void* buf = nullptr;
+      if (int rc = pool_take(c, sizeof(double) * (2 * ev2(nR) + 2 * nL + 2 * nR), &buf, &h->pool_idx)) { delete h; return rc; }
+      h->GRc = (double*)buf;
+      h->GLc = h->GRc + 2 * ev2(nR);
+      double* stage = h->GLc + 2 * nL;
+      SlabIndex ir{1 << 30, 1, (int64_t)2 * Dr * Dr, 0, 0, (int64_t)2 * Dr}, il{1 << 30, 1, (int64_t)2 * Dlo * Dl, 0, 0, (int64_t)2 * Dlo};
+      hipError_t e = mix_apply(H->jr, (const double*)GR, ir, stage, ir, 2 * Dr, Dr, c->stream);
+      if (e == hipSuccess) e = cx_planes(stage, nR, h->GRc, h->GRc + ev2(nR), c->stream);
+      if (e == hipSuccess) e = mix_apply(H->jl, (const double*)GL, il, h->GLc, il, 2 * Dlo, Dl, c->stream);
+      if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        c->pool[h->pool_idx].used = false; delete h; return fail(MPSK_ERR_HIP, hipGetErrorString(e));
+      }
+      *out = h;
+      return MPSK_OK;
+    }
     const size_t nG = (size_t)Wr * Dr * Dr;
     void* buf = nullptr;
     if (int rc = pool_take(c, sizeof(double) * 2 * ev2(nG), &buf, &h->pool_idx)) { delete h; return rc; }
@@ -1170,12 +1220,45 @@ int mpsk_hac_info(const mpsk_hac* h, int* mode, int* nslabs) {
   return MPSK_OK;
 }
 
+// complex mode 3: y[:, t, :] = sum_s x[:, s, :] GRc0[(s, t)] + sum_s GLc[(s, t)] x[:, s, :], two launches batched over t with
+// all d values of s as K-segments (re and im plane of the B operand each, the second through the J loader): 16 d^2 D^3
+// real flops, against 16 (Wl + Wr) d D^3 of the mix form
+static int hac_apply_jordan_c128(mpsk_hac* h, const double* x, double* y) {
+  mpsk_ctx* c = h->ctx;
+  const int d = h->H->d, Dlo = h->Dlo, Dl = h->Dl, Dr = h->Dr;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t nx = (size_t)Dl * d * Dr, nR = (size_t)d * d * Dr * Dr;
+  if (int rc = ensure_ws(c, sizeof(double) * 2 * ev2(nx))) return rc;
+  double* xp = (double*)c->ws;
+  HIPCHK(cx_planes(x, nx, xp, xp + ev2(nx), c->stream));
+  std::vector<int64_t> sa, sb;
+  std::vector<int> sj;
+  for (int si = 0; si < d; ++si)
+    for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)si * 2 * Dl); sb.push_back((int64_t)(pl * ev2(nR) + (size_t)si * Dr * Dr)); sj.push_back(pl); }
+  GemmArgs g1 = mk(x, h->GRc, y, 2 * Dlo, Dr, Dr, (int64_t)2 * Dl * d, Dr, (int64_t)2 * Dlo * d);
+  g1.batch = d; g1.bsA = 0; g1.bsB = (int64_t)d * Dr * Dr; g1.bsC = (int64_t)2 * Dlo;
+  g1.cplx = 1;
+  HIPCHK(gemm_segments(g1, sa, sb, c->stream, &sj));
+  sa.clear(); sb.clear(); sj.clear();
+  for (int si = 0; si < d; ++si)
+    for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)si * 2 * Dlo * Dl); sb.push_back((int64_t)(pl * ev2(nx) + (size_t)si * Dl)); sj.push_back(pl); }
+  GemmArgs g2 = mk(h->GLc, xp, y, 2 * Dlo, Dr, Dl, (int64_t)2 * Dlo, (int64_t)Dl * d, (int64_t)2 * Dlo * d);
+  g2.batch = d; g2.bsA = (int64_t)d * 2 * Dlo * Dl; g2.bsB = 0; g2.bsC = (int64_t)2 * Dlo;
+  g2.cplx = 1; g2.beta = 1.0;
+  HIPCHK(gemm_segments(g2, sa, sb, c->stream, &sj));
+  return MPSK_OK;
+}
+
 int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
   REQUIRE(h && x && y, "NULL argument");
   mpsk_ctx* c = h->ctx;
   const mpsk_mposlice* H = h->H;
   const int Dlo = h->Dlo, Dl = h->Dl, Dr = h->Dr;
   REQUIRE(nblk >= 1 && nblk <= MAXSEG && Dl % nblk == 0, "nblk must divide Dl (and be <= 32)");
+  if (h->mode == 3 && H->dtype == MPSK_C128) {
+    if (nblk != 1) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_hac_apply: the blocked layout is implemented for MPSK_F64 only");
+    return hac_apply_jordan_c128(h, (const double*)x, (double*)y);
+  }
   if (h->mode == 2) {
     if (nblk != 1) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_hac_apply: the blocked layout is implemented for MPSK_F64 only");
     return dAC_c128(c, H, Dlo, Dl, Dr, Dr, h->GL, h->GR, h->GRc, (const double*)x, (double*)y);
@@ -1231,6 +1314,30 @@ int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
   return MPSK_OK;
 }
 
+// y = a0 x + a1 (H_AC x): the shifted operator of linsolve(H_AC, b, x0, alg, a0, a1) (corvector.jl:68, :123).  The
+// application is mpsk_hac_apply itself (every mode, same launches, same bits); the shift and the scale are ONE fused
+// vector pass over x and y behind its last GEMM.  a0 = 0, a1 = 1 adds nothing to mpsk_hac_apply.
+int mpsk_hac_apply_axpby(mpsk_hac* h, const double* a1, const void* x, int nblk, const double* a0, void* y) {
+  REQUIRE(h && x && y && a0 && a1, "NULL argument");
+  REQUIRE(x != y, "x and y must not alias");
+  const bool cplx = h->H->dtype == MPSK_C128;
+  const bool shift = a0[0] != 0.0 || (cplx && a0[1] != 0.0);
+  const bool scale = a1[0] != 1.0 || (cplx && a1[1] != 0.0);
+  REQUIRE(!shift || (h->Dlo == h->Dl && nblk == 1), "a shift needs a square operator (Dlo == Dl) on the plain vector layout");
+  if (int rc = mpsk_hac_apply(h, x, nblk, y)) return rc;
+  if (!shift && !scale) return MPSK_OK;
+  mpsk_ctx* c = h->ctx;
+  const int64_t n = (int64_t)h->Dlo * h->H->d * h->Dr;
+  if (cplx) {
+    HIPCHK(vec_axpby_c(a0, shift ? (const double*)x : nullptr, a1, (double*)y, n, c->stream));
+  } else if (shift) {
+    HIPCHK(vec_axpby(a0[0], (const double*)x, a1[0], (double*)y, n, c->stream));
+  } else {
+    HIPCHK(vec_scal(a1[0], (double*)y, n, c->stream));
+  }
+  return MPSK_OK;
+}
+
 // Fixed-budget smallest-real solve with the prepared operator, one call per site (fixedpoint(H_AC, AC, :SR, alg) of
 // dmrg.jl:36 with Arnoldi(; krylovdim = m, maxiter = 1) and no convergence test): V[0] = x0 / |x0|, m Krylov steps
 // (apply, CGS2 + normalise), Ritz step of the m x m projected matrix on the device, y = normalised Ritz vector.  Nothing is
@@ -1241,7 +1348,7 @@ int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
 int mpsk_hac_eigsolve_fixed(mpsk_hac* h, const void* x0, int m, void* const* V, void* scal, void* y, void* first_image) {
   REQUIRE(h && x0 && V && scal && y, "NULL argument");
   REQUIRE(m >= 1 && m <= 32, "needs 1 <= m <= 32");
-  REQUIRE(h->mode != 2, "mpsk_hac_eigsolve_fixed: MPSK_F64 operators only");
+  REQUIRE(h->H->dtype == MPSK_F64, "mpsk_hac_eigsolve_fixed: MPSK_F64 operators only");
   mpsk_ctx* c = h->ctx;
   HIPCHK(hipSetDevice(c->device));
   const int64_t n = (int64_t)h->Dlo * h->H->d * h->Dr;
@@ -3005,6 +3112,63 @@ int mpsk_vaxpby(mpsk_ctx* c, int64_t n, double alpha, const void* x, double beta
   HIPCHK(vec_axpby(alpha, (const double*)x, beta, (double*)y, n, c->stream));
   return MPSK_OK;
 }
+// ---- complex forms of the vector protocol: interleaved complex128 vectors, n = complex elements ----------------------
+static bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
+int mpsk_vdotc(mpsk_ctx* c, int64_t n, const void* x, const void* y, double* host_out) {
+  REQUIRE(c && x && y && host_out, "NULL argument");
+  REQUIRE(n > 0, "bad n");
+  REQUIRE(aligned16(x) && aligned16(y), "operands must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  const double* xs[1] = {(const double*)x};
+  HIPCHK(vec_multidotc(xs, 1, (const double*)y, n, c->d_scal, c->d_partial, c->stream));
+  return fetch_scalars(c, 2, host_out);
+}
+
+int mpsk_vaxpby_c(mpsk_ctx* c, int64_t n, const double* alpha, const void* x, const double* beta, void* y) {
+  REQUIRE(c && x && y && alpha && beta, "NULL argument");
+  REQUIRE(n > 0, "bad n");
+  REQUIRE(aligned16(x) && aligned16(y), "operands must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(vec_axpby_c(alpha, (const double*)x, beta, (double*)y, n, c->stream));
+  return MPSK_OK;
+}
+
+// mpsk_vorth_step in complex arithmetic: CGS2 of y against xs[0..k), y <- y / ||y||, ONE host sync.  host_h: k complex
+// coefficients (h = X^H y, both rounds summed), *host_beta = ||y|| before the normalisation.
+int mpsk_vorth_step_c(mpsk_ctx* c, int64_t n, int k, const void* const* xs, void* y, double* host_h, double* host_beta) {
+  REQUIRE(c && xs && y && host_h && host_beta, "NULL argument");
+  REQUIRE(k > 0 && k <= 32 && n > 0, "needs 0 < k <= 32 and n > 0");
+  REQUIRE(aligned16(y), "operands must be 16-byte aligned");
+  for (int j = 0; j < k; ++j) REQUIRE(xs[j] && aligned16(xs[j]) && xs[j] != y, "basis vectors must be 16-byte aligned and distinct from y");
+  HIPCHK(hipSetDevice(c->device));
+  double* yy = (double*)y;
+  HIPCHK(vec_cgs2_c((const double* const*)xs, k, yy, n, c->d_scal, c->d_partial, c->stream));
+  HIPCHK(vec_scal_rsqrt_dev(c->d_scal + 4 * k, yy, 2 * n, c->stream));
+  double tmp[MAXK];
+  if (int rc = fetch_scalars(c, 4 * k + 1, tmp)) return rc;
+  for (int j = 0; j < 2 * k; ++j) host_h[j] = tmp[j] + tmp[2 * k + j];
+  *host_beta = tmp[4 * k] > 0.0 ? std::sqrt(tmp[4 * k]) : 0.0;
+  return MPSK_OK;
+}
+
+// y = sum_j coefs[j] xs[j] with complex coefficients (host_coefs: 2k doubles); asynchronous like mpsk_vlincomb
+int mpsk_vlincomb_c(mpsk_ctx* c, int64_t n, int k, const void* const* xs, const double* host_coefs, void* y) {
+  REQUIRE(c && xs && y && host_coefs, "NULL argument");
+  REQUIRE(k > 0 && 2 * k <= MAXK && n > 0, "bad k or n");
+  REQUIRE(aligned16(y), "operands must be 16-byte aligned");
+  for (int j = 0; j < k; ++j) REQUIRE(xs[j] && aligned16(xs[j]) && xs[j] != y, "inputs must be 16-byte aligned and distinct from y");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->coef_pending) { HIPCHK(hipEventSynchronize(c->ev_coef)); c->coef_pending = false; }
+  std::memcpy(c->h_coef, host_coefs, sizeof(double) * 2 * k);
+  HIPCHK(hipMemcpyAsync(c->d_coef, c->h_coef, sizeof(double) * 2 * k, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(c->ev_coef, c->stream));
+  c->coef_pending = true;
+  HIPCHK(hipMemsetAsync(y, 0, sizeof(double) * 2 * n, c->stream));
+  HIPCHK(vec_multiaxpy_c((const double* const*)xs, c->d_coef, k, 1.0, (double*)y, n, c->stream));
+  return MPSK_OK;
+}
+
 int mpsk_vscal(mpsk_ctx* c, int64_t n, double alpha, void* x) {
   REQUIRE(c && x, "NULL argument");
   HIPCHK(hipSetDevice(c->device));

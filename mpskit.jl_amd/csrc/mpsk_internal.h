@@ -141,6 +141,15 @@ hipError_t vec_multilincomb(const double* const* xs, int k, double* const* ys, i
                             hipStream_t s);   // ys[j] = sum_i d_coefs[i + k j] xs[i]; k, m <= 32
 hipError_t vec_multiaxpy(const double* const* xs, const double* d_coefs, int k, double sign, double* y,
                          int64_t n, hipStream_t s);
+// complex128 forms (interleaved vectors, n = complex elements, complex scalars as (re, im) pairs); d_out of vec_multidotc:
+// [2k], of vec_cgs2_c: {h1[2k], h2[2k], |y|^2}; vec_axpby_c: y = a x + b y, x == nullptr: y = b y
+hipError_t vec_multidotc(const double* const* xs, int k, const double* y, int64_t n, double* d_out, double* d_partial,
+                         hipStream_t s);
+hipError_t vec_multiaxpy_c(const double* const* xs, const double* d_coefs, int k, double sign, double* y, int64_t n,
+                           hipStream_t s);
+hipError_t vec_cgs2_c(const double* const* xs, int k, double* y, int64_t n, double* d_out, double* d_partial, hipStream_t s);
+hipError_t vec_axpby_c(const double a[2], const double* x, const double b[2], double* y, int64_t n, hipStream_t s);
+hipError_t identity_dev_c(const double* G, int n, double* d_out, int nblocks, hipStream_t s);   // d_out[b]: per-block max|G - I|
 
 // ---- gauge kernels ----------------------------------------------------------------------------
 size_t regularize_workspace_doubles(int W, int D1, int D2);

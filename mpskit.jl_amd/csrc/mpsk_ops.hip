@@ -781,4 +781,166 @@ hipError_t vec_multiaxpy(const double* const* xs, const double* d_coefs, int k, 
   return hipGetLastError();
 }
 
+// ---- complex128 forms of the Krylov vector protocol -------------------------------------------------------------------
+// Interleaved complex vectors, n counts COMPLEX elements (one d2 per element).  Same reduction structure as the real
+// kernels: per-thread accumulation in a fixed element order, wavefront reduction, one final reduction launch
+// (dot_final_kernel); the grid is the one multidot_kernel takes for the 2n doubles.
+// partial[(2j) * DOT_BLOCKS + b] / partial[(2j + 1) * DOT_BLOCKS + b] = block b's share of Re / Im conj(xs[j]) . y
+template <int NVEC>
+__global__ __launch_bounds__(256) void multidotc_kernel(PtrPack xs, const double* __restrict__ y, int64_t n,
+                                                        double* __restrict__ partial) {
+  __shared__ double sh[4 * 2 * NVEC];
+  double acc[2 * NVEC];
+#pragma unroll
+  for (int j = 0; j < 2 * NVEC; ++j) acc[j] = 0.0;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    const d2 yv = *reinterpret_cast<const d2*>(y + 2 * e);
+#pragma unroll
+    for (int j = 0; j < NVEC; ++j) {
+      const d2 xv = *reinterpret_cast<const d2*>(xs.p[j] + 2 * e);
+      acc[2 * j] += xv.x * yv.x + xv.y * yv.y;
+      acc[2 * j + 1] += xv.x * yv.y - xv.y * yv.x;
+    }
+  }
+  block_sum<2 * NVEC>(acc, sh);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < 2 * NVEC; ++j) partial[(int64_t)j * DOT_BLOCKS + blockIdx.x] = acc[j];
+  }
+}
+
+// d_out[2j], d_out[2j + 1] = Re, Im of conj(xs[j]) . y
+hipError_t vec_multidotc(const double* const* xs, int k, const double* y, int64_t n, double* d_out, double* d_partial,
+                         hipStream_t s) {
+  if (n <= 0 || k <= 0) return hipErrorInvalidValue;
+  const int nb = dot_grid(2 * n);
+  for (int j0 = 0; j0 < k; j0 += MD) {
+    const int nv = k - j0 < MD ? k - j0 : MD;
+    PtrPack pk;
+    for (int j = 0; j < MD; ++j) pk.p[j] = xs[j0 + (j < nv ? j : 0)];
+    switch (nv) {
+      case 1: hipLaunchKernelGGL(multidotc_kernel<1>, dim3(nb), dim3(256), 0, s, pk, y, n, d_partial); break;
+      case 2: hipLaunchKernelGGL(multidotc_kernel<2>, dim3(nb), dim3(256), 0, s, pk, y, n, d_partial); break;
+      case 3: hipLaunchKernelGGL(multidotc_kernel<3>, dim3(nb), dim3(256), 0, s, pk, y, n, d_partial); break;
+      case 4: hipLaunchKernelGGL(multidotc_kernel<4>, dim3(nb), dim3(256), 0, s, pk, y, n, d_partial); break;
+      case 5: hipLaunchKernelGGL(multidotc_kernel<5>, dim3(nb), dim3(256), 0, s, pk, y, n, d_partial); break;
+      case 6: hipLaunchKernelGGL(multidotc_kernel<6>, dim3(nb), dim3(256), 0, s, pk, y, n, d_partial); break;
+      case 7: hipLaunchKernelGGL(multidotc_kernel<7>, dim3(nb), dim3(256), 0, s, pk, y, n, d_partial); break;
+      default: hipLaunchKernelGGL(multidotc_kernel<8>, dim3(nb), dim3(256), 0, s, pk, y, n, d_partial); break;
+    }
+    hipLaunchKernelGGL(dot_final_kernel, dim3(2 * nv), dim3(256), 0, s, d_partial, nb, d_out + 2 * j0);
+  }
+  return hipGetLastError();
+}
+
+// y += sign * sum_j coefs[j] * xs[j] with complex coefficients (interleaved, on the device)
+template <int NVEC>
+__global__ __launch_bounds__(256) void multiaxpy_c_kernel(PtrPack xs, const double* __restrict__ coefs, double sign,
+                                                          double* __restrict__ y, int64_t n) {
+  double cr[NVEC], ci[NVEC];
+#pragma unroll
+  for (int j = 0; j < NVEC; ++j) { cr[j] = sign * coefs[2 * j]; ci[j] = sign * coefs[2 * j + 1]; }
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    d2 yv = *reinterpret_cast<const d2*>(y + 2 * e);
+#pragma unroll
+    for (int j = 0; j < NVEC; ++j) {
+      const d2 xv = *reinterpret_cast<const d2*>(xs.p[j] + 2 * e);
+      yv.x += cr[j] * xv.x - ci[j] * xv.y;
+      yv.y += cr[j] * xv.y + ci[j] * xv.x;
+    }
+    *reinterpret_cast<d2*>(y + 2 * e) = yv;
+  }
+}
+
+hipError_t vec_multiaxpy_c(const double* const* xs, const double* d_coefs, int k, double sign, double* y, int64_t n,
+                           hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  int64_t nb64 = (n + 255) / 256;
+  if (nb64 > 4096) nb64 = 4096;
+  const int nb = (int)nb64;
+  for (int j0 = 0; j0 < k; j0 += MD) {
+    const int nv = k - j0 < MD ? k - j0 : MD;
+    PtrPack pk;
+    for (int j = 0; j < MD; ++j) pk.p[j] = xs[j0 + (j < nv ? j : 0)];
+    const double* cf = d_coefs + 2 * j0;
+    switch (nv) {
+      case 1: hipLaunchKernelGGL(multiaxpy_c_kernel<1>, dim3(nb), dim3(256), 0, s, pk, cf, sign, y, n); break;
+      case 2: hipLaunchKernelGGL(multiaxpy_c_kernel<2>, dim3(nb), dim3(256), 0, s, pk, cf, sign, y, n); break;
+      case 3: hipLaunchKernelGGL(multiaxpy_c_kernel<3>, dim3(nb), dim3(256), 0, s, pk, cf, sign, y, n); break;
+      case 4: hipLaunchKernelGGL(multiaxpy_c_kernel<4>, dim3(nb), dim3(256), 0, s, pk, cf, sign, y, n); break;
+      case 5: hipLaunchKernelGGL(multiaxpy_c_kernel<5>, dim3(nb), dim3(256), 0, s, pk, cf, sign, y, n); break;
+      case 6: hipLaunchKernelGGL(multiaxpy_c_kernel<6>, dim3(nb), dim3(256), 0, s, pk, cf, sign, y, n); break;
+      case 7: hipLaunchKernelGGL(multiaxpy_c_kernel<7>, dim3(nb), dim3(256), 0, s, pk, cf, sign, y, n); break;
+      default: hipLaunchKernelGGL(multiaxpy_c_kernel<8>, dim3(nb), dim3(256), 0, s, pk, cf, sign, y, n); break;
+    }
+  }
+  return hipGetLastError();
+}
+
+// CGS2 of y against xs[0..k) in complex arithmetic, d_out = {h1[2k], h2[2k], |y_final|^2}: h = X^H y, y -= X h, twice,
+// then the squared norm of the remainder (the real dot of its 2n doubles).  y is left un-normalised.
+hipError_t vec_cgs2_c(const double* const* xs, int k, double* y, int64_t n, double* d_out, double* d_partial, hipStream_t s) {
+  if (n <= 0 || k <= 0) return hipErrorInvalidValue;
+  hipError_t e;
+  for (int round = 0; round < 2; ++round) {
+    if ((e = vec_multidotc(xs, k, y, n, d_out + 2 * k * round, d_partial, s)) != hipSuccess) return e;
+    if ((e = vec_multiaxpy_c(xs, d_out + 2 * k * round, k, -1.0, y, n, s)) != hipSuccess) return e;
+  }
+  const double* ys[1] = {y};
+  return vec_multidot(ys, 1, y, 2 * n, d_out + 4 * k, d_partial, s);
+}
+
+// y = a x + b y with complex a, b  (b == 0: y is not read; x == nullptr: y = b y)
+__global__ __launch_bounds__(256) void axpby_c_kernel(double ar, double ai, const double* __restrict__ x, double br, double bi,
+                                                      double* __restrict__ y, int64_t n) {
+  const bool bz = br == 0.0 && bi == 0.0;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    d2 r = {0.0, 0.0};
+    if (x) {
+      const d2 xv = *reinterpret_cast<const d2*>(x + 2 * e);
+      r.x = ar * xv.x - ai * xv.y;
+      r.y = ar * xv.y + ai * xv.x;
+    }
+    if (!bz) {
+      const d2 yv = *reinterpret_cast<const d2*>(y + 2 * e);
+      r.x += br * yv.x - bi * yv.y;
+      r.y += br * yv.y + bi * yv.x;
+    }
+    *reinterpret_cast<d2*>(y + 2 * e) = r;
+  }
+}
+
+hipError_t vec_axpby_c(const double a[2], const double* x, const double b[2], double* y, int64_t n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  int64_t nb = (n + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(axpby_c_kernel, dim3((int)nb), dim3(256), 0, s, a[0], a[1], x, b[0], b[1], y, n);
+  return hipGetLastError();
+}
+
+// out[b] = block b's share of max |G - I| over an n x n interleaved complex matrix (contiguous, ld = n complex): the
+// eligibility test of the complex Jordan-form operator.  The caller takes the maximum of the nblocks values.
+__global__ __launch_bounds__(256) void identity_dev_c_kernel(const double* __restrict__ G, int n, double* __restrict__ out) {
+  __shared__ double sh[256];
+  double m = 0.0;
+  const int64_t total = (int64_t)n * n;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const d2 v = *reinterpret_cast<const d2*>(G + 2 * e);
+    const double re = v.x - ((e % n) == (e / n) ? 1.0 : 0.0);
+    m = fmax(m, fmax(fabs(re), fabs(v.y)));
+  }
+  sh[threadIdx.x] = m;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + off]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
+}
+
+hipError_t identity_dev_c(const double* G, int n, double* d_out, int nblocks, hipStream_t s) {
+  hipLaunchKernelGGL(identity_dev_c_kernel, dim3(nblocks), dim3(256), 0, s, G, n, d_out);
+  return hipGetLastError();
+}
+
 }  // namespace mpsk

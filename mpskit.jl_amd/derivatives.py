@@ -43,6 +43,15 @@ class MPO_ddAC:  # MPO_∂∂AC  derivatives.jl:11-15
 
     __mul__ = __call__
 
+    def apply_axpby(self, a1, x: DTensor, a0, out: DTensor = None):
+        """out = a0 x + a1 (H_AC x) in one library call (mpsk_hac_apply_axpby): what a shifted linear solve applies."""
+        if not hasattr(self.be, "hac_create"):                   # host stand-in backend of the CPU tests
+            if complex(a0).imag != 0.0 or complex(a1).imag != 0.0:
+                raise TypeError("MPO_ddAC.apply_axpby on a real backend takes real a0 and a1")
+            y = self.be.dAC(self.o, self.leftenv, self.rightenv, x, out=out)
+            return self.be.axpby(complex(a0).real, x, complex(a1).real, y)
+        return self._prepare().apply_axpby(a1, x, a0, out=out)
+
     def eigsolve_fixed(self, x0: DTensor, m: int, vecs, scal: DTensor, out: DTensor, first_image: DTensor = None):
         """Fixed-budget :SR solve in one library call (mpsk_hac_eigsolve_fixed); None if this operator cannot take it
         (host stand-in backend, complex operator)."""

@@ -398,6 +398,153 @@ def gmres(be: Backend, matvec, b: DTensor, x0: DTensor, tol=1e-12, krylovdim=30,
     return x
 
 
+class _RealVec:
+    """the vector arithmetic linsolve needs, on real vectors (the backend's own methods)"""
+
+    def __init__(self, be):
+        self.be = be
+        self.dtype = float
+
+    def dot(self, x, y):
+        return self.be.dot(x, y)
+
+    def axpby(self, a, x, b, y):
+        return self.be.axpby(float(np.real(a)), x, float(np.real(b)), y)
+
+    def orth_step(self, xs, y):
+        return self.be.orth_step(xs, y)
+
+    def lincomb(self, xs, coefs, out):
+        return self.be.lincomb(xs, np.real(coefs), out=out)
+
+
+class ComplexVec:
+    """the same on INTERLEAVED complex vectors: conj(x) . y, complex linear combinations, complex CGS2 (mpsk_vdotc /
+    mpsk_vaxpby_c / mpsk_vorth_step_c / mpsk_vlincomb_c).  A backend without these entry points (the host stand-in of the
+    CPU tests) gets them composed from its real vector methods and times_i: Im conj(x) . y = <i x, y> on the doubles."""
+
+    def __init__(self, be):
+        self.be = be
+        self.dtype = complex
+
+    def dot(self, x, y):
+        be = self.be
+        if hasattr(be, "dotc"):
+            return be.dotc(x, y)
+        return complex(be.dot(x, y), be.dot(be.times_i(x), y))
+
+    def axpby(self, a, x, b, y):
+        be = self.be
+        a, b = complex(a), complex(b)
+        if hasattr(be, "axpby_c"):
+            return be.axpby_c(a, x, b, y)
+        ix = be.times_i(x) if a.imag != 0.0 else None
+        if b == 0:
+            be.axpby(a.real, x, 0.0, y)
+        else:
+            if b.imag != 0.0:
+                be.axpby(b.imag, be.times_i(y), b.real, y)
+            elif b.real != 1.0:
+                be.scal(b.real, y)
+            be.axpby(a.real, x, 1.0, y)
+        if ix is not None:
+            be.axpby(a.imag, ix, 1.0, y)
+        return y
+
+    def orth_step(self, xs, y):
+        be = self.be
+        if hasattr(be, "orth_step_c"):
+            return be.orth_step_c(xs, y)
+        h = np.zeros(len(xs), dtype=complex)
+        for _ in range(2):
+            hh = np.array([self.dot(x, y) for x in xs])
+            for c, x in zip(hh, xs):
+                self.axpby(-c, x, 1.0, y)
+            h += hh
+        beta = be.norm(y)
+        if beta > 0:
+            be.scal(1.0 / beta, y)
+        return h, beta
+
+    def lincomb(self, xs, coefs, out):
+        be = self.be
+        if hasattr(be, "lincomb_c"):
+            return be.lincomb_c(xs, coefs, out=out)
+        self.axpby(coefs[0], xs[0], 0.0, out)
+        for c, x in zip(coefs[1:], xs[1:]):
+            self.axpby(c, x, 1.0, out)
+        return out
+
+
+class ConvergenceInfo:
+    """what KrylovKit's linsolve returns next to the solution: converged (0 / 1), normres, numiter (restart cycles),
+    numops (operator applications); hessenberg: the projected matrix of the last cycle."""
+
+    def __init__(self, converged, normres, numiter, numops, hessenberg):
+        self.converged, self.normres, self.numiter, self.numops = converged, normres, numiter, numops
+        self.hessenberg = hessenberg
+
+
+def linsolve(be: Backend, op, b: DTensor, x0: DTensor, a0=0.0, a1=1.0, tol=1e-12, krylovdim=30, maxiter=100,
+             ws: KrylovWorkspace | None = None, cplx=False):
+    """linsolve(op, b, x0, GMRES(; tol, krylovdim, maxiter), a0, a1): solve (a0 + a1 op) x = b by restarted GMRES
+    (KrylovKit, as called by corvector.jl:68, :123).  op(x, out) -> out; an operator with `apply_axpby(a1, x, a0, out)`
+    (a prepared H_AC, LinearCombination) applies the shifted operator in one call.  cplx: the vectors are interleaved
+    complex tensors and a0, a1 may be complex -- the Krylov space is then built over the complex numbers (complex inner
+    products, a complex Hessenberg matrix, complex combinations), not over the reals of the 2n-dimensional embedding, in
+    which multiplication by i is not a scalar.  Converged when the residual norm is <= tol (absolute, as KrylovKit).
+    Never raises on non-convergence.  Returns (x, ConvergenceInfo)."""
+    ws = KrylovWorkspace(be) if ws is None else ws
+    vs = ComplexVec(be) if cplx else _RealVec(be)
+    shape = b.shape
+    nvec = b.size // 2 if cplx else b.size
+    m = int(max(1, min(krylovdim, nvec)))
+    if cplx and hasattr(be, "orth_step_c"):
+        m = min(m, 32)                    # mpsk_vorth_step_c orthogonalises against at most 32 vectors: shorter cycles
+    vecs = ws.get(shape, m + 3, tag="linsolve")
+    V, r, tmp = vecs[:m + 1], vecs[m + 1], vecs[m + 2]
+    shifted = getattr(op, "apply_axpby", None)
+
+    def apply(x, out):
+        if shifted is not None:
+            return shifted(a1, x, a0, out)
+        op(x, out)
+        return vs.axpby(a0, x, a1, out)
+
+    x = be.copy(x0)
+    Hm = np.zeros((m + 1, m), dtype=vs.dtype)
+    numops, numiter, res = 0, 0, np.inf
+    for numiter in range(1, maxiter + 1):
+        apply(x, r)
+        numops += 1
+        vs.axpby(1.0, b, -1.0, r)                       # r = b - (a0 + a1 op) x
+        beta = be.norm(r)
+        res = beta
+        if beta <= tol:
+            break
+        be.axpby(1.0 / beta, r, 0.0, V[0])
+        Hm = np.zeros((m + 1, m), dtype=vs.dtype)
+        k, y = 0, None
+        while k < m:
+            apply(V[k], V[k + 1])
+            numops += 1
+            h, hn = vs.orth_step(V[:k + 1], V[k + 1])
+            Hm[:k + 1, k] = h
+            Hm[k + 1, k] = hn
+            k += 1
+            e1 = np.zeros(k + 1, dtype=vs.dtype)
+            e1[0] = beta
+            y, *_ = np.linalg.lstsq(Hm[:k + 1, :k], e1, rcond=None)
+            res = float(np.linalg.norm(Hm[:k + 1, :k] @ y - e1))
+            if res <= tol or hn <= 1e-14 * max(np.abs(Hm[:k, :k]).max(), 1e-300):
+                break
+        vs.lincomb(V[:k], y, tmp)
+        vs.axpby(1.0, tmp, 1.0, x)
+        if res <= tol:
+            break
+    return x, ConvergenceInfo(int(res <= tol), float(res), numiter, numops, Hm)
+
+
 def arnoldi_eigvals(be: Backend, matvec, x0: DTensor, num=1, tol=1e-10, krylovdim=60, ws: KrylovWorkspace | None = None):
     """The `num` largest-magnitude eigenvalues (complex in general) of a real non-symmetric operator matvec(x, out): one
     Arnoldi factorisation of dimension <= krylovdim, Ritz values of the Hessenberg matrix on the host; a Ritz value counts

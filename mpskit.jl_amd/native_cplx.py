@@ -560,6 +560,18 @@ def find_groundstate(psi: NativeFiniteMPS, H, alg, envs: NativeFinEnv = None):
     return psi, envs, delta
 
 
+def propagator(psi0: NativeFiniteMPS, z, H, alg=None, init: NativeFiniteMPS = None, canonical=True):
+    """propagator(psi0, z, H, DynamicalDMRG(flavour = NaiveInvert()))  (corvector.jl:50-90) on interleaved states: the
+    sweep of mpskit.jl_amd/propagator.py, which runs this flavour on NativeFiniteMPS / NativeFinEnv.  The site operator is
+    asked for in Jordan form (MPSK_HAC_CANONICAL_C128); canonical=False keeps the general complex one.  Returns (value, init)."""
+    from .propagator import DynamicalDMRG, NaiveInvert, propagator as _propagator
+    alg = DynamicalDMRG() if alg is None else alg
+    if not isinstance(alg.flavour, NaiveInvert):
+        raise NotImplementedError("propagator on interleaved complex states: the NaiveInvert flavour only (Jeckelmann with a "
+                                  "complex state is not implemented)")
+    return _propagator(psi0, z, H, alg, init=init, canonical=canonical)
+
+
 def timestep(psi: NativeFiniteMPS, H, t, dt, alg, envs: NativeFinEnv = None):
     """timestep(psi, H, t, dt, TDVP() | TDVP2(...))  (tdvp.jl:61-94, :113-146).  Returns (psi, envs)."""
     from .algorithms import TDVP, TDVP2
