@@ -306,6 +306,9 @@ def test_qrpos2_pair(be, m, n):
 
 @pytest.mark.parametrize("m,n", QR_CASES)
 def test_qrpos(be, qr_mode, m, n):
+    """Routes (qr-auto): n <= 64 ((8, 4) .. (33, 1), incl. 100 x 37) is the Householder kernel; 768 x 256, 1030 x 515 and
+    2048 x 1024 take CholeskyQR3 with the in-step solve and Gram ((npad / 64) ceil(m / 64) <= 768); only 4096 x 1024 (1024 tiles) reaches the GEMM route (recursive-doubling
+    R^-1, Q = X R^-1).  The GEMM route at small and ragged shapes: tests/test_gpu_factor_paths.py (MPSK_CQ_TRSM=0 child)."""
     rng = np.random.default_rng(m * 31 + n)
     A = rng.random((m, n))          # uniform[0,1) like the reference's `rand`
     Q, R = be.qrpos(be.upload(A))
@@ -356,6 +359,9 @@ def test_lqpos(be, m, n):
 @pytest.mark.parametrize("m,n", [(4, 4), (6, 10), (64, 64), (100, 37), (37, 100), (256, 256), (768, 768),
                                  (2048, 1024)])
 def test_tsvd_full(be, m, n):
+    """Routes (svd mode 3): min(m, n) <= 64 is one pair (P = 1) on theta itself; the others iterate on the n x n factor of
+    two QRpos with P = 2 .. 16 pairs, Q = 2 .. 8 Gram splits, always UNCHAINED (chains start at P = 32) and with the default
+    jacobi_eig2_kernel.  Chained schedules, forced Q and the other kernels: tests/test_gpu_factor_paths.py."""
     rng = np.random.default_rng(m * 13 + n)
     A = rng.random((m, n))
     U, S, Vh, kept, disc = be.tsvd(be.upload(A))
