@@ -627,9 +627,16 @@ __global__ __launch_bounds__(64) void ritz_small_kernel(const double* __restrict
             // hardware reciprocal / reciprocal-square-root seeds + Newton steps: the IEEE divide / sqrt expansions are
             // ~40-instruction dependent chains each and five of them sit on the critical path of every round
             const double theta = (aqq - app) * 0.5 * ritz_rcp(apq);
-            const double h2 = theta * theta + 1.0;
-            const double hyp = h2 * ritz_rsq(h2);                                  // sqrt(theta^2 + 1)
-            const double tt = (theta >= 0.0 ? 1.0 : -1.0) * ritz_rcp(fabs(theta) + hyp);
+            double tt;
+            if (fabs(theta) > 1e150) {
+              // theta^2 would overflow (a zero diagonal entry beside a tiny off-diagonal one) and ritz_rsq(inf) is NaN;
+              // t = 1 / (theta + sign(theta) sqrt(theta^2 + 1)) = 1 / (2 theta) to full precision here
+              tt = 0.5 * ritz_rcp(theta);
+            } else {
+              const double h2 = theta * theta + 1.0;
+              const double hyp = h2 * ritz_rsq(h2);                                // sqrt(theta^2 + 1)
+              tt = (theta >= 0.0 ? 1.0 : -1.0) * ritz_rcp(fabs(theta) + hyp);
+            }
             c = ritz_rsq(tt * tt + 1.0); sn = tt * c;
           }
         } else { qq = pp; }                              // bye: identity on (pp, pp), never applied
