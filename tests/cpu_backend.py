@@ -6,6 +6,7 @@ names / argument conventions as Backend, DTensor buffers are CPU torch tensors h
 column-major data, arithmetic is done by NumPy / the oracle.  It is never imported by the
 product package (which has no CPU fallback)."""
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -407,19 +408,52 @@ class CpuComplexBackend(CpuBackend):
 
     # ---- operators
     class _Hac:
-        def __init__(self, be, H, GL, GR):
-            self.be, self.H, self.GL, self.GR = be, H, GL, GR
+        """what PreparedHAC is to the tests: applies the oracle on the operands it was prepared with.  `flags` as in
+        mpsk_hac_create_ex (1: MPSK_HAC_CANONICAL, 2: MPSK_HAC_CANONICAL_C128); info() reports the mode the library would
+        take for a Jordan-form slice (MPSK_HAC_MODE is honoured as mpsk_hac_create_ex reads it)."""
+
+        def __init__(self, be, H, GL, GR, flags=0):
+            self.be, self.H, self.GL, self.GR, self.flags = be, H, GL, GR, int(flags)
+            self.cplx = bool(getattr(H, "cplx", False))
+            ev = os.environ.get("MPSK_HAC_MODE")
+            if self.cplx:
+                self.mode = 3 if flags & 2 else 2
+            elif ev is not None:
+                self.mode = 3 if (ev[:1] == "3" and flags & 1) else 1 if ev[:1] == "1" else 0
+            else:
+                self.mode = 3 if flags & 1 else 1
+
+        def info(self):
+            return {"mode": self.mode, "combined_slabs": 2 * self.H.d ** 2 if self.mode == 3 else 0}
+
+        def _y(self, x):
+            be, H = self.be, self.H
+            if self.cplx:
+                return mo.dAC(be.download_c(x), H.oracle, be._env_c(self.GL, H.chil), be._env_c(self.GR, H.chir))
+            return mo.dAC(be.download(x), H.oracle, be._env(self.GL, H.chil), be._env(self.GR, H.chir))
 
         def apply(self, x, out=None, nblk=1):
-            be, H = self.be, self.H
-            be._count("hac_apply_c")
-            y = mo.dAC(be.download_c(x), H.oracle, be._env_c(self.GL, H.chil), be._env_c(self.GR, H.chir))
-            o = be.empty(self.GL.shape[1], x.shape[1], x.shape[2]) if out is None else out
-            return be._set_c(o, y)
+            self.be._count("hac_apply_c" if self.cplx else "hac_apply")
+            o = self.be.empty(self.GL.shape[1], x.shape[1], x.shape[2]) if out is None else out
+            return (self.be._set_c if self.cplx else self.be._set)(o, self._y(x))
+
+        def apply_axpby(self, a1, x, a0, out=None, nblk=1):
+            """out = a0 x + a1 (H x); a real operator takes the real parts of the scalars"""
+            down = self.be.download_c if self.cplx else self.be.download
+            if not self.cplx:
+                a0, a1 = complex(a0).real, complex(a1).real
+            o = self.be.empty(self.GL.shape[1], x.shape[1], x.shape[2]) if out is None else out
+            return (self.be._set_c if self.cplx else self.be._set)(o, a0 * down(x) + a1 * self._y(x))
+
+        def close(self):
+            pass
 
     def hac_create(self, H, GL, GR):
         assert getattr(H, "cplx", False), "the stand-in only prepares complex operators"
         return CpuComplexBackend._Hac(self, H, GL, GR)
+
+    def hac_create_ex(self, H, GL, GR, canonical=False, canonical_c128=False):
+        return CpuComplexBackend._Hac(self, H, GL, GR, flags=(1 if canonical else 0) | (2 if canonical_c128 else 0))
 
     def dC(self, GL, GR, c, out=None, cplx=False):
         if not cplx:
@@ -436,15 +470,27 @@ class CpuComplexBackend(CpuBackend):
         o = self.empty(GL.shape[1], x2.shape[1], GR.shape[2], x2.shape[3]) if out is None else out
         return self._set_c(o, y)
 
-    def transfer_left(self, H, GLin, A, Ab, out=None, cplx=False):
+    def transfer_left(self, H, GLin, A, Ab, out=None, cplx=False, canonical=False):
+        """canonical=True (real Jordan-form slice, A is Ab): level 0 of the result is written as the identity, as
+        mpsk_transfer_left_ex does, unless MPSK_TRANSFER_MODE=0 keeps the dense route"""
         if not (cplx or getattr(H, "cplx", False)):
-            return super().transfer_left(H, GLin, A, Ab, out)
+            y = super().transfer_left(H, GLin, A, Ab, out)
+            if canonical and H is not None and A is Ab and os.environ.get("MPSK_TRANSFER_MODE", "")[:1] != "0":
+                res = self._env(y, H.chir)
+                res[0] = np.eye(A.shape[2])[:, None, :]
+                self._put_env(res, y)
+            return y
         res = mo.transfer_left(self._env_c(GLin, H.chil), H.oracle, self.download_c(A), self.download_c(Ab))
         return self._put_env_c(res, out)
 
-    def transfer_right(self, H, GRin, A, Ab, out=None, cplx=False):
+    def transfer_right(self, H, GRin, A, Ab, out=None, cplx=False, canonical=False):
         if not (cplx or getattr(H, "cplx", False)):
-            return super().transfer_right(H, GRin, A, Ab, out)
+            y = super().transfer_right(H, GRin, A, Ab, out)
+            if canonical and H is not None and A is Ab and os.environ.get("MPSK_TRANSFER_MODE", "")[:1] != "0":
+                res = self._env(y, H.chil)
+                res[-1] = np.eye(A.shape[0])[:, None, :]
+                self._put_env(res, y)
+            return y
         res = mo.transfer_right(self._env_c(GRin, H.chir), H.oracle, self.download_c(A), self.download_c(Ab))
         return self._put_env_c(res, out)
 

@@ -6,8 +6,8 @@ These are the launches mpsk_gemm cannot reach: the tagged dac_gemm_f64_kernel / 
 stage 3 of mpsk_dAC / mpsk_hac_apply, K-segments over the MPO levels, batch offset tables of the dense route) and the
 complex128 family cgemm_f64_kernel (J-aware loader: segJ = 1 in stage 1, segJ = 2 under TB in transfer_right, the
 transposed K-contiguous loader with segJ = 0 / 1 and row-strided C in transfer_left).  Mode 3 of the prepared operator
-and the canonical transfers need isometries and identity levels, which integer data cannot supply: they keep their own
-tests (test_gpu_hac_canonical.py, test_gpu_transfer_canonical.py)."""
+and the canonical transfers get the same exact treatment in test_gpu_canonical_exact.py (identity levels are integer
+data, dyadic Hadamard blocks are exact isometries: tests/exact_canonical_inputs.py)."""
 import numpy as np
 import pytest
 
