@@ -395,6 +395,33 @@ int mpsk_cx_half(mpsk_ctx* ctx, int m, int n, const void* E, int64_t lde, void* 
 int mpsk_gemm(mpsk_ctx* ctx, int transA, int transB, int M, int N, int K, double alpha, const void* A,
               int64_t lda, const void* B, int64_t ldb, double beta, void* C, int64_t ldc);
 
+/* Paired column-scaled product: the retraction, transport and preconditioner of the Grassmann gradient optimiser
+ * (src/algorithms/grassmann.jl:154-205 retract / transport!, :227-235 the regularised rho^-1), which the reference takes
+ * from TensorKitManifolds' Grassmann.retract / Grassmann.transport! on the SVD Z = U S Vt of the direction at base W:
+ *   out1 = beta1 out1 + (P diag(a1) + Q diag(b1)) B
+ *   out2 = beta2 out2 + (P diag(a2) + Q diag(b2)) B          (out2 == NULL: not computed)
+ * P, Q: M x K (ldp, ldq), B: K x N (ldb), out1 / out2: M x N (ld1, ld2), all column-major and not transposed; leading
+ * dimensions are independent of the row counts.  coef: device matrix of four rows a1, b1, a2, b2 of length K, row r at
+ * coef + r ldcoef (what mpsk_grassmann_coef writes with ldcoef = K).  Q == NULL drops the Q terms (rows b1 / b2 are
+ * not read); without out2 rows a2 / b2 are not read.  beta == 0 never reads the output.  The column scaling and the
+ * P / Q combination happen while the A tile is staged into LDS in front of v_mfma_f64_16x16x4_f64; P and Q are read once
+ * for both outputs.  One launch, no workspace, ascending k inside one workgroup per output tile: results are bit-identical
+ * from run to run.  Outputs must not alias the operands.  mpsk_ctx_force_tile applies.  MPSK_F64 only: a ctx set to
+ * MPSK_C128 gets MPSK_ERR_UNSUPPORTED. */
+int mpsk_gemm_pair(mpsk_ctx* ctx, int M, int N, int K, const void* P, int64_t ldp, const void* Q, int64_t ldq,
+                   const void* B, int64_t ldb, const void* coef, int64_t ldcoef, double beta1, void* out1, int64_t ld1,
+                   double beta2, void* out2, int64_t ld2);
+/* The four coefficient rows of mpsk_gemm_pair from the K singular values S (device) and one host scalar, on the device:
+ * a line-search trial step at a new alpha costs no device-to-host copy.  coef: 4 K doubles, row r at coef + r K; rows a
+ * mode does not use are zeroed.
+ *   MPSK_GRASSMANN_RETRACT      (scalar alpha):  cos(alpha s), sin(alpha s), -s sin(alpha s), s cos(alpha s)
+ *                                                -> out1 = W', out2 = transported direction, with P = W Vt^T, Q = U, B = Vt
+ *   MPSK_GRASSMANN_TRANSPORT    (scalar alpha):  -sin(alpha s), cos(alpha s) - 1      -> B = U^T Theta, beta1 = 1
+ *   MPSK_GRASSMANN_PRECONDITION (scalar delta):  s / (s^2 + (max(s) delta)^2)         grassmann.jl:231
+ * MPSK_F64 only (MPSK_C128: MPSK_ERR_UNSUPPORTED). */
+enum { MPSK_GRASSMANN_RETRACT = 0, MPSK_GRASSMANN_TRANSPORT = 1, MPSK_GRASSMANN_PRECONDITION = 2 };
+int mpsk_grassmann_coef(mpsk_ctx* ctx, int K, const void* S, double scalar, int mode, void* coef);
+
 /* strided column-major matrix copy dst[r, c] = src[r, c] (index permutations of small tensors, e.g.
  * AR[k, s, b] <- Vh[k, b, s] after tsvd!: dmrg.jl:104 `_transpose_front(ar)`) */
 int mpsk_copy2d(mpsk_ctx* ctx, int rows, int cols, const void* src, int64_t lds, void* dst, int64_t ldd);

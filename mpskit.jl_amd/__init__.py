@@ -10,8 +10,9 @@ from .operators import (MPOHamiltonian, SparseMPO, LazySum, heisenberg_XXX, tran
 from .states import FiniteMPS, InfiniteMPS  # noqa: F401,E402
 from .environments import FinEnv, FinEnvPair, MPOHamInfEnv, MultipleEnvironments, environments  # noqa: F401,E402
 from .derivatives import ddAC, ddAC2, ddC, MPO_ddAC, MPO_ddAC2, MPO_ddC  # noqa: F401,E402
-from .algorithms import (DMRG, DMRG2, VUMPS, IDMRG1, IDMRG2, TDVP, TDVP2, Arnoldi, find_groundstate, calc_galerkin,  # noqa: F401,E402
-                         expectation_value, timestep, time_evolve)
+from .algorithms import (DMRG, DMRG2, VUMPS, IDMRG1, IDMRG2, GradientGrassmann, UnionAlg, TDVP, TDVP2, Arnoldi,  # noqa: F401,E402
+                         find_groundstate, calc_galerkin, expectation_value, timestep, time_evolve)
+from . import grassmann  # noqa: F401,E402
 from .changebonds import changebonds, OptimalExpand, RandExpand, SvdCut  # noqa: F401,E402
 from .approximate import approximate, make_time_mpo, WI, WII, TaylorCluster  # noqa: F401,E402
 from .excitations import excitations, FiniteExcited, ProjectionOperator  # noqa: F401,E402

@@ -130,6 +130,10 @@ SIGNATURES = {
     "mpsk_vaxpby_c": [C.c_void_p, C.c_int64, c_double_p, C.c_void_p, c_double_p, C.c_void_p],
     "mpsk_vorth_step_c": [C.c_void_p, C.c_int64, C.c_int, c_void_pp, C.c_void_p, c_double_p, c_double_p],
     "mpsk_vlincomb_c": [C.c_void_p, C.c_int64, C.c_int, c_void_pp, c_double_p, C.c_void_p],
+    "mpsk_gemm_pair": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                       C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
+                       C.c_int64],
+    "mpsk_grassmann_coef": [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p],
 }
 # symbols without the (ctx, ...) -> int shape
 EXTRA_SYMBOLS = ["mpsk_version", "mpsk_last_error"]

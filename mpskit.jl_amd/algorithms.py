@@ -18,6 +18,23 @@ from .states import FiniteMPS, InfiniteMPS, leftorth, mul_AC
 from . import krylov
 
 
+class _Algorithm:
+    """alg1 & alg2 -> UnionAlg(alg1, alg2)   (src/algorithms/unionalg.jl:9)."""
+
+    def __and__(self, other):
+        if not isinstance(other, _Algorithm):
+            return NotImplemented
+        return UnionAlg(self, other)
+
+
+class UnionAlg(_Algorithm):  # unionalg.jl:4-7
+    def __init__(self, alg1, alg2):
+        self.alg1, self.alg2 = alg1, alg2
+
+    def __repr__(self):
+        return f"UnionAlg({self.alg1!r}, {self.alg2!r})"
+
+
 @dataclass
 class Arnoldi:  # Defaults.eigsolver  (defaults.jl:33)
     tol: float = 1e-12
@@ -28,7 +45,7 @@ class Arnoldi:  # Defaults.eigsolver  (defaults.jl:33)
 
 
 @dataclass
-class DMRG:  # dmrg.jl:14-20
+class DMRG(_Algorithm):  # dmrg.jl:14-20
     tol: float = 1e-12
     maxiter: int = 100
     eigalg: Arnoldi = field(default_factory=Arnoldi)
@@ -37,7 +54,7 @@ class DMRG:  # dmrg.jl:14-20
 
 
 @dataclass
-class DMRG2:  # dmrg.jl:71-78
+class DMRG2(_Algorithm):  # dmrg.jl:71-78
     tol: float = 1e-12
     maxiter: int = 100
     eigalg: Arnoldi = field(default_factory=Arnoldi)
@@ -48,7 +65,7 @@ class DMRG2:  # dmrg.jl:71-78
 
 
 @dataclass
-class VUMPS:  # vumps.jl:18-27 with the dynamic tolerances of defaults.jl:38-57
+class VUMPS(_Algorithm):  # vumps.jl:18-27 with the dynamic tolerances of defaults.jl:38-57
     tol: float = 1e-12
     maxiter: int = 100
     verbosity: int = 0
@@ -63,6 +80,15 @@ class VUMPS:  # vumps.jl:18-27 with the dynamic tolerances of defaults.jl:38-57
     env_tol_max: float = 1e-5
     env_tol_factor: float = 1e-5
     finalize: object = None
+
+
+@dataclass
+class GradientGrassmann(_Algorithm):  # gradient_grassmann.jl:26-44 ; method = ConjugateGradient (grassmann.py)
+    tol: float = 1e-12            # Defaults.tol, the optimiser's gradtol
+    maxiter: int = 100            # Defaults.maxiter
+    verbosity: int = 0
+    finalize: object = None       # finalize(x, f, g, numiter) -> x, f, g   (gradient_grassmann.jl:10-11)
+    route: str | None = None      # None: by size (grassmann.DEVICE_ROUTE_MIN); "device" / "composed" force one
 
 
 def updatetol(tol_min, tol_max, factor, it, eps):  # dynamictols.jl:50-53
@@ -178,10 +204,54 @@ def _no_cplx(psi, what):
                                   "only up to a rotation inside each doubled singular value (cplx.py)")
 
 
-def find_groundstate(psi, H, alg=None, envs=None):
-    """find_groundstate(psi, H, alg[, envs]) -> (psi, envs, eps)  (find_groundstate.jl:19-41)."""
+def _trscheme(trscheme):
+    """dict(trunc_dim=64) / dict(trunc_err=1e-6): truncdim / truncerr of the reference."""
+    if not isinstance(trscheme, dict) or not trscheme or set(trscheme) - {"trunc_dim", "trunc_err"}:
+        raise TypeError(f"trscheme must be dict(trunc_dim=...) and / or dict(trunc_err=...), not {trscheme!r}")
+    return dict(trscheme)
+
+
+def _default_algorithm(psi, tol, maxiter, verbosity, trscheme):
+    """the composite of find_groundstate.jl:22-39 (Defaults.tol = 1e-12, Defaults.maxiter = 100; verbosity keeps this
+    package's silent default)."""
+    tol = 1e-12 if tol is None else tol
+    maxiter = 100 if maxiter is None else maxiter
+    verbosity = 0 if verbosity is None else verbosity
+    if isinstance(psi, InfiniteMPS):
+        alg = VUMPS(tol=max(1e-4, tol), verbosity=verbosity, maxiter=maxiter)
+        if tol < 1e-4:
+            alg = alg & GradientGrassmann(tol=tol, maxiter=maxiter, verbosity=verbosity)
+        if trscheme is not None:
+            alg = IDMRG2(tol=min(1e-2, 100 * tol), verbosity=verbosity, **_trscheme(trscheme)) & alg
+    elif isinstance(psi, FiniteMPS):
+        alg = DMRG(tol=tol, maxiter=maxiter, verbosity=verbosity)
+        if trscheme is not None:
+            alg = DMRG2(tol=min(1e-2, 100 * tol), verbosity=verbosity, **_trscheme(trscheme)) & alg
+    else:
+        raise TypeError("Unknown input state type")
+    return alg
+
+
+def find_groundstate(psi, H, alg=None, envs=None, *, tol=None, maxiter=None, verbosity=None, trscheme=None):
+    """find_groundstate(psi, H, alg[, envs]) -> (psi, envs, eps)  (find_groundstate.jl:19-41).  Without alg and without
+    keywords: DMRG() / VUMPS().  Without alg and with any keyword: the reference's composite (_default_algorithm).
+    A UnionAlg leaves the stages it ran in envs.stages = [(name, history), ...]."""
     if alg is None:
-        alg = DMRG() if isinstance(psi, FiniteMPS) else VUMPS()
+        if tol is None and maxiter is None and verbosity is None and trscheme is None:
+            alg = DMRG() if isinstance(psi, FiniteMPS) else VUMPS()
+        else:
+            alg = _default_algorithm(psi, tol, maxiter, verbosity, trscheme)
+    elif not (tol is None and maxiter is None and verbosity is None and trscheme is None):
+        raise TypeError("find_groundstate: pass either an algorithm or the keywords tol / maxiter / verbosity / trscheme")
+    if envs is not None and getattr(envs, "stages", None) is not None:
+        envs.stages = None                 # the record of an earlier composite run on the same environments is not this run's
+    if isinstance(alg, UnionAlg):  # unionalg.jl:23-26
+        psi, envs, _ = find_groundstate(psi, H, alg.alg1, envs)
+        stages = list(getattr(envs, "stages", None) or [(type(alg.alg1).__name__, list(getattr(envs, "history", [])))])
+        psi, envs, eps = find_groundstate(psi, H, alg.alg2, envs)
+        stages += list(getattr(envs, "stages", None) or [(type(alg.alg2).__name__, list(getattr(envs, "history", [])))])
+        envs.stages = stages
+        return psi, envs, eps
     if isinstance(alg, DMRG):
         return _dmrg(psi.copy(), H, alg, envs)
     if isinstance(alg, DMRG2):
@@ -192,6 +262,9 @@ def find_groundstate(psi, H, alg=None, envs=None):
         return _idmrg1(psi, H, alg, envs)
     if isinstance(alg, IDMRG2):
         return _idmrg2(psi, H, alg, envs)
+    if isinstance(alg, GradientGrassmann):
+        from .grassmann import find_groundstate_grassmann
+        return find_groundstate_grassmann(psi, H, alg, envs)
     raise TypeError(f"unknown algorithm {alg!r}")
 
 
@@ -572,7 +645,7 @@ def time_evolve(psi, H, t_span, alg=None, envs=None):
 # ---- IDMRG1 (src/algorithms/groundstate/idmrg.jl:21-77, src/environments/idmrgenv.jl) ---------------------
 
 @dataclass
-class IDMRG1:  # idmrg.jl:13-19
+class IDMRG1(_Algorithm):  # idmrg.jl:13-19
     tol: float = 1e-12
     tol_gauge: float = 1e-14
     maxiter: int = 100
@@ -650,7 +723,7 @@ def _idmrg1(ost, H, alg: IDMRG1, oenvs=None):  # idmrg.jl:21-77
 # ---- IDMRG2 (idmrg.jl:79-204) -----------------------------------------------------------------------------
 
 @dataclass
-class IDMRG2:  # idmrg.jl:89-96 ; trscheme = truncerr(1e-6)
+class IDMRG2(_Algorithm):  # idmrg.jl:89-96 ; trscheme = truncerr(1e-6)
     tol: float = 1e-12
     tol_gauge: float = 1e-14
     maxiter: int = 100

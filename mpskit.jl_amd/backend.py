@@ -455,6 +455,36 @@ class Backend:
         check(self.lib.mpsk_gemm(self.ctx, int(transA), int(transB), M, N, K, float(alpha), a_ptr, lda, b_ptr,
                                  ldb, float(beta), c_ptr, ldc), "mpsk_gemm")
 
+    def gemm_pair(self, P: DTensor, Q, B: DTensor, coef: DTensor, out1: DTensor = None, out2: DTensor = None, beta1=0.0,
+                  beta2=0.0, two=True):
+        """mpsk_gemm_pair: out1 = beta1 out1 + (P diag(a1) + Q diag(b1)) B and, with two=True, out2 likewise from rows
+        a2 / b2 of coef (grassmann_coef: (K, 4) column-major, column r = row r of the ABI).  P, Q: (M, K), B: (K, N); Q may be None.  Returns (out1, out2 | None)."""
+        M, K = P.shape
+        K2, N = B.shape
+        assert K2 == K and coef.shape == (K, 4) and (Q is None or Q.shape == (M, K)), (P.shape, B.shape, coef.shape)
+        o1 = self.empty(M, N) if out1 is None else out1
+        o2 = (self.empty(M, N) if out2 is None else out2) if two else None
+        check(self.lib.mpsk_gemm_pair(self.ctx, M, N, K, P.ptr, M, None if Q is None else Q.ptr, M, B.ptr, K, coef.ptr, K,
+                                      float(beta1), o1.ptr, M, float(beta2), None if o2 is None else o2.ptr, M),
+              "mpsk_gemm_pair")
+        return o1, o2
+
+    def gemm_pair_raw(self, M, N, K, p_ptr, ldp, q_ptr, ldq, b_ptr, ldb, coef_ptr, ldcoef, beta1, o1_ptr, ld1, beta2, o2_ptr,
+                      ld2):
+        check(self.lib.mpsk_gemm_pair(self.ctx, M, N, K, p_ptr, ldp, q_ptr, ldq, b_ptr, ldb, coef_ptr, ldcoef, float(beta1),
+                                      o1_ptr, ld1, float(beta2), o2_ptr, ld2), "mpsk_gemm_pair")
+
+    GRASSMANN_MODES = {"retract": 0, "transport": 1, "precondition": 2}
+
+    def grassmann_coef(self, S: DTensor, scalar, mode, out: DTensor = None):
+        """mpsk_grassmann_coef: the coefficient rows a1, b1, a2, b2 of gemm_pair (the columns of a (K, 4) tensor) from the
+        device vector S and one host scalar (alpha, or delta for "precondition"); no device-to-host copy."""
+        K = S.size
+        coef = self.empty(K, 4) if out is None else out
+        check(self.lib.mpsk_grassmann_coef(self.ctx, K, S.ptr, float(scalar), self.GRASSMANN_MODES[mode], coef.ptr),
+              "mpsk_grassmann_coef")
+        return coef
+
     def triu_(self, M: DTensor):
         """zero the strictly lower triangle of a column-major matrix in place (torch view of the buffer: a fill, no arithmetic)."""
         torch = _torch()

@@ -2940,6 +2940,41 @@ int mpsk_gemm(mpsk_ctx* c, int transA, int transB, int M, int N, int K, double a
   return MPSK_OK;
 }
 
+// fp64 only; no workspace (the kernel keeps both outputs' accumulators in registers and writes C directly)
+int mpsk_gemm_pair(mpsk_ctx* c, int M, int N, int K, const void* P, int64_t ldp, const void* Q, int64_t ldq, const void* B,
+                   int64_t ldb, const void* coef, int64_t ldcoef, double beta1, void* out1, int64_t ld1, double beta2,
+                   void* out2, int64_t ld2) {
+  REQUIRE(c && P && B && coef && out1, "NULL argument");
+  if (c->dtype == MPSK_C128) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_gemm_pair: fp64 only");
+  REQUIRE(M > 0 && N > 0 && K > 0, "dimensions must be positive");
+  REQUIRE(ldp >= M && ldb >= K && ld1 >= M && ldcoef >= K, "leading dimension below the row count");
+  REQUIRE(!Q || ldq >= M, "ldq below the row count");
+  REQUIRE(!out2 || ld2 >= M, "ld2 below the row count");
+  REQUIRE(out1 != out2 && out1 != P && out1 != Q && out1 != B && (!out2 || (out2 != P && out2 != Q && out2 != B)),
+          "outputs must not alias the operands or each other");
+  HIPCHK(hipSetDevice(c->device));
+  const double* cf = (const double*)coef;
+  GemmPairArgs g{};
+  g.P = (const double*)P; g.Q = (const double*)Q; g.B = (const double*)B;
+  g.C1 = (double*)out1; g.C2 = (double*)out2;
+  g.M = M; g.N = N; g.K = K;
+  g.ldp = ldp; g.ldq = Q ? ldq : 0; g.ldb = ldb; g.ld1 = ld1; g.ld2 = out2 ? ld2 : 0;
+  g.a1 = cf; g.b1 = cf + ldcoef; g.a2 = cf + 2 * ldcoef; g.b2 = cf + 3 * ldcoef;
+  g.beta1 = beta1; g.beta2 = beta2;
+  HIPCHK(gemm_pair_f64(g, c->stream));
+  return MPSK_OK;
+}
+
+int mpsk_grassmann_coef(mpsk_ctx* c, int K, const void* S, double scalar, int mode, void* coef) {
+  REQUIRE(c && S && coef, "NULL argument");
+  if (c->dtype == MPSK_C128) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_grassmann_coef: fp64 only");
+  REQUIRE(K > 0, "K must be positive");
+  REQUIRE(mode >= MPSK_GRASSMANN_RETRACT && mode <= MPSK_GRASSMANN_PRECONDITION, "mode must be 0 (retract), 1 (transport) or 2 (precondition)");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(grassmann_coef(K, (const double*)S, scalar, mode, (double*)coef, c->stream));
+  return MPSK_OK;
+}
+
 int mpsk_copy2d(mpsk_ctx* c, int rows, int cols, const void* src, int64_t lds, void* dst, int64_t ldd) {
   REQUIRE(c && src && dst, "NULL argument");
   REQUIRE(rows > 0 && cols > 0 && lds >= rows && ldd >= rows, "bad dimensions");

@@ -994,4 +994,232 @@ hipError_t gemm_f64(const GemmArgs& g_in, hipStream_t s) {
 #undef MPSK_DISPATCH
 }
 
+// ---- paired column-scaled product (mpsk_gemm_pair) ----------------------------------------------
+//   C1 = beta1 C1 + (P diag(a1) + Q diag(b1)) B,   C2 = beta2 C2 + (P diag(a2) + Q diag(b2)) B
+// The retraction, transport and preconditioner of the Grassmann optimiser (grassmann.py) all have this shape.  Same
+// tiles, LDS images, MFMA operand order and epilogue as gemm_body; the A side differs: the tiles of P and Q are read
+// ONCE into registers and combined column by column on their way into LDS, into one A image per output, and both
+// outputs share the B fragments.  P / B not transposed: the A images are MN-major, the B image K-major.  One workgroup
+// per output tile, k ascending, no split: bit-identical from run to run.
+template <int BM, bool ALIGNED, bool TWO> struct PairLoader {
+  using L = TileLoader<BM, false, ALIGNED>;
+  using Img = typename L::Img;
+  static constexpr int NV = L::NV;
+  L p, q;
+  double c[NV][4];     // a1, b1, a2, b2 at the k of vector i
+
+  __device__ inline void load(const GemmPairArgs& g, int m0, int k0, int tid) {
+    p.load(g.P, g.ldp, m0, k0, g.M, g.K, tid);
+    if (g.Q) q.load(g.Q, g.ldq, m0, k0, g.M, g.K, tid);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int gk = k0 + (tid + i * NTHREADS) / (BM / 2);
+      const bool in = ALIGNED || gk < g.K;
+      if (!g.Q) q.r[i] = d2{0.0, 0.0};
+      c[i][0] = in ? g.a1[gk] : 0.0;
+      c[i][1] = (in && g.Q) ? g.b1[gk] : 0.0;
+      c[i][2] = (TWO && in) ? g.a2[gk] : 0.0;
+      c[i][3] = (TWO && in && g.Q) ? g.b2[gk] : 0.0;
+    }
+  }
+  // image 0 (and image 1 at lds + Img::SIZE when TWO)
+  __device__ inline void store(double* __restrict__ lds, int tid) const {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = tid + i * NTHREADS;
+      const int mn = (v % (BM / 2)) * 2, k = v / (BM / 2);
+      const d2 pv = p.r[i], qv = q.r[i];
+      *reinterpret_cast<d2*>(&lds[Img::idx(mn, k)]) = d2{pv.x * c[i][0] + qv.x * c[i][1], pv.y * c[i][0] + qv.y * c[i][1]};
+      if (TWO)
+        *reinterpret_cast<d2*>(&lds[Img::SIZE + Img::idx(mn, k)]) =
+            d2{pv.x * c[i][2] + qv.x * c[i][3], pv.y * c[i][2] + qv.y * c[i][3]};
+    }
+  }
+};
+
+// waves per SIMD the register allocation leaves room for.  Two accumulator sets: 64x64 fits 2 (168 VGPRs); the wider tiles
+// need the AGPR half of the file (their four A images allow one or two workgroups per CU anyway).  128x128 with two
+// outputs does not fit at all (143+ spilled VGPRs when tried) and is not built: gemm_pair_f64 runs it as 128x64.
+constexpr int pair_min_waves(int bm, int bn, bool two) { return (bm * bn == 64 * 64) ? 2 : ((two || bm * bn == 128 * 128) ? 1 : 2); }
+
+template <int BM, int BN, bool ALIGNED, bool TWO>
+__global__ __launch_bounds__(NTHREADS, pair_min_waves(BM, BN, TWO)) void gemm_pair_f64_kernel(GemmPairArgs g) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  constexpr int WTM = BM / 2, WTN = BN / 2, TM = WTM / 16, TN = WTN / 16;
+  constexpr int NA = TWO ? 2 : 1;
+  using LA = PairLoader<BM, ALIGNED, TWO>;
+  using LB = TileLoader<BN, true, ALIGNED>;
+  using IA = typename LA::Img;
+  using IB = typename LB::Img;
+  double* const sA = smem;                       // two buffers of NA images each, then two B images
+  double* const sB = smem + 2 * NA * IA::SIZE;
+  const int tilesM = (g.M + BM - 1) / BM;
+  const int bn = blockIdx.x / tilesM, bm = blockIdx.x - bn * tilesM;
+  const int m0 = bm * BM, n0 = bn * BN;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int fr = lane & 15, fq = lane >> 4;
+  d4 acc1[TM][TN], acc2[TWO ? TM : 1][TWO ? TN : 1];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      acc1[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+      if (TWO) acc2[TWO ? i : 0][TWO ? j : 0] = d4{0.0, 0.0, 0.0, 0.0};
+    }
+  const int nt = (g.K + BK - 1) / BK;
+  LA la; LB lb;
+  la.load(g, m0, 0, tid);
+  lb.load(g.B, g.ldb, n0, 0, g.N, g.K, tid);
+  la.store(sA, tid);
+  lb.store(sB, tid);
+  __syncthreads();
+  for (int t = 0; t < nt; ++t) {
+    const int cur = t & 1;
+    if (t + 1 < nt) {
+      la.load(g, m0, (t + 1) * BK, tid);
+      lb.load(g.B, g.ldb, n0, (t + 1) * BK, g.N, g.K, tid);
+    }
+    const double* a_s = sA + cur * NA * IA::SIZE;
+    const double* b_s = sB + cur * IB::SIZE;
+#pragma unroll
+    for (int ks = 0; ks < BK; ks += 4) {
+      double af1[TM], af2[TM], bf[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        af1[i] = a_s[IA::idx(wm * WTM + i * 16 + fr, ks + fq)];
+        af2[i] = TWO ? a_s[IA::SIZE + IA::idx(wm * WTM + i * 16 + fr, ks + fq)] : 0.0;
+      }
+#pragma unroll
+      for (int j = 0; j < TN; ++j) bf[j] = b_s[IB::idx(wn * WTN + j * 16 + fr, ks + fq)];
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          acc1[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[j], af1[i], acc1[i][j], 0, 0, 0);
+          if (TWO)
+            acc2[TWO ? i : 0][TWO ? j : 0] =
+                __builtin_amdgcn_mfma_f64_16x16x4f64(bf[j], af2[i], acc2[TWO ? i : 0][TWO ? j : 0], 0, 0, 0);
+        }
+    }
+    if (t + 1 < nt) {
+      la.store(sA + (cur ^ 1) * NA * IA::SIZE, tid);
+      lb.store(sB + (cur ^ 1) * IB::SIZE, tid);
+    }
+    __syncthreads();
+  }
+  // epilogue: lane holds C[m = .. + fr][n = .. + fq + 4*reg]
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int m = m0 + wm * WTM + i * 16 + fr;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const int n = n0 + wn * WTN + j * 16 + fq + 4 * rg;
+        if (m < g.M && n < g.N) {
+          double* p1 = g.C1 + m + (int64_t)n * g.ld1;
+          double v1 = acc1[i][j][rg];
+          if (g.beta1 != 0.0) v1 += g.beta1 * (*p1);
+          *p1 = v1;
+          if (TWO) {
+            double* p2 = g.C2 + m + (int64_t)n * g.ld2;
+            double v2 = acc2[TWO ? i : 0][TWO ? j : 0][rg];
+            if (g.beta2 != 0.0) v2 += g.beta2 * (*p2);
+            *p2 = v2;
+          }
+        }
+      }
+    }
+  }
+}
+
+template <int BM, int BN, bool ALIGNED, bool TWO>
+static hipError_t launch_pair(const GemmPairArgs& g, hipStream_t s) {
+  using IA = LdsImg<BM, false>;
+  using IB = LdsImg<BN, true>;
+  constexpr size_t smem = (2 * (TWO ? 2 : 1) * IA::SIZE + 2 * IB::SIZE) * sizeof(double);
+  static std::atomic<uint64_t> done{0};
+  const auto kern = gemm_pair_f64_kernel<BM, BN, ALIGNED, TWO>;
+  if (hipError_t e = ensure_dyn_smem(done, reinterpret_cast<const void*>(kern), smem); e != hipSuccess) return e;
+  const int tilesM = (g.M + BM - 1) / BM, tilesN = (g.N + BN - 1) / BN;
+  hipLaunchKernelGGL(kern, dim3(tilesM * tilesN), dim3(NTHREADS), smem, s, g);
+  return hipGetLastError();
+}
+
+template <bool ALIGNED, bool TWO>
+static hipError_t launch_pair_tile(const GemmPairArgs& g, int bm, int bn, hipStream_t s) {
+  if constexpr (!TWO) {
+    if (bm == 128 && bn == 128) return launch_pair<128, 128, ALIGNED, TWO>(g, s);
+  }
+  if (bm == 64 && bn == 128) return launch_pair<64, 128, ALIGNED, TWO>(g, s);
+  if (bm == 128 && bn == 64) return launch_pair<128, 64, ALIGNED, TWO>(g, s);
+  return launch_pair<64, 64, ALIGNED, TWO>(g, s);
+}
+
+hipError_t gemm_pair_f64(const GemmPairArgs& g, hipStream_t s) {
+  if (g.M <= 0 || g.N <= 0) return hipSuccess;
+  if (g.K <= 0 || !g.P || !g.B || !g.C1 || !g.a1 || (g.Q && !g.b1) || (g.C2 && (!g.a2 || (g.Q && !g.b2))))
+    return hipErrorInvalidValue;
+  // the tall operands of the optimiser (M = D d, N = K = D) give (D / 64)^2 d tiles of 64x64: the tile of the plain
+  // core's short-to-medium products; 128 rows once that list is several waves of workgroups long
+  int bm = 64, bn = 64;
+  if ((int64_t)((g.M + 63) / 64) * ((g.N + 63) / 64) > 4096) bm = 128;
+  if (g_force_bm.load()) { bm = g_force_bm.load(); bn = g_force_bn.load(); }
+  if (g.C2 && bm == 128 && bn == 128) bn = 64;      // (see pair_min_waves)
+  const bool aligned = (g.M % bm == 0) && (g.N % bn == 0) && (g.K % BK == 0) && (g.ldp % 2 == 0) && (g.ldb % 2 == 0) &&
+                       (!g.Q || (g.ldq % 2 == 0 && (uintptr_t)g.Q % 16 == 0)) && ((uintptr_t)g.P % 16 == 0) &&
+                       ((uintptr_t)g.B % 16 == 0) && g.ldp < ((int64_t)1 << 21) && g.ldq < ((int64_t)1 << 21) &&
+                       g.ldb < ((int64_t)1 << 21);
+  if (g.C2) return aligned ? launch_pair_tile<true, true>(g, bm, bn, s) : launch_pair_tile<false, true>(g, bm, bn, s);
+  return aligned ? launch_pair_tile<true, false>(g, bm, bn, s) : launch_pair_tile<false, false>(g, bm, bn, s);
+}
+
+// Coefficient rows of mpsk_gemm_pair for the Grassmann geometry, filled from the singular values on the device (a trial
+// step at a new alpha costs this launch, not a copy): coef[r * K + k], r = a1, b1, a2, b2; rows a mode does not use are
+// zeroed.  One workgroup: K is a bond dimension.
+//   0 retract      cos(alpha s), sin(alpha s), -s sin(alpha s), s cos(alpha s)
+//   1 transport    -sin(alpha s), cos(alpha s) - 1
+//   2 precondition s / (s^2 + (max(s) delta)^2)
+__global__ __launch_bounds__(256) void grassmann_coef_kernel(int K, const double* __restrict__ S, double scalar, int mode,
+                                                             double* __restrict__ coef) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  double smax = 0.0;
+  if (mode == 2) {
+    double m = 0.0;
+    for (int k = tid; k < K; k += 256) m = fmax(m, S[k]);
+    red[tid] = m;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (tid < w) red[tid] = fmax(red[tid], red[tid + w]);
+      __syncthreads();
+    }
+    smax = red[0];
+  }
+  for (int k = tid; k < K; k += 256) {
+    const double s = S[k];
+    double a1 = 0.0, b1 = 0.0, a2 = 0.0, b2 = 0.0;
+    if (mode == 2) {
+      const double t = smax * scalar;
+      a1 = s / (s * s + t * t);
+    } else {
+      const double sn = sin(scalar * s), cs = cos(scalar * s);
+      if (mode == 0) { a1 = cs; b1 = sn; a2 = -s * sn; b2 = s * cs; }
+      else { a1 = -sn; b1 = cs - 1.0; }
+    }
+    coef[k] = a1;
+    coef[(int64_t)K + k] = b1;
+    coef[2 * (int64_t)K + k] = a2;
+    coef[3 * (int64_t)K + k] = b2;
+  }
+}
+
+hipError_t grassmann_coef(int K, const double* S, double scalar, int mode, double* coef, hipStream_t s) {
+  if (K <= 0 || !S || !coef || mode < 0 || mode > 2) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grassmann_coef_kernel, dim3(1), dim3(256), 0, s, K, S, scalar, mode, coef);
+  return hipGetLastError();
+}
+
 }  // namespace mpsk

@@ -90,6 +90,30 @@ void gemm_enable_streamk(bool on);
 void gemm_prof_enable(bool on);
 std::string gemm_prof_summary();
 
+// ---- paired column-scaled product (mpsk_gemm_pair; mpsk_gemm.hip) ------------------------------
+//   C1 = beta1 C1 + (P diag(a1) + Q diag(b1)) B,   C2 = beta2 C2 + (P diag(a2) + Q diag(b2)) B
+// P, Q: M x K, B: K x N, column-major, not transposed; a* / b*: device vectors of length K.  Q == nullptr drops the Q
+// terms (b* are not read), C2 == nullptr the second output (a2 / b2 are not read).  One launch, no workspace, one
+// workgroup per output tile walking k in ascending order: the summation order is fixed.
+struct GemmPairArgs {
+  const double* P;
+  const double* Q;
+  const double* B;
+  double* C1;
+  double* C2;
+  int M, N, K;
+  int64_t ldp, ldq, ldb, ld1, ld2;
+  const double* a1;
+  const double* b1;
+  const double* a2;
+  const double* b2;
+  double beta1, beta2;
+};
+hipError_t gemm_pair_f64(const GemmPairArgs& g, hipStream_t s);
+// coefficient rows of the Grassmann retraction / transport / preconditioner (mpsk_grassmann_coef): coef[r * K + k],
+// r = a1, b1, a2, b2; mode 0 retract, 1 transport, 2 precondition
+hipError_t grassmann_coef(int K, const double* S, double scalar, int mode, double* coef, hipStream_t s);
+
 // ---- slab mixing:  out_slab[o][r,c] = sum_t coef[t] * in_slab[src[t]][r,c]  --------------------
 // A "slab" is an R x C column-major matrix view (ld, base offset) inside a larger tensor.  This
 // is the (w,s) -> (v,t) application of the small MPO tensor between the two big GEMMs.
