@@ -243,6 +243,13 @@ int mpsk_dAC2(mpsk_ctx* ctx, const mpsk_mposlice* H1, const mpsk_mposlice* H2, i
  *   Dlo d Dr (Wl + Wr) doubles (twice that, plus the planes of x and GR, for complex).  Dro == Dr is mpsk_dAC bit for bit. */
 int mpsk_dAC_proj(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR,
                   const void* x, void* y);
+/* mpsk_dC_proj == c_proj (derivatives.jl:204-207), the zero-site map on the same rectangular environments:
+ *   y[p,q] = sum_w GL[w][p,a] c[a,b] GR[w][b,q],  GL: W slabs [Dlo, Dl], GR: W slabs [Dr, Dro], c: [Dl, Dr], y: [Dlo, Dro].
+ *   The order of contraction is fixed, left first: one batched fp64 MFMA GEMM T[w] = GL[w] c, then the segmented-K GEMM over
+ *   (w, b) as mpsk_dC runs it: 2 W (Dlo Dl Dr + Dlo Dr Dro) flops; workspace W Dlo Dr doubles.  MPSK_F64 only: a ctx set to
+ *   MPSK_C128 (mpsk_ctx_set_dtype) gets MPSK_ERR_UNSUPPORTED.  Dro == Dr is mpsk_dC bit for bit (same launches, same tiles). */
+int mpsk_dC_proj(mpsk_ctx* ctx, int W, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR, const void* c,
+                 void* y);
 /* mpsk_dAC2_proj == ac2_proj applied to the two factors of the state above, AC [Dl, d1, Dm] and AR [Dm, d2, Dr] (as
  * mpsk_dAC2_product takes them); Y: [Dlo, d1, Dro, d2] (the layout of mpsk_dAC2's result).
  *   MPSK_F64: factorised through the middle bond, Y = sum_u Lhalf[u] Rhalf[u] with Lhalf[u] [Dlo, d1, Dm] and Rhalf[u]

@@ -10,15 +10,15 @@ from .operators import (MPOHamiltonian, SparseMPO, LazySum, heisenberg_XXX, tran
 from .states import FiniteMPS, InfiniteMPS  # noqa: F401,E402
 from .environments import FinEnv, FinEnvPair, MPOHamInfEnv, MultipleEnvironments, environments  # noqa: F401,E402
 from .derivatives import ddAC, ddAC2, ddC, MPO_ddAC, MPO_ddAC2, MPO_ddC  # noqa: F401,E402
-from .algorithms import (DMRG, DMRG2, VUMPS, IDMRG1, IDMRG2, GradientGrassmann, UnionAlg, TDVP, TDVP2, Arnoldi,  # noqa: F401,E402
+from .algorithms import (DMRG, DMRG2, VUMPS, VOMPS, IDMRG1, IDMRG2, GradientGrassmann, UnionAlg, TDVP, TDVP2, Arnoldi,  # noqa: F401,E402
                          find_groundstate, calc_galerkin, expectation_value, timestep, time_evolve)
 from . import grassmann  # noqa: F401,E402
 from .changebonds import changebonds, OptimalExpand, RandExpand, SvdCut  # noqa: F401,E402
-from .approximate import approximate, make_time_mpo, WI, WII, TaylorCluster  # noqa: F401,E402
+from .approximate import approximate, ac_proj, c_proj, make_time_mpo, WI, WII, TaylorCluster  # noqa: F401,E402
 from .excitations import excitations, FiniteExcited, ProjectionOperator  # noqa: F401,E402
 from .quasiparticle import QuasiparticleAnsatz, LeftGaugedQP  # noqa: F401,E402
 from .toolbox import (variance, entropy, entanglement_spectrum, transfer_spectrum, marek_gap, correlation_length,  # noqa: F401,E402
                       exact_diagonalization)
-from .statmech import DenseMPO, PerMPOInfEnv, leading_boundary, classical_ising, sixvertex  # noqa: F401,E402
+from .statmech import DenseMPO, PerMPOInfEnv, leading_boundary, classical_ising, sixvertex, dot  # noqa: F401,E402
 from . import native_cplx  # noqa: F401,E402   (complex128 states on interleaved storage: NativeFiniteMPS, dmrg, tdvp_step)
 from .propagator import propagator, DynamicalDMRG, NaiveInvert, Jeckelmann, GMRES, LinearCombination  # noqa: F401,E402

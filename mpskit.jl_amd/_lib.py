@@ -122,6 +122,8 @@ SIGNATURES = {
     "mpsk_ctx_complement_stats": [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)],
     "mpsk_dAC_proj": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                       C.c_void_p],
+    "mpsk_dC_proj": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                     C.c_void_p],
     "mpsk_dAC2_proj": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mpsk_vdiff_nrm2": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, c_double_p],

@@ -83,6 +83,22 @@ class VUMPS(_Algorithm):  # vumps.jl:18-27 with the dynamic tolerances of defaul
 
 
 @dataclass
+class VOMPS(_Algorithm):  # statmech/vomps.jl:17-25 with the dynamic gauge / environment tolerances VUMPS carries
+    """Power method for uniform states: approximate(psi::InfiniteMPS, (O, above), VOMPS()) and
+    leading_boundary(psi, mpo, VOMPS())."""
+    tol: float = 1e-12
+    maxiter: int = 100
+    finalize: object = None
+    verbosity: int = 0
+    gauge_tol_min: float = 1e-14
+    gauge_tol_max: float = 1e-5
+    gauge_tol_factor: float = 1e-8
+    env_tol_min: float = 1e-12
+    env_tol_max: float = 1e-5
+    env_tol_factor: float = 1e-5
+
+
+@dataclass
 class GradientGrassmann(_Algorithm):  # gradient_grassmann.jl:26-44 ; method = ConjugateGradient (grassmann.py)
     tol: float = 1e-12            # Defaults.tol, the optimiser's gradtol
     maxiter: int = 100            # Defaults.maxiter

@@ -6,7 +6,11 @@ A site visit has no Krylov loop: it is ONE projection of the tensors of the stat
 `below` (ac_proj / ac2_proj, derivatives.jl:210-226), one gauge step and one mixed transfer.  The projection runs on
 mpsk_dAC_proj / mpsk_dAC2_proj (rectangular environments; the two-site form never builds the two-site tensor of `above`) and
 the convergence measure on mpsk_vdiff_nrm2.  Backends without these entry points take the composed route (dAC / dAC2 on a
-formed two-site tensor, two norms) -- the pattern changebonds uses for dAC2_product."""
+formed two-site tensor, two norms) -- the pattern changebonds uses for dAC2_product.
+
+approximate for InfiniteMPS (src/algorithms/approximate/vomps.jl): the VOMPS power method on the mixed environments of
+statmech.PerMPOInfEnv -- per site one ac_proj (mpsk_dAC_proj) and one c_proj (mpsk_dC_proj), then a regauge.  The IDMRG1 / IDMRG2
+forms (approximate/idmrg.jl), MPSMultiline / MPOMultiline with more than one row and complex tensors are not implemented."""
 from __future__ import annotations
 
 import math
@@ -15,10 +19,12 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .algorithms import DMRG, DMRG2, _log, _no_cplx, _two_site_tensor
+from .algorithms import DMRG, DMRG2, VOMPS, VUMPS, _log, _no_cplx, _two_site_tensor, regauge, updatetol
 from .backend import DTensor
 from .environments import FinEnvPair, environments
 from .operators import MPOHamiltonian, SparseMPO
+from .states import InfiniteMPS
+from .statmech import DenseMPO, PerMPOInfEnv, calc_galerkin as _calc_galerkin_mpo
 
 
 # ---- projections --------------------------------------------------------------------------------------------------
@@ -31,8 +37,11 @@ def _sandwich(be, GL: DTensor, x: DTensor, GR: DTensor):
     return be.gemm(t.reshape(t.size // Dr, Dr), DTensor(GR.buf, (Dr, Dro)))
 
 
-def ac_proj(pos, below, envs: FinEnvPair):
-    """ac_proj(pos, below, envs)  (derivatives.jl:210-215): dAC of above.AC[pos] with the environments of `below`."""
+def ac_proj(pos, below, envs):
+    """ac_proj(pos, below, envs)  (derivatives.jl:210-219): dAC of above.AC[pos] with the environments of `below`
+    (FinEnvPair, or statmech.PerMPOInfEnv on uniform states)."""
+    if isinstance(envs, PerMPOInfEnv):
+        return envs.ac_proj(pos, below)
     be = below.be
     GL, GR = envs.leftenv(pos, below), envs.rightenv(pos, below)
     x, H = envs.above.AC(pos), envs.opp[pos]
@@ -42,6 +51,12 @@ def ac_proj(pos, below, envs: FinEnvPair):
     if hasattr(be, "dAC_proj"):
         return be.dAC_proj(H, GL, GR, x)
     return be.dAC(H, GL, GR, x, out=be.empty(Dlo, d, Dro))
+
+
+def c_proj(pos, below, envs: PerMPOInfEnv):
+    """c_proj(pos, below, envs)  (derivatives.jl:204-207): dC of above.CR[pos] with the environments of `below` (uniform
+    states; mpsk_dC_proj)."""
+    return envs.c_proj(pos, below)
 
 
 def ac2_proj(pos, below, envs: FinEnvPair):
@@ -90,7 +105,13 @@ def approximate(psi0, toapprox, alg, envs=None):
     toapprox: an (O, above) pair, a bare FiniteMPS, or a list of those (summed); alg: DMRG() (one-site, fixed bond dimension)
     or DMRG2() (two-site, alg's truncation).  envs: what a previous call returned.  eps is the largest relative change of a
     site tensor during the last sweep; the (iteration, eps) pairs of all sweeps are kept as `.history` on every returned
-    environment.  Complex states / operators: native_cplx.approximate."""
+    environment.  Complex states / operators: native_cplx.approximate.
+    psi0 an InfiniteMPS: toapprox = (O, above) with O a DenseMPO or a real SparseMPO (make_time_mpo of an infinite
+    Hamiltonian), alg = VOMPS() (approximate/vomps.jl; a VUMPS is converted, as the reference's deprecation does); eps is the
+    Galerkin error.  Not implemented for uniform states: IDMRG1 / IDMRG2 (approximate/idmrg.jl), more than one row, complex
+    tensors."""
+    if isinstance(psi0, InfiniteMPS):
+        return _approximate_inf(psi0, toapprox, alg, envs)
     _no_cplx(psi0, "approximate")
     single = not isinstance(toapprox, list)
     squash = [toapprox] if single else list(toapprox)
@@ -110,6 +131,40 @@ def approximate(psi0, toapprox, alg, envs=None):
     else:
         raise TypeError(f"approximate takes DMRG or DMRG2, not {type(alg).__name__}")
     return psi, (envs[0] if single else envs), eps
+
+
+def _approximate_inf(psi, toapprox, alg, envs=None):  # approximate/vomps.jl:1-80 (one row)
+    if isinstance(alg, VUMPS):           # vomps.jl:12-17
+        alg = VOMPS(tol=alg.tol, maxiter=alg.maxiter, finalize=alg.finalize, verbosity=alg.verbosity,
+                    gauge_tol_min=alg.gauge_tol_min, gauge_tol_max=alg.gauge_tol_max, gauge_tol_factor=alg.gauge_tol_factor,
+                    env_tol_min=alg.env_tol_min, env_tol_max=alg.env_tol_max, env_tol_factor=alg.env_tol_factor)
+    if not isinstance(alg, VOMPS):
+        raise TypeError(f"approximate on an InfiniteMPS takes VOMPS (or VUMPS), not {type(alg).__name__}")
+    if not (isinstance(toapprox, tuple) and len(toapprox) == 2 and isinstance(toapprox[0], (DenseMPO, SparseMPO))
+            and isinstance(toapprox[1], InfiniteMPS)):
+        raise TypeError("approximate on an InfiniteMPS takes (O, above): a DenseMPO or SparseMPO and an InfiniteMPS")
+    O, above = toapprox
+    if getattr(psi, "cplx", False) or getattr(above, "cplx", False) or getattr(O, "cplx", False):
+        raise NotImplementedError("approximate on an InfiniteMPS: complex states / operators are not supported (real fp64 only)")
+    if len(above) != len(psi):
+        raise ValueError(f"unit cells of the states above ({len(above)}) and below ({len(psi)}) differ")
+    be, n = psi.be, len(psi)
+    envs = environments(psi, toapprox) if envs is None else envs
+    eps = _calc_galerkin_mpo(psi, envs)
+    t0, history = time.time(), []
+    for it in range(1, alg.maxiter + 1):
+        newAL = [regauge(be, ac_proj(loc, psi, envs), c_proj(loc, psi, envs)) for loc in range(n)]
+        gtol = updatetol(alg.gauge_tol_min, alg.gauge_tol_max, alg.gauge_tol_factor, it, eps)
+        psi = InfiniteMPS.from_AL(newAL, psi.CR[n - 1], tol=gtol, be=be)
+        envs.recalculate(psi, updatetol(alg.env_tol_min, alg.env_tol_max, alg.env_tol_factor, it, eps))
+        if alg.finalize is not None:
+            psi, envs = alg.finalize(it, psi, toapprox, envs)
+        eps = _calc_galerkin_mpo(psi, envs)
+        _finish(alg, "VOMPS", it, eps, t0, history)
+        if eps <= alg.tol:
+            break
+    envs.history = history
+    return psi, envs, eps
 
 
 def _finish(alg, name, it, eps, t0, history):

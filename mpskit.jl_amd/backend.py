@@ -324,6 +324,17 @@ class Backend:
         check(self.lib.mpsk_dAC_proj(self.ctx, H.handle, Dlo // m, Dl, Dr, Dro, GL.ptr, GR.ptr, x.ptr, y.ptr), "mpsk_dAC_proj")
         return y
 
+    def dC_proj(self, GL: DTensor, GR: DTensor, c: DTensor, out: DTensor = None):
+        """mpsk_dC_proj (c_proj): the zero-site map with rectangular environments, GL (W, Dlo, Dl) and GR (W, Dr, Dro); c is
+        [Dl, Dr], the result [Dlo, Dro].  Real fp64 only."""
+        Dl, Dr = c.shape
+        W, Dlo, Dl2 = GL.shape
+        W2, Dr2, Dro = GR.shape
+        assert W2 == W and Dl2 == Dl and Dr2 == Dr, (GL.shape, GR.shape, c.shape)
+        y = self.empty(Dlo, Dro) if out is None else out
+        check(self.lib.mpsk_dC_proj(self.ctx, W, Dlo, Dl, Dr, Dro, GL.ptr, GR.ptr, c.ptr, y.ptr), "mpsk_dC_proj")
+        return y
+
     def dAC2_proj(self, H1, H2, GL: DTensor, GR: DTensor, AC: DTensor, AR: DTensor, out: DTensor = None):
         """mpsk_dAC2_proj (ac2_proj) on the two factors of the state above, AC [Dl, d1, Dm] and AR [Dm, d2, Dr], with
         GL (Wl, Dlo, Dl) and GR (Wr, Dr, Dro).  Returns Y[Dlo, d1, Dro, d2]; the two-site tensor is not formed (fp64)."""

@@ -1369,25 +1369,42 @@ int mpsk_hac_eigsolve_fixed(mpsk_hac* h, const void* x0, int m, void* const* V, 
   return mpsk_vnormalize_dev(c, n, V[m + 1], y, nullptr);
 }
 
+// y = sum_w GL[w] c GR[w] with GR slabs [Dr, Dro]: one batched GEMM T[w] = GL[w] c, then the segmented-K GEMM over (w, b).
+// mpsk_dC passes Dro = Dr, mpsk_dC_proj the bond dimension of the state below.
+static int dC_f64(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, int Dro, const double* GL, const double* GR, const double* cm,
+                  double* y) {
+  HIPCHK(hipSetDevice(c->device));
+  const size_t slab = (size_t)Dlo * Dr;
+  if (int rc = ensure_ws(c, sizeof(double) * slab * W)) return rc;
+  double* T1 = (double*)c->ws;
+  GemmArgs g1 = mk(GL, cm, T1, Dlo, Dr, Dl, Dlo, Dl, Dlo);
+  g1.batch = W; g1.bsA = (int64_t)Dlo * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
+  g1.tag = 1;
+  HIPCHK(gemm_f64(g1, c->stream));
+  std::vector<int64_t> sa, sb;
+  for (int w = 0; w < W; ++w) { sa.push_back((int64_t)w * slab); sb.push_back((int64_t)w * Dr * Dro); }
+  GemmArgs g3 = mk(T1, GR, y, Dlo, Dro, Dr, Dlo, Dr, Dlo);
+  g3.tag = 1;
+  HIPCHK(gemm_segments(g3, sa, sb, c->stream));
+  return MPSK_OK;
+}
+
 int mpsk_dC(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, const void* GL, const void* GR, const void* cm, void* y) {
   REQUIRE(c && GL && GR && cm && y, "NULL argument");
   REQUIRE(W > 0 && Dlo > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
   if (c->dtype == MPSK_C128)
     return dC_c128(c, W, Dlo, Dl, Dr, (const double*)GL, (const double*)GR, (const double*)cm, (double*)y);
-  HIPCHK(hipSetDevice(c->device));
-  const size_t slab = (size_t)Dlo * Dr;
-  if (int rc = ensure_ws(c, sizeof(double) * slab * W)) return rc;
-  double* T1 = (double*)c->ws;
-  GemmArgs g1 = mk((const double*)GL, (const double*)cm, T1, Dlo, Dr, Dl, Dlo, Dl, Dlo);
-  g1.batch = W; g1.bsA = (int64_t)Dlo * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
-  g1.tag = 1;
-  HIPCHK(gemm_f64(g1, c->stream));
-  std::vector<int64_t> sa, sb;
-  for (int w = 0; w < W; ++w) { sa.push_back((int64_t)w * slab); sb.push_back((int64_t)w * Dr * Dr); }
-  GemmArgs g3 = mk(T1, (const double*)GR, (double*)y, Dlo, Dr, Dr, Dlo, Dr, Dlo);
-  g3.tag = 1;
-  HIPCHK(gemm_segments(g3, sa, sb, c->stream));
-  return MPSK_OK;
+  return dC_f64(c, W, Dlo, Dl, Dr, Dr, (const double*)GL, (const double*)GR, (const double*)cm, (double*)y);
+}
+
+// c_proj (derivatives.jl:204-207): the zero-site map with a rectangular right environment, GR slabs [Dr, Dro] (ket leg of the
+// state above, bra leg of the state below).  Dro = Dr is mpsk_dC launch for launch.
+int mpsk_dC_proj(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR, const void* cm,
+                 void* y) {
+  REQUIRE(c && GL && GR && cm && y, "NULL argument");
+  REQUIRE(W > 0 && Dlo > 0 && Dl > 0 && Dr > 0 && Dro > 0, "dimensions must be positive");
+  if (c->dtype == MPSK_C128) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_dC_proj: implemented for MPSK_F64 only");
+  return dC_f64(c, W, Dlo, Dl, Dr, Dro, (const double*)GL, (const double*)GR, (const double*)cm, (double*)y);
 }
 
 static int pair_plan(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, const MixPlan** out) {

@@ -185,13 +185,16 @@ class MultipleEnvironments:
 
 def environments(psi, H, **kw):
     """environments(psi, H)  (FinEnv.jl:41-70 / mpohaminfenv.jl:40-44 / multipleenv.jl:30-34; a DenseMPO:
-    permpoinfenv.jl:20-29, statmech.PerMPOInfEnv)."""
+    permpoinfenv.jl:20-29, an InfiniteMPS with H = (O, above): permpoinfenv.jl:29-42, both statmech.PerMPOInfEnv)."""
     from .states import FiniteMPS
     from .operators import LazySum
     from .statmech import DenseMPO, PerMPOInfEnv
     if isinstance(psi, FiniteMPS) and isinstance(H, (tuple, FiniteMPS)):       # FinEnv.jl:21-23, :91-99
         O, above = H if isinstance(H, tuple) else (None, H)
         return FinEnvPair(psi, O, above)
+    if isinstance(H, tuple):                                                    # permpoinfenv.jl:29-42
+        from .statmech import environments as _mixed
+        return _mixed(psi, H, **kw)
     if isinstance(H, DenseMPO):
         return PerMPOInfEnv(psi, H, **kw)
     if isinstance(H, LazySum):
