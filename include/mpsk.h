@@ -308,6 +308,27 @@ int mpsk_transfer_left(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, int 
                        int Drb, const void* GLin, const void* A, const void* Ab, void* GLout);
 int mpsk_transfer_right(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb,
                         int Drb, const void* A, const void* Ab, const void* GRin, void* GRout);
+/* ---- local measurements: src/algorithms/expval.jl:23-37, src/algorithms/correlators.jl:10-43 ----
+ * mpsk_site_gram: the Gram matrix over the physical index of two site tensors,
+ *   dev_out[w][t,s] = sum_{p,b} conj(Ab[p,t,b]) X[w][p,s,b]
+ *   X: W tensors [Dl,d,Dr], contiguous; Ab: [Dl,d,Dr]; dev_out: W column-major d x d matrices (t fastest) in DEVICE memory.
+ *   X = Ab = AC, W = 1 is the one-site reduced density matrix: <O> = sum_{t,s} O[t,s] dev_out[t,s] for every one-site
+ *   operator of that site (expval.jl:23-37).  One pass over X and Ab for d <= 4 (ceil(d/4) passes above), O(d^2 Dl Dr)
+ *   flops.  Asynchronous on the ctx stream, nothing is copied to the host.  Follows mpsk_ctx_set_dtype: under MPSK_C128
+ *   all three arrays are interleaved complex; under MPSK_F64 the conj does nothing.  The reduction takes a fixed order
+ *   (per-thread partial sums, wavefront reduction, one final reduction launch, no atomics): bit-identical from run to run.
+ *   Workspace: W d^2 1024 doubles (twice that for MPSK_C128).
+ * mpsk_transfer_left_gram: one site of correlator(psi, O1, O2, i, js) (correlators.jl:25-38): the pass-through
+ *   (H == NULL) mpsk_transfer_left together with the site Gram of its stage-1 product T1[w][p,s,b] = sum_a Vin[w][p,a] A[a,s,b],
+ *   dev_gram[w][t,s] = sum Vin[w][p,a] A[a,s,b] conj(Ab[p,t,b])       (= mpsk_site_gram(T1, Ab); needs Dr == Drb)
+ *   so that the closing contraction with O2, sum_{w,t,s} O2[w,t,s] dev_gram[w][t,s], costs no second pair of GEMMs.
+ *   Vin: W slabs [Dlb, Dl]; A: [Dl,d,Dr]; Ab: [Dlb,d,Drb]; Vout: W slabs [Drb, Dr], bit for bit what
+ *   mpsk_transfer_left(ctx, NULL, W, ...) writes (the same GEMM calls), or NULL for the last site of a range: stage 2 is
+ *   then skipped.  dev_gram: W column-major d x d matrices in DEVICE memory.  Asynchronous; follows the ctx dtype.
+ *   Dr != Drb: MPSK_ERR_INVALID. */
+int mpsk_site_gram(mpsk_ctx* ctx, int W, int d, int Dl, int Dr, const void* X, const void* Ab, void* dev_out);
+int mpsk_transfer_left_gram(mpsk_ctx* ctx, int W, int d, int Dl, int Dr, int Dlb, int Drb, const void* Vin, const void* A,
+                            const void* Ab, void* Vout, void* dev_gram);
 /* The transfers with flags.  MPSK_TRANSFER_CANONICAL: the caller guarantees that level 0 of GLin (mpsk_transfer_left_ex) /
  * level W-1 of GRin (mpsk_transfer_right_ex) is the identity and that A == Ab is an isometry on the contracted side
  * (sum_{p,t} A[p,t,q] A[p,t,b] = delta_qb, resp. sum_{t,b} A[a,t,b] A[p,t,b] = delta_ap) -- the environment update of a finite

@@ -255,6 +255,23 @@ function transfer_right(v::ROCTensor{3}, ::Nothing, A::ROCTensor{3}, Ab::ROCTens
         CTX[], C_NULL, W, A.dims[2], A.dims[1], A.dims[3], Ab.dims[1], Ab.dims[3], A.ptr, Ab.ptr, v.ptr, out.ptr))
     return out
 end
+# ---- local measurements: expval.jl:23-37, correlators.jl:25-38 ----
+"gram[w][t,s] = sum_{p,b} conj(Ab[p,t,b]) X[w][p,s,b] into device memory (W matrices d x d); X = Ab = AC: one-site rho"
+function site_gram!(gram::Ptr{Cvoid}, W::Integer, X::ROCTensor, Ab::ROCTensor{3})
+    check(ccall((:mpsk_site_gram, libmpsk[]), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        CTX[], W, Ab.dims[2], Ab.dims[1], Ab.dims[3], X.ptr, Ab.ptr, gram))
+    return gram
+end
+"pass-through transfer_left plus the site Gram of its intermediate; last = true: last site of a range, nothing is transferred"
+function transfer_left_gram!(gram::Ptr{Cvoid}, v::ROCTensor{3}, A::ROCTensor{3}, Ab::ROCTensor{3}; last::Bool=false)
+    W = v.dims[1]
+    out = last ? nothing : ROCTensor((W, Ab.dims[3], A.dims[3]))
+    check(ccall((:mpsk_transfer_left_gram, libmpsk[]), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        CTX[], W, A.dims[2], A.dims[1], A.dims[3], Ab.dims[1], Ab.dims[3], v.ptr, A.ptr, Ab.ptr,
+        last ? C_NULL : out.ptr, gram))
+    return out
+end
 "v[w] -= <lvec, v[w]> rvec on every slab (RegTransferMatrix, transfermatrix.jl:55,70-90)"
 function regularize!(v::ROCTensor{3}, lvec::ROCTensor{2}, rvec::ROCTensor{2})
     check(ccall((:mpsk_regularize, libmpsk[]), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),

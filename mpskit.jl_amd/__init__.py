@@ -21,4 +21,5 @@ from .toolbox import (variance, entropy, entanglement_spectrum, transfer_spectru
                       exact_diagonalization)
 from .statmech import DenseMPO, PerMPOInfEnv, leading_boundary, classical_ising, sixvertex, dot  # noqa: F401,E402
 from . import native_cplx  # noqa: F401,E402   (complex128 states on interleaved storage: NativeFiniteMPS, dmrg, tdvp_step)
+from .measure import correlator, decompose_localmpo  # noqa: F401,E402   (local expectation values: expectation_value above)
 from .propagator import propagator, DynamicalDMRG, NaiveInvert, Jeckelmann, GMRES, LinearCombination  # noqa: F401,E402

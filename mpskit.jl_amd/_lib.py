@@ -136,6 +136,9 @@ SIGNATURES = {
                        C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                        C.c_int64],
     "mpsk_grassmann_coef": [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p],
+    "mpsk_site_gram": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mpsk_transfer_left_gram": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p],
 }
 # symbols without the (ctx, ...) -> int shape
 EXTRA_SYMBOLS = ["mpsk_version", "mpsk_last_error"]

@@ -171,9 +171,15 @@ def calc_galerkin(psi, pos, envs=None, h=None, g=None):
     return _galerkin(be, h, ac, al, g)
 
 
-def expectation_value(psi, H, envs=None):
+def expectation_value(psi, H, envs=None, *, device=None):
     """Per-site energies (expval.jl:92-109 finite, :111-124 infinite); for a DenseMPO the per-site leading eigenvalue
-    (expval.jl:156-172, statmech.expectation_value)."""
+    (expval.jl:156-172, statmech.expectation_value).
+    Local operators (expval.jl:23-61, measure.py): expectation_value(psi, O) with O a [d,d] ndarray or a list of one per
+    site, and expectation_value(psi, O, at) with an N-site ndarray or a list of MPO tensors and an int position; `device`
+    selects their route (measure.expectation_value)."""
+    from . import measure
+    if measure.is_local_operator(H, envs):
+        return measure.expectation_value(psi, H, envs, device=device)
     from .statmech import DenseMPO, expectation_value as _expval_dense
     if isinstance(H, DenseMPO):
         return _expval_dense(psi, H, envs)

@@ -406,6 +406,47 @@ class Backend:
                                           GLin.ptr, A.ptr, Ab.ptr, y.ptr), "mpsk_transfer_left")
         return y
 
+    # ---- local measurements (measure.py): the presence of these two methods tells the host code that the backend has the
+    # fused device route.  Gram results are slabs like an environment: W column-major d x d matrices (t fastest), shape
+    # (W, d, d), or (W, 2 d, d) interleaved for complex tensors; they stay on the device.
+    def site_gram(self, X: DTensor, Ab: DTensor, out: DTensor = None, cplx=False):
+        """mpsk_site_gram: out[w][t,s] = sum_{p,b} conj(Ab[p,t,b]) X[w][p,s,b].  X: [Dl,d,Dr] or W of them as
+        (W, Dl, d, Dr) slabs; asynchronous."""
+        c = 2 if cplx else 1
+        Dl, d, Dr = Ab.shape[0] // c, Ab.shape[1], Ab.shape[2]
+        W = X.size // Ab.size
+        if W < 1 or W * Ab.size != X.size:
+            raise MpskError(f"site_gram: X {X.shape} is not a whole number of tensors of the shape of Ab {Ab.shape}")
+        g = self.empty(W, c * d, d) if out is None else out
+        if g.size != W * c * d * d:
+            raise MpskError(f"site_gram: out {g.shape} does not hold {W} matrices {c * d} x {d}")
+        self._set_dtype(cplx)
+        try:
+            check(self.lib.mpsk_site_gram(self.ctx, W, d, Dl, Dr, X.ptr, Ab.ptr, g.ptr), "mpsk_site_gram")
+        finally:
+            self._set_dtype(False)
+        return g
+
+    def transfer_left_gram(self, Vin: DTensor, A: DTensor, Ab: DTensor, gram_out: DTensor, out: DTensor = None, last=False,
+                           cplx=False):
+        """mpsk_transfer_left_gram: the pass-through transfer_left(None, Vin, A, Ab) plus gram_out[w][t,s] =
+        sum Vin[w][p,a] A[a,s,b] conj(Ab[p,t,b]) from its intermediate.  gram_out: a view into a caller-owned buffer (a whole
+        range is downloaded once).  last=True: last site of a range, nothing is transferred and None is returned."""
+        c = 2 if cplx else 1
+        Dl, d, Dr = A.shape[0] // c, A.shape[1], A.shape[2]
+        Dlb, Drb = Ab.shape[0] // c, Ab.shape[2]
+        W = Vin.shape[0]
+        if gram_out.size != W * c * d * d:
+            raise MpskError(f"transfer_left_gram: gram_out {gram_out.shape} does not hold {W} matrices {c * d} x {d}")
+        y = None if last else (self.empty(W, c * Drb, Dr) if out is None else out)
+        self._set_dtype(cplx)
+        try:
+            check(self.lib.mpsk_transfer_left_gram(self.ctx, W, d, Dl, Dr, Dlb, Drb, Vin.ptr, A.ptr, Ab.ptr,
+                                                   None if last else y.ptr, gram_out.ptr), "mpsk_transfer_left_gram")
+        finally:
+            self._set_dtype(False)
+        return y
+
     def transfer_left_ex(self, H, GLin: DTensor, A: DTensor, Ab: DTensor, canonical: bool = False, out: DTensor = None):
         """mpsk_transfer_left_ex (real tensors); its presence tells FinEnv that the backend has the canonical route."""
         return self.transfer_left(H, GLin, A, Ab, out=out, canonical=canonical)

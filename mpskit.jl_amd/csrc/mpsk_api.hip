@@ -732,14 +732,18 @@ static int dAC2_c128(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* 
 }
 
 // GLout[v][q,b] = sum GLin[w][p,a] A[a,s,b] O[w,t,s,v] conj(Ab[p,t,q])
+// gram (pass-through only, Dr == Drb): gram[w][t,s] = sum conj(Ab[p,t,b]) T1[w][p,s,b] of the stage-1 product, partials
+// after T1 in the workspace; GLout == nullptr then skips stage 2 (mpsk_transfer_left_gram)
 static int transfer_left_c128(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
-                              const double* GLin, const double* A, const double* Ab, double* GLout) {
+                              const double* GLin, const double* A, const double* Ab, double* GLout,
+                              double* gram = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   int Wl = W, Wr = W;
   if (H) { Wl = H->Wl; Wr = H->Wr; d = H->d; }
   const size_t nA = (size_t)Dl * d * Dr, slab = (size_t)2 * Dlb * d * Dr;
   const size_t o_t1 = 2 * ev2(nA), o_t2 = o_t1 + slab * Wl;
-  if (int rc = ensure_ws(c, sizeof(double) * (o_t2 + (H ? slab * Wr : 0)))) return rc;
+  if (int rc = ensure_ws(c, sizeof(double) * (o_t2 + (H ? slab * Wr : 0) + (gram ? site_gram_partial_doubles(Wl, d, true) : 0))))
+    return rc;
   double* Ap = (double*)c->ws;
   double* T1 = Ap + o_t1;
   double* T2 = H ? Ap + o_t2 : T1;
@@ -753,6 +757,8 @@ static int transfer_left_c128(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d,
     SlabIndex ix{d, 1 << 30, (int64_t)2 * Dlb, (int64_t)slab, 0, (int64_t)2 * Dlb * d};
     HIPCHK(mix_apply(H->fwd, T1, ix, T2, ix, 2 * Dlb, Dr, c->stream));
   }
+  if (gram) HIPCHK(site_gram(Wl, d, Dlb, Dr, T1, Ab, true, gram, Ap + o_t2, c->stream));
+  if (!GLout) return MPSK_OK;
   // GLout[v] = Ab^H T2[v]:  K = (re / im, p, t) interleaved on both operands ->  real part = Ab_half^T T2_half,
   // imaginary part = (J Ab_half)^T T2_half ; plane alpha goes to the rows 2 q + alpha of the interleaved result
   for (int al = 0; al < 2; ++al) {
@@ -1653,6 +1659,9 @@ int mpsk_transfer_right_ex(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, in
   return mpsk_transfer_right(c, H, W, d, Dl, Dr, Dlb, Drb, A, Ab, GRin, GRout);
 }
 
+static int transfer_left_f64(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr, int d, int Dl, int Dr, int Dlb, int Drb,
+                             const void* GLin, const void* A, const void* Ab, void* GLout, double* gram);
+
 int mpsk_transfer_left(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
                        const void* GLin, const void* A, const void* Ab, void* GLout) {
   REQUIRE(c && GLin && A && Ab && GLout, "NULL argument");
@@ -1664,8 +1673,16 @@ int mpsk_transfer_left(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl
     return transfer_left_c128(c, H, W, d, Dl, Dr, Dlb, Drb, (const double*)GLin, (const double*)A, (const double*)Ab, (double*)GLout);
   if (dense_route(H))
     return transfer_left_dense(c, H, Dl, Dr, Dlb, Drb, (const double*)GLin, (const double*)A, (const double*)Ab, (double*)GLout);
-  const size_t slab = (size_t)Dlb * d * Dr;
-  if (int rc = ensure_ws(c, sizeof(double) * slab * (Wl + (H ? Wr : 0)))) return rc;
+  return transfer_left_f64(c, H, Wl, Wr, d, Dl, Dr, Dlb, Drb, GLin, A, Ab, GLout, nullptr);
+}
+
+// gram (pass-through only, Dr == Drb): gram[w][t,s] = sum Ab[p,t,b] T1[w][p,s,b] of the stage-1 product, partials after
+// T1 in the workspace; GLout == nullptr then skips stage 2 (mpsk_transfer_left_gram)
+static int transfer_left_f64(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr, int d, int Dl, int Dr, int Dlb, int Drb,
+                             const void* GLin, const void* A, const void* Ab, void* GLout, double* gram) {
+  const size_t slab = (size_t)Dlb * d * Dr, o_part = up32(slab * (Wl + (H ? Wr : 0)));
+  if (int rc = ensure_ws(c, sizeof(double) * (gram ? o_part + site_gram_partial_doubles(Wl, d, false) : slab * (Wl + (H ? Wr : 0)))))
+    return rc;
   double* T1 = (double*)c->ws;
   double* T2 = H ? T1 + slab * Wl : T1;
   // T1[w][p,s,b] = sum_a GLin[w][p,a] A[a,s,b]
@@ -1676,10 +1693,38 @@ int mpsk_transfer_left(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl
     SlabIndex ix{d, 1 << 30, (int64_t)Dlb, (int64_t)slab, 0, (int64_t)Dlb * d};
     HIPCHK(mix_apply(H->fwd, T1, ix, T2, ix, Dlb, Dr, c->stream));
   }
+  if (gram) HIPCHK(site_gram(Wl, d, Dlb, Dr, T1, (const double*)Ab, false, gram, T1 + o_part, c->stream));
+  if (!GLout) return MPSK_OK;
   // GLout[v][q,b] = sum_{(p,t)} Ab[(p,t),q] T2[v][(p,t),b]
   GemmArgs g3 = mk((const double*)Ab, T2, (double*)GLout, Drb, Dr, Dlb * d, (int64_t)Dlb * d, (int64_t)Dlb * d, Drb, 1, 0);
   g3.batch = Wr; g3.bsA = 0; g3.bsB = (int64_t)slab; g3.bsC = (int64_t)Drb * Dr;
   HIPCHK(gemm_f64(g3, c->stream));
+  return MPSK_OK;
+}
+
+// The pass-through left transfer plus the site Gram of its stage-1 product: one site of a correlator
+// (correlators.jl:10-43).  Vout == NULL: last site of a range, stage 2 is skipped.
+int mpsk_transfer_left_gram(mpsk_ctx* c, int W, int d, int Dl, int Dr, int Dlb, int Drb, const void* Vin, const void* A,
+                            const void* Ab, void* Vout, void* dev_gram) {
+  REQUIRE(c && Vin && A && Ab && dev_gram, "NULL argument");
+  REQUIRE(W > 0 && d > 0 && Dl > 0 && Dr > 0 && Dlb > 0 && Drb > 0, "dimensions must be positive");
+  REQUIRE(Dr == Drb, "the Gram of the intermediate needs Dr == Drb");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->dtype == MPSK_C128)
+    return transfer_left_c128(c, nullptr, W, d, Dl, Dr, Dlb, Drb, (const double*)Vin, (const double*)A, (const double*)Ab,
+                              (double*)Vout, (double*)dev_gram);
+  return transfer_left_f64(c, nullptr, W, W, d, Dl, Dr, Dlb, Drb, Vin, A, Ab, Vout, (double*)dev_gram);
+}
+
+// dev_out[w][t,s] = sum_{p,b} conj(Ab[p,t,b]) X[w][p,s,b]: the one-site reduced density matrix for X = Ab = AC
+// (expval.jl:23-37).  Asynchronous; the result stays on the device.
+int mpsk_site_gram(mpsk_ctx* c, int W, int d, int Dl, int Dr, const void* X, const void* Ab, void* dev_out) {
+  REQUIRE(c && X && Ab && dev_out, "NULL argument");
+  REQUIRE(W > 0 && d > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
+  HIPCHK(hipSetDevice(c->device));
+  const bool cplx = c->dtype == MPSK_C128;
+  if (int rc = ensure_ws(c, sizeof(double) * site_gram_partial_doubles(W, d, cplx))) return rc;
+  HIPCHK(site_gram(W, d, Dl, Dr, (const double*)X, (const double*)Ab, cplx, (double*)dev_out, (double*)c->ws, c->stream));
   return MPSK_OK;
 }
 

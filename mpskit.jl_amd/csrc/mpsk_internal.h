@@ -174,6 +174,12 @@ hipError_t vec_multiaxpy_c(const double* const* xs, const double* d_coefs, int k
 hipError_t vec_cgs2_c(const double* const* xs, int k, double* y, int64_t n, double* d_out, double* d_partial, hipStream_t s);
 hipError_t vec_axpby_c(const double a[2], const double* x, const double b[2], double* y, int64_t n, hipStream_t s);
 hipError_t identity_dev_c(const double* G, int n, double* d_out, int nblocks, hipStream_t s);   // d_out[b]: per-block max|G - I|
+// d_out[w][t,s] = sum_{p,b} conj(Ab[p,t,b]) X[w][p,s,b]: X W tensors [Dl,d,Dr], Ab [Dl,d,Dr] (interleaved when cplx), d_out
+// W column-major d x d matrices; d_partial: site_gram_partial_doubles(W, d, cplx) doubles of scratch.  Asynchronous,
+// deterministic (fixed-order partial sums + dot_final_kernel).
+size_t site_gram_partial_doubles(int W, int d, bool cplx);
+hipError_t site_gram(int W, int d, int Dl, int Dr, const double* X, const double* Ab, bool cplx, double* d_out,
+                     double* d_partial, hipStream_t s);
 
 // ---- gauge kernels ----------------------------------------------------------------------------
 size_t regularize_workspace_doubles(int W, int D1, int D2);

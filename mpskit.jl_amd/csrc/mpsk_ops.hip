@@ -840,6 +840,136 @@ hipError_t vec_multidotc(const double* const* xs, int k, const double* y, int64_
   return hipGetLastError();
 }
 
+// ---- site Gram: out[w][t,s] = sum_{p,b} conj(Ab[p,t,b]) X[w][p,s,b] ---------------------------------------------------
+// The d x d reduced density matrix of a site (X = Ab = AC) and the closing contraction of a correlator (X = the stage-1
+// product of a transfer, Ab = AR) are the same reduction over the two bond indices.  One work item is one (p, b)
+// position: a p-pair read as one d2 per physical index (real, even Dl, 16-B aligned operands), one p (real otherwise:
+// with odd Dl the column starts are only 8-B aligned) or one complex element (one d2, or two doubles when unaligned).
+// Consecutive lanes take consecutive p, so every load of a wavefront is one contiguous run of a column; the (p, b)
+// position advances by the grid stride with one division per thread, not one per item.  The N x N tile (t0.., s0..) of
+// accumulators lives in registers; blockIdx.y = w.  Same reduction structure as the dot kernels: fixed element order
+// per thread, wave_sum / block_sum, per-block partials, dot_final_kernel.
+// partial[((w d^2 + t + d s) C + c) * DOT_BLOCKS + blockIdx.x], C = 2 (re, im) for complex, else 1
+template <int N, bool CPLX, bool VEC2>
+__global__ __launch_bounds__(256) void site_gram_kernel(const double* __restrict__ X, const double* __restrict__ Ab, int d,
+                                                        int Dl, int Dr, int t0, int s0, int nt, int ns,
+                                                        double* __restrict__ partial) {
+  constexpr int C = CPLX ? 2 : 1;
+  constexpr int NV = N * N * C;
+  constexpr bool PAIR = CPLX || VEC2;             // an item is two doubles
+  __shared__ double sh[4 * NV];
+  double acc[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) acc[k] = 0.0;
+  const int64_t rows = (!CPLX && VEC2) ? Dl / 2 : Dl;   // items per column
+  const int64_t items = rows * Dr;
+  const int64_t ldp = (int64_t)C * Dl;                  // doubles between two physical indices
+  const int64_t ldb = ldp * d;                          // ... between two b
+  const double* __restrict__ Xw = X + (int64_t)blockIdx.y * ldb * Dr;
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  const int64_t e0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t sr = step % rows, sb = step / rows;
+  int64_t r = e0 % rows, b = e0 / rows;
+  for (int64_t e = e0; e < items; e += step) {
+    const int64_t base = (PAIR ? 2 : 1) * r + ldb * b;
+    d2 a[N], x[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      a[i] = d2{0.0, 0.0};
+      x[i] = d2{0.0, 0.0};
+      if (i < nt) {
+        const double* q = Ab + base + ldp * (t0 + i);
+        if constexpr (VEC2) a[i] = *reinterpret_cast<const d2*>(q);
+        else if constexpr (CPLX) a[i] = d2{q[0], q[1]};
+        else a[i].x = q[0];
+      }
+      if (i < ns) {
+        const double* q = Xw + base + ldp * (s0 + i);
+        if constexpr (VEC2) x[i] = *reinterpret_cast<const d2*>(q);
+        else if constexpr (CPLX) x[i] = d2{q[0], q[1]};
+        else x[i].x = q[0];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        if constexpr (CPLX) {
+          acc[2 * (i + N * j)] += a[i].x * x[j].x + a[i].y * x[j].y;
+          acc[2 * (i + N * j) + 1] += a[i].x * x[j].y - a[i].y * x[j].x;
+        } else if constexpr (VEC2) {
+          acc[i + N * j] += a[i].x * x[j].x + a[i].y * x[j].y;
+        } else {
+          acc[i + N * j] += a[i].x * x[j].x;
+        }
+      }
+    r += sr;
+    b += sb;
+    if (r >= rows) { r -= rows; ++b; }
+  }
+  block_sum<NV>(acc, sh);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+#pragma unroll
+      for (int i = 0; i < N; ++i)
+        if (i < nt && j < ns) {
+          const int64_t row = ((int64_t)blockIdx.y * d * d + (t0 + i) + (int64_t)d * (s0 + j)) * C;
+#pragma unroll
+          for (int c = 0; c < C; ++c) partial[(row + c) * DOT_BLOCKS + blockIdx.x] = acc[C * (i + N * j) + c];
+        }
+  }
+}
+
+constexpr int GRAM_TILE = 4;   // d <= GRAM_TILE: one instance per d, X and Ab read once per w
+
+size_t site_gram_partial_doubles(int W, int d, bool cplx) { return (size_t)W * d * d * (cplx ? 2 : 1) * DOT_BLOCKS; }
+
+template <int N, bool CPLX>
+static void site_gram_launch(bool vec2, dim3 grid, hipStream_t s, const double* X, const double* Ab, int d, int Dl, int Dr,
+                             int t0, int s0, int nt, int ns, double* partial) {
+  if (vec2)
+    hipLaunchKernelGGL((site_gram_kernel<N, CPLX, true>), grid, dim3(256), 0, s, X, Ab, d, Dl, Dr, t0, s0, nt, ns, partial);
+  else
+    hipLaunchKernelGGL((site_gram_kernel<N, CPLX, false>), grid, dim3(256), 0, s, X, Ab, d, Dl, Dr, t0, s0, nt, ns, partial);
+}
+
+template <bool CPLX>
+static void site_gram_tiles(bool vec2, dim3 grid, hipStream_t s, const double* X, const double* Ab, int d, int Dl, int Dr,
+                            double* partial) {
+  switch (d) {
+    case 1: site_gram_launch<1, CPLX>(vec2, grid, s, X, Ab, d, Dl, Dr, 0, 0, 1, 1, partial); return;
+    case 2: site_gram_launch<2, CPLX>(vec2, grid, s, X, Ab, d, Dl, Dr, 0, 0, 2, 2, partial); return;
+    case 3: site_gram_launch<3, CPLX>(vec2, grid, s, X, Ab, d, Dl, Dr, 0, 0, 3, 3, partial); return;
+    case 4: site_gram_launch<4, CPLX>(vec2, grid, s, X, Ab, d, Dl, Dr, 0, 0, 4, 4, partial); return;
+    default: break;
+  }
+  // d > GRAM_TILE: one launch per GRAM_TILE x GRAM_TILE tile of (t, s); X and Ab are each read ceil(d / GRAM_TILE) times
+  for (int s0 = 0; s0 < d; s0 += GRAM_TILE)
+    for (int t0 = 0; t0 < d; t0 += GRAM_TILE) {
+      const int nt = d - t0 < GRAM_TILE ? d - t0 : GRAM_TILE, ns = d - s0 < GRAM_TILE ? d - s0 : GRAM_TILE;
+      site_gram_launch<GRAM_TILE, CPLX>(vec2, grid, s, X, Ab, d, Dl, Dr, t0, s0, nt, ns, partial);
+    }
+}
+
+// X: W tensors [Dl, d, Dr], Ab: [Dl, d, Dr] (interleaved complex when cplx); d_out: W column-major d x d matrices;
+// d_partial: site_gram_partial_doubles(W, d, cplx) doubles.  Asynchronous.
+hipError_t site_gram(int W, int d, int Dl, int Dr, const double* X, const double* Ab, bool cplx, double* d_out,
+                     double* d_partial, hipStream_t s) {
+  if (W <= 0 || d <= 0 || Dl <= 0 || Dr <= 0) return hipErrorInvalidValue;
+  const bool aligned = (((uintptr_t)X | (uintptr_t)Ab) & 15) == 0;
+  const bool vec2 = aligned && (cplx || Dl % 2 == 0);
+  const int64_t items = (int64_t)((!cplx && vec2) ? Dl / 2 : Dl) * Dr;
+  int64_t nb = (items + 255) / 256;
+  if (nb > DOT_BLOCKS) nb = DOT_BLOCKS;
+  const dim3 grid((unsigned)nb, (unsigned)W);
+  if (cplx) site_gram_tiles<true>(vec2, grid, s, X, Ab, d, Dl, Dr, d_partial);
+  else site_gram_tiles<false>(vec2, grid, s, X, Ab, d, Dl, Dr, d_partial);
+  hipLaunchKernelGGL(dot_final_kernel, dim3((unsigned)(W * d * d * (cplx ? 2 : 1))), dim3(256), 0, s, d_partial, (int)nb,
+                     d_out);
+  return hipGetLastError();
+}
+
 // y += sign * sum_j coefs[j] * xs[j] with complex coefficients (interleaved, on the device)
 template <int NVEC>
 __global__ __launch_bounds__(256) void multiaxpy_c_kernel(PtrPack xs, const double* __restrict__ coefs, double sign,

@@ -582,3 +582,18 @@ def timestep(psi: NativeFiniteMPS, H, t, dt, alg, envs: NativeFinEnv = None):
     if isinstance(alg, TDVP):
         return tdvp_step(psi, H, envs, t, dt, alg)
     raise TypeError(f"timestep on interleaved states takes TDVP or TDVP2, not {type(alg).__name__}")
+
+
+def expectation_value(psi: NativeFiniteMPS, O, device=None):
+    """expectation_value(psi, O): <O_i> of every site for a [d,d] operator or a list of one per site (expval.jl:23-37), complex.
+    One mpsk_site_gram(AC_i, AC_i) under MPSK_C128 per site, one download (measure.py).  The centre is moved on a copy: psi
+    and the environments that follow its gauge stay as they are."""
+    from . import measure
+    return measure.expectation_value(psi.copy(), O, None, device=device)
+
+
+def correlator(psi: NativeFiniteMPS, O1, O2, i=None, js=None, device=None):
+    """correlator(psi, O1, O2, i, js) / correlator(psi, O12, i, js)  (correlators.jl:10-43), complex: move_center(i) on a
+    copy, then one mpsk_transfer_left_gram under MPSK_C128 per site asked for through the right-canonical tensors."""
+    from . import measure
+    return measure.correlator(psi.copy(), O1, O2, i, js, device=device)
