@@ -613,7 +613,85 @@ static hipError_t gemm_segments(GemmArgs g, const std::vector<int64_t>& sa, cons
 
 static hipError_t zero_async(void* p, size_t bytes, hipStream_t s) { return hipMemsetAsync(p, 0, bytes, s); }
 
-extern "C" {
+static size_t ev2(size_t v) { return (v + 1) & ~(size_t)1; }
+static size_t up32(size_t n) { return (n + 31) & ~(size_t)31; }      // 256-B aligned parts of the workspace
+
+namespace {
+// Workspace cursor: the regions of c->ws in the order they are taken, in doubles.  take() returns the offset of a region
+// and advances by its size rounded up to a multiple of `round` (2: ev2, 32: up32 -- the caller's choice); ensure() asks for
+// exactly what was taken, and only then at() is a valid pointer.
+struct Ws {
+  size_t n = 0;
+  size_t take(size_t doubles, size_t round = 1) { const size_t o = n; n += (doubles + round - 1) / round * round; return o; }
+  int ensure(mpsk_ctx* c) const { return ensure_ws(c, sizeof(double) * n); }
+  static double* at(mpsk_ctx* c, size_t off) { return (double*)c->ws + off; }
+};
+// K-segment lists: element offsets into A / B; j: plane of a complex B operand (the J-aware loader), empty for a real one
+struct Segs { std::vector<int64_t> a, b; std::vector<int> j; };
+}  // namespace
+
+// over MPO levels: level v gives (v strideA, v strideB + pl planeB) for each of the `planes` (1: real, 2: re / im) planes
+// of B; levels with used[v] == 0 (used2[v] == 0) are skipped.  Returns false when no segment is left: the result is zero.
+static bool level_segs(Segs& s, int W, int64_t strideA, int64_t strideB, const std::vector<char>* used = nullptr,
+                       int planes = 1, int64_t planeB = 0, const std::vector<char>* used2 = nullptr) {
+  for (int v = 0; v < W; ++v) {
+    if ((used && !(*used)[v]) || (used2 && !(*used2)[v])) continue;
+    for (int pl = 0; pl < planes; ++pl) {
+      s.a.push_back((int64_t)v * strideA); s.b.push_back(pl * planeB + (int64_t)v * strideB);
+      if (planes == 2) s.j.push_back(pl);
+    }
+  }
+  return !s.a.empty();
+}
+// over the physical index: (t strideA, t strideB)
+static void phys_segs(Segs& s, int d, int64_t strideA, int64_t strideB) { level_segs(s, d, strideA, strideB); }
+static hipError_t gemm_segments(const GemmArgs& g, const Segs& s, hipStream_t st) {
+  return gemm_segments(g, s.a, s.b, st, s.j.empty() ? nullptr : &s.j);
+}
+static int zero_fill(mpsk_ctx* c, void* y, size_t bytes) { HIPCHK(zero_async(y, bytes, c->stream)); return MPSK_OK; }
+
+// stage 2 as a slab mix over MPO levels: T2[v][:,t,:] = sum_{w,s} O[..] T1[w][:,s,:] on slabs [M, d, N]
+static hipError_t mix_levels(mpsk_ctx* c, const MixPlan& plan, int d, int M, int N, const double* T1, double* T2) {
+  SlabIndex ix{d, 1 << 30, (int64_t)M, (int64_t)M * d * N, 0, (int64_t)M * d};
+  return mix_apply(plan, T1, ix, T2, ix, M, N, c->stream);
+}
+
+// B of g is a plane pair `stride` doubles apart: two K-segments, the second through the J loader (1: J, 2: -J of A)
+static void cx_operand(GemmArgs& g, int64_t stride, int j = 1) { g.nseg = 2; g.segB[1] = stride; g.segJ[1] = (signed char)j; g.cplx = 1; }
+
+// stage 1 of the left-to-right contractions: T1[w] = G[w] X for W slabs G[w] [M, K] and X [K, N] (complex: M = 2 x rows,
+// X the plane pair cx_stride apart).  X may come in nblk row blocks, which become K-segments (mpsk_dAC_blocked).
+static hipError_t stage1(mpsk_ctx* c, int W, int M, int K, int N, const double* G, const double* X, double* T1, int tag,
+                         int nblk = 1, int64_t cx_stride = 0) {
+  const int kb = K / nblk;
+  GemmArgs g1 = mk(G, X, T1, M, N, kb, M, kb, M);
+  g1.batch = W; g1.bsA = (int64_t)M * K; g1.bsB = 0; g1.bsC = (int64_t)M * N;
+  g1.nseg = nblk;
+  for (int q = 0; q < nblk; ++q) { g1.segA[q] = (int64_t)q * kb * M; g1.segB[q] = (int64_t)q * kb * N; }
+  g1.tag = tag;
+  if (cx_stride) cx_operand(g1, cx_stride);
+  return gemm_f64(g1, c->stream);
+}
+
+// device copy of a host offset / segment table (the caller caches and frees it)
+static int upload_table(const std::vector<int64_t>& h, const char* what, int64_t** out) {
+  int64_t* p = nullptr;
+  if (hipMalloc(&p, sizeof(int64_t) * h.size()) != hipSuccess) return fail(MPSK_ERR_NOMEM, std::string(what) + " hipMalloc failed");
+  if (hipMemcpy(p, h.data(), sizeof(int64_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(MPSK_ERR_HIP, std::string(what) + " upload failed");
+  }
+  *out = p;
+  return MPSK_OK;
+}
+
+// (Wl, Wr, d) of a call that takes either a slice or, with H == NULL, the pass-through dimensions (W, d)
+static void site_dims(const mpsk_mposlice* H, int W, int& Wl, int& Wr, int& d) {
+  Wl = Wr = W;
+  if (H) { Wl = H->Wl; Wr = H->Wr; d = H->d; }
+}
+
+static bool hac_check_on() { const char* ev = getenv("MPSK_HAC_CHECK"); return ev && ev[0] == '1'; }
 
 // --------------------------------------------------------------------------------------------
 // derivatives
@@ -630,7 +708,14 @@ static hipError_t cx_planes(const double* z, size_t n, double* re, double* im, h
   if (e != hipSuccess) return e;
   return copy_strided(z + 1, 2, 0, im, 1, 0, (int64_t)n, 1, s);
 }
-static size_t ev2(size_t v) { return (v + 1) & ~(size_t)1; }
+// planar copy of an interleaved tensor of n complex elements in the workspace: [re | im], ev2(n) doubles apart
+struct CxPlanes {
+  size_t off, n;
+  CxPlanes(Ws& ws, size_t n_) : off(ws.take(n_, 2)), n(n_) { ws.take(n_, 2); }
+  int64_t stride() const { return (int64_t)ev2(n); }
+  double* at(mpsk_ctx* c) const { return Ws::at(c, off); }
+  hipError_t split(mpsk_ctx* c, const double* z) const { return cx_planes(z, n, at(c), at(c) + ev2(n), c->stream); }
+};
 
 // GRp: planar copy of GR ([re plane | im plane], each Wr Dr Dro doubles) if the caller has one (prepared operator), else null.
 // Dro: columns of the GR slabs [Dr, Dro] = last dimension of y (the square matvec passes Dro = Dr; mpsk_dAC_proj the bond
@@ -640,32 +725,22 @@ static int dAC_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t nx = (size_t)Dl * d * Dr, nG = (size_t)Wr * Dr * Dro, slab = (size_t)2 * Dlo * d * Dr;
-  const size_t o_g = 2 * ev2(nx), o_t1 = o_g + (GRp ? 0 : 2 * ev2(nG)), o_t2 = o_t1 + slab * Wl;
-  if (int rc = ensure_ws(c, sizeof(double) * (o_t2 + slab * Wr))) return rc;
-  double* xp = (double*)c->ws;
-  double* T1 = xp + o_t1;
-  double* T2 = xp + o_t2;
-  HIPCHK(cx_planes(x, nx, xp, xp + ev2(nx), c->stream));
+  Ws ws;
+  const CxPlanes xpl(ws, nx), gpl(ws, GRp ? 0 : nG);      // no region for GR when the caller has the planar copy
+  const size_t o_t1 = ws.take(slab * Wl), o_t2 = ws.take(slab * Wr);
+  if (int rc = ws.ensure(c)) return rc;
+  double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
+  HIPCHK(xpl.split(c, x));
   const double* gr = GRp;
-  size_t gplane = ev2(nG);
-  if (!gr) { double* g = xp + o_g; HIPCHK(cx_planes(GR, nG, g, g + ev2(nG), c->stream)); gr = g; gplane = ev2(nG); }
-  // stage 1: T1[w] = GL[w] x
-  GemmArgs g1 = mk(GL, xp, T1, 2 * Dlo, d * Dr, Dl, 2 * Dlo, Dl, 2 * Dlo);
-  g1.batch = Wl; g1.bsA = (int64_t)2 * Dlo * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
-  g1.nseg = 2; g1.segA[0] = g1.segA[1] = 0; g1.segB[0] = 0; g1.segB[1] = (int64_t)ev2(nx); g1.segJ[0] = 0; g1.segJ[1] = 1;
-  g1.cplx = 1;
-  HIPCHK(gemm_f64(g1, c->stream));
-  SlabIndex ix{d, 1 << 30, (int64_t)2 * Dlo, (int64_t)slab, 0, (int64_t)2 * Dlo * d};
-  HIPCHK(mix_apply(H->fwd, T1, ix, T2, ix, 2 * Dlo, Dr, c->stream));
-  std::vector<int64_t> sa, sb;
-  std::vector<int> sj;
-  for (int v = 0; v < Wr; ++v)
-    if (H->col_used[v])
-      for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)v * slab); sb.push_back((int64_t)(pl * gplane + (size_t)v * Dr * Dro)); sj.push_back(pl); }
-  if (sa.empty()) { HIPCHK(zero_async(y, sizeof(double) * 2 * Dlo * d * Dro, c->stream)); return MPSK_OK; }
+  if (!gr) { HIPCHK(gpl.split(c, GR)); gr = gpl.at(c); }
+  HIPCHK(stage1(c, Wl, 2 * Dlo, Dl, d * Dr, GL, xpl.at(c), T1, 0, 1, xpl.stride()));      // T1[w] = GL[w] x
+  HIPCHK(mix_levels(c, H->fwd, d, 2 * Dlo, Dr, T1, T2));
+  Segs sg;
+  if (!level_segs(sg, Wr, (int64_t)slab, (int64_t)Dr * Dro, &H->col_used, 2, (int64_t)ev2(nG)))
+    return zero_fill(c, y, sizeof(double) * 2 * Dlo * d * Dro);
   GemmArgs g3 = mk(T2, gr, y, 2 * Dlo * d, Dro, Dr, (int64_t)2 * Dlo * d, Dr, (int64_t)2 * Dlo * d);
   g3.cplx = 1;
-  HIPCHK(gemm_segments(g3, sa, sb, c->stream, &sj));
+  HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
 
@@ -673,28 +748,56 @@ static int dC_c128(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, const double* GL
                    double* y) {
   HIPCHK(hipSetDevice(c->device));
   const size_t nx = (size_t)Dl * Dr, nG = (size_t)W * Dr * Dr, slab = (size_t)2 * Dlo * Dr;
-  const size_t o_g = 2 * ev2(nx), o_t1 = o_g + 2 * ev2(nG);
-  if (int rc = ensure_ws(c, sizeof(double) * (o_t1 + slab * W))) return rc;
-  double* xp = (double*)c->ws;
-  double* g = xp + o_g;
-  double* T1 = xp + o_t1;
-  HIPCHK(cx_planes(cm, nx, xp, xp + ev2(nx), c->stream));
-  HIPCHK(cx_planes(GR, nG, g, g + ev2(nG), c->stream));
-  GemmArgs g1 = mk(GL, xp, T1, 2 * Dlo, Dr, Dl, 2 * Dlo, Dl, 2 * Dlo);
-  g1.batch = W; g1.bsA = (int64_t)2 * Dlo * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
-  g1.nseg = 2; g1.segB[1] = (int64_t)ev2(nx); g1.segJ[1] = 1; g1.cplx = 1;
-  HIPCHK(gemm_f64(g1, c->stream));
-  std::vector<int64_t> sa, sb;
-  std::vector<int> sj;
-  for (int w = 0; w < W; ++w)
-    for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)w * slab); sb.push_back((int64_t)(pl * ev2(nG) + (size_t)w * Dr * Dr)); sj.push_back(pl); }
-  GemmArgs g3 = mk(T1, g, y, 2 * Dlo, Dr, Dr, 2 * Dlo, Dr, 2 * Dlo);
+  Ws ws;
+  const CxPlanes xpl(ws, nx), gpl(ws, nG);
+  const size_t o_t1 = ws.take(slab * W);
+  if (int rc = ws.ensure(c)) return rc;
+  double* T1 = Ws::at(c, o_t1);
+  HIPCHK(xpl.split(c, cm));
+  HIPCHK(gpl.split(c, GR));
+  HIPCHK(stage1(c, W, 2 * Dlo, Dl, Dr, GL, xpl.at(c), T1, 0, 1, xpl.stride()));
+  Segs sg;
+  level_segs(sg, W, (int64_t)slab, (int64_t)Dr * Dr, nullptr, 2, gpl.stride());
+  GemmArgs g3 = mk(T1, gpl.at(c), y, 2 * Dlo, Dr, Dr, 2 * Dlo, Dr, 2 * Dlo);
   g3.cplx = 1;
-  HIPCHK(gemm_segments(g3, sa, sb, c->stream, &sj));
+  HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
 
-static int pair_plan(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, const MixPlan** out);
+static int pair_plan(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, const MixPlan** out) {
+  auto key = std::make_pair(H1, H2);
+  auto it = c->pair_plans.find(key);
+  if (it != c->pair_plans.end()) { *out = &it->second; return MPSK_OK; }
+  const int d1 = H1->d, d2 = H2->d, Wl = H1->Wl, Wm = H1->Wr, Wr = H2->Wr;
+  // O12[(t1,t2,v) <- (s1,s2,w)] = sum_u O1[w,t1,s1,u] O2[u,t2,s2,v]   (derivatives.jl:128-147)
+  std::map<std::pair<int, int>, std::pair<double, double>> acc;
+  for (int u = 0; u < Wm; ++u)
+    for (int w = 0; w < Wl; ++w)
+      for (int t1 = 0; t1 < d1; ++t1)
+        for (int s1 = 0; s1 < d1; ++s1) {
+          const double a = H1->O(w, t1, s1, u), ai = H1->Oi(w, t1, s1, u);
+          if (a == 0.0 && ai == 0.0) continue;
+          for (int v = 0; v < Wr; ++v)
+            for (int t2 = 0; t2 < d2; ++t2)
+              for (int s2 = 0; s2 < d2; ++s2) {
+                const double b = H2->O(u, t2, s2, v), bi = H2->Oi(u, t2, s2, v);
+                if (b == 0.0 && bi == 0.0) continue;
+                int o = t1 + d1 * (t2 + d2 * v), in = s1 + d1 * (s2 + d2 * w);
+                auto& e = acc[{o, in}];
+                e.first += a * b - ai * bi;
+                e.second += a * bi + ai * b;
+              }
+        }
+  std::vector<MixTerm> terms;
+  for (auto& kv : acc)
+    if (kv.second.first != 0.0 || kv.second.second != 0.0)
+      terms.push_back({kv.first.first, kv.first.second, kv.second.first, kv.second.second});
+  MixPlan p;
+  HIPCHK(mix_plan_create(terms, d1 * d2 * Wr, d1 * d2 * Wl, &p));
+  auto res = c->pair_plans.emplace(key, p);
+  *out = &res.first->second;
+  return MPSK_OK;
+}
 
 // x2: [Dl, d1, Dr, d2]; GR: Wr slabs [Dr, Dro]; y2: [Dlo, d1, Dro, d2] (Dro = Dr: mpsk_dAC2)
 static int dAC2_c128(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dlo, int Dl, int Dr, int Dro,
@@ -703,61 +806,46 @@ static int dAC2_c128(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* 
   const int d1 = H1->d, d2 = H2->d, Wl = H1->Wl, Wr = H2->Wr;
   const size_t nx = (size_t)Dl * d1 * Dr * d2, nG = (size_t)Wr * Dr * Dro;
   const size_t plane = (size_t)2 * Dlo * d1 * Dr, slab = plane * d2, oplane = (size_t)2 * Dlo * d1 * Dro;
-  const size_t o_g = 2 * ev2(nx), o_t1 = o_g + 2 * ev2(nG), o_t2 = o_t1 + slab * Wl;
-  if (int rc = ensure_ws(c, sizeof(double) * (o_t2 + slab * Wr))) return rc;
-  double* xp = (double*)c->ws;
-  double* g = xp + o_g;
-  double* T1 = xp + o_t1;
-  double* T2 = xp + o_t2;
+  Ws ws;
+  const CxPlanes xpl(ws, nx), gpl(ws, nG);
+  const size_t o_t1 = ws.take(slab * Wl), o_t2 = ws.take(slab * Wr);
+  if (int rc = ws.ensure(c)) return rc;
+  double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
   const MixPlan* plan = nullptr;
   if (int rc = pair_plan(c, H1, H2, &plan)) return rc;
-  HIPCHK(cx_planes(x2, nx, xp, xp + ev2(nx), c->stream));
-  HIPCHK(cx_planes(GR, nG, g, g + ev2(nG), c->stream));
-  GemmArgs g1 = mk(GL, xp, T1, 2 * Dlo, d1 * Dr * d2, Dl, 2 * Dlo, Dl, 2 * Dlo);
-  g1.batch = Wl; g1.bsA = (int64_t)2 * Dlo * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
-  g1.nseg = 2; g1.segB[1] = (int64_t)ev2(nx); g1.segJ[1] = 1; g1.cplx = 1;
-  HIPCHK(gemm_f64(g1, c->stream));
+  HIPCHK(xpl.split(c, x2));
+  HIPCHK(gpl.split(c, GR));
+  HIPCHK(stage1(c, Wl, 2 * Dlo, Dl, d1 * Dr * d2, GL, xpl.at(c), T1, 0, 1, xpl.stride()));
   SlabIndex ix{d1, d2, (int64_t)2 * Dlo, (int64_t)plane, (int64_t)slab, (int64_t)2 * Dlo * d1};
   HIPCHK(mix_apply(*plan, T1, ix, T2, ix, 2 * Dlo, Dr, c->stream));
-  std::vector<int64_t> sa, sb;
-  std::vector<int> sj;
-  for (int v = 0; v < Wr; ++v)
-    if (H2->col_used[v])
-      for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)v * slab); sb.push_back((int64_t)(pl * ev2(nG) + (size_t)v * Dr * Dro)); sj.push_back(pl); }
-  if (sa.empty()) { HIPCHK(zero_async(y2, sizeof(double) * oplane * d2, c->stream)); return MPSK_OK; }
-  GemmArgs g3 = mk(T2, g, y2, 2 * Dlo * d1, Dro, Dr, (int64_t)2 * Dlo * d1, Dr, (int64_t)2 * Dlo * d1);
+  Segs sg;
+  if (!level_segs(sg, Wr, (int64_t)slab, (int64_t)Dr * Dro, &H2->col_used, 2, gpl.stride()))
+    return zero_fill(c, y2, sizeof(double) * oplane * d2);
+  GemmArgs g3 = mk(T2, gpl.at(c), y2, 2 * Dlo * d1, Dro, Dr, (int64_t)2 * Dlo * d1, Dr, (int64_t)2 * Dlo * d1);
   g3.batch = d2; g3.bsA = (int64_t)plane; g3.bsB = 0; g3.bsC = (int64_t)oplane; g3.cplx = 1;
-  HIPCHK(gemm_segments(g3, sa, sb, c->stream, &sj));
+  HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
 
 // GLout[v][q,b] = sum GLin[w][p,a] A[a,s,b] O[w,t,s,v] conj(Ab[p,t,q])
 // gram (pass-through only, Dr == Drb): gram[w][t,s] = sum conj(Ab[p,t,b]) T1[w][p,s,b] of the stage-1 product, partials
 // after T1 in the workspace; GLout == nullptr then skips stage 2 (mpsk_transfer_left_gram)
-static int transfer_left_c128(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
+static int transfer_left_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr, int d, int Dl, int Dr, int Dlb, int Drb,
                               const double* GLin, const double* A, const double* Ab, double* GLout,
                               double* gram = nullptr) {
   HIPCHK(hipSetDevice(c->device));
-  int Wl = W, Wr = W;
-  if (H) { Wl = H->Wl; Wr = H->Wr; d = H->d; }
   const size_t nA = (size_t)Dl * d * Dr, slab = (size_t)2 * Dlb * d * Dr;
-  const size_t o_t1 = 2 * ev2(nA), o_t2 = o_t1 + slab * Wl;
-  if (int rc = ensure_ws(c, sizeof(double) * (o_t2 + (H ? slab * Wr : 0) + (gram ? site_gram_partial_doubles(Wl, d, true) : 0))))
-    return rc;
-  double* Ap = (double*)c->ws;
-  double* T1 = Ap + o_t1;
-  double* T2 = H ? Ap + o_t2 : T1;
-  HIPCHK(cx_planes(A, nA, Ap, Ap + ev2(nA), c->stream));
-  // T1[w] = GLin[w] A      (2 Dlb x d Dr, rows interleaved)
-  GemmArgs g1 = mk(GLin, Ap, T1, 2 * Dlb, d * Dr, Dl, 2 * Dlb, Dl, 2 * Dlb);
-  g1.batch = Wl; g1.bsA = (int64_t)2 * Dlb * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
-  g1.nseg = 2; g1.segB[1] = (int64_t)ev2(nA); g1.segJ[1] = 1; g1.cplx = 1;
-  HIPCHK(gemm_f64(g1, c->stream));
-  if (H) {
-    SlabIndex ix{d, 1 << 30, (int64_t)2 * Dlb, (int64_t)slab, 0, (int64_t)2 * Dlb * d};
-    HIPCHK(mix_apply(H->fwd, T1, ix, T2, ix, 2 * Dlb, Dr, c->stream));
-  }
-  if (gram) HIPCHK(site_gram(Wl, d, Dlb, Dr, T1, Ab, true, gram, Ap + o_t2, c->stream));
+  Ws ws;
+  const CxPlanes apl(ws, nA);
+  const size_t o_t1 = ws.take(slab * Wl), o_t2 = ws.take(H ? slab * Wr : 0);
+  const size_t o_part = ws.take(gram ? site_gram_partial_doubles(Wl, d, true) : 0);     // H == NULL: straight after T1
+  if (int rc = ws.ensure(c)) return rc;
+  double* T1 = Ws::at(c, o_t1);
+  double* T2 = H ? Ws::at(c, o_t2) : T1;
+  HIPCHK(apl.split(c, A));
+  HIPCHK(stage1(c, Wl, 2 * Dlb, Dl, d * Dr, GLin, apl.at(c), T1, 0, 1, apl.stride()));      // T1[w] = GLin[w] A, rows interleaved
+  if (H) HIPCHK(mix_levels(c, H->fwd, d, 2 * Dlb, Dr, T1, T2));
+  if (gram) HIPCHK(site_gram(Wl, d, Dlb, Dr, T1, Ab, true, gram, Ws::at(c, o_part), c->stream));
   if (!GLout) return MPSK_OK;
   // GLout[v] = Ab^H T2[v]:  K = (re / im, p, t) interleaved on both operands ->  real part = Ab_half^T T2_half,
   // imaginary part = (J Ab_half)^T T2_half ; plane alpha goes to the rows 2 q + alpha of the interleaved result
@@ -771,33 +859,27 @@ static int transfer_left_c128(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d,
 }
 
 // GRout[w][a,p] = sum A[a,s,b] O[w,t,s,v] conj(Ab[p,t,q]) GRin[v][b,q]   evaluated as  ((A GRin) mixed) Ab^H
-static int transfer_right_c128(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
+static int transfer_right_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr, int d, int Dl, int Dr, int Dlb, int Drb,
                                const double* A, const double* Ab, const double* GRin, double* GRout) {
   HIPCHK(hipSetDevice(c->device));
-  int Wl = W, Wr = W;
-  if (H) { Wl = H->Wl; Wr = H->Wr; d = H->d; }
   const size_t nG = (size_t)Wr * Dr * Drb, nB = (size_t)Dlb * d * Drb, slab = (size_t)2 * Dl * d * Drb;
-  const size_t o_b = 2 * ev2(nG), o_x = o_b + 2 * ev2(nB), o_y = o_x + slab * Wr;
-  if (int rc = ensure_ws(c, sizeof(double) * (o_y + (H ? slab * Wl : 0)))) return rc;
-  double* Gp = (double*)c->ws;
-  double* Bp = Gp + o_b;
-  double* X = Gp + o_x;
-  double* Y = H ? Gp + o_y : X;
-  HIPCHK(cx_planes(GRin, nG, Gp, Gp + ev2(nG), c->stream));
-  HIPCHK(cx_planes(Ab, nB, Bp, Bp + ev2(nB), c->stream));
+  Ws ws;
+  const CxPlanes gpl(ws, nG), bpl(ws, nB);
+  const size_t o_x = ws.take(slab * Wr), o_y = ws.take(H ? slab * Wl : 0);
+  if (int rc = ws.ensure(c)) return rc;
+  double *X = Ws::at(c, o_x), *Y = H ? Ws::at(c, o_y) : X;
+  HIPCHK(gpl.split(c, GRin));
+  HIPCHK(bpl.split(c, Ab));
   // X[v][a,s,q] = sum_b A[a,s,b] GRin[v][b,q]      A as the (2 Dl d) x Dr interleaved matrix
-  GemmArgs g1 = mk(A, Gp, X, 2 * Dl * d, Drb, Dr, (int64_t)2 * Dl * d, Dr, (int64_t)2 * Dl * d);
+  GemmArgs g1 = mk(A, gpl.at(c), X, 2 * Dl * d, Drb, Dr, (int64_t)2 * Dl * d, Dr, (int64_t)2 * Dl * d);
   g1.batch = Wr; g1.bsA = 0; g1.bsB = (int64_t)Dr * Drb; g1.bsC = (int64_t)slab;
-  g1.nseg = 2; g1.segB[1] = (int64_t)ev2(nG); g1.segJ[1] = 1; g1.cplx = 1;
+  cx_operand(g1, gpl.stride());
   HIPCHK(gemm_f64(g1, c->stream));
-  if (H) {   // Y[w][a,t,q] = sum_{v,s} O[w,t,s,v] X[v][a,s,q]
-    SlabIndex ix{d, 1 << 30, (int64_t)2 * Dl, (int64_t)slab, 0, (int64_t)2 * Dl * d};
-    HIPCHK(mix_apply(H->rgt, X, ix, Y, ix, 2 * Dl, Drb, c->stream));
-  }
+  if (H) HIPCHK(mix_levels(c, H->rgt, d, 2 * Dl, Drb, X, Y));      // Y[w][a,t,q] = sum_{v,s} O[w,t,s,v] X[v][a,s,q]
   // GRout[w][a,p] = sum_{t,q} Y[w][a,(t,q)] conj(Ab[p,(t,q)]) = Y_half Abr^T + (-J Y_half) Abi^T
-  GemmArgs g3 = mk(Y, Bp, GRout, 2 * Dl, Dlb, d * Drb, (int64_t)2 * Dl, Dlb, (int64_t)2 * Dl, 0, 1);
+  GemmArgs g3 = mk(Y, bpl.at(c), GRout, 2 * Dl, Dlb, d * Drb, (int64_t)2 * Dl, Dlb, (int64_t)2 * Dl, 0, 1);
   g3.batch = Wl; g3.bsA = (int64_t)slab; g3.bsB = 0; g3.bsC = (int64_t)2 * Dl * Dlb;
-  g3.nseg = 2; g3.segB[1] = (int64_t)ev2(nB); g3.segJ[1] = 2; g3.cplx = 1;
+  cx_operand(g3, bpl.stride(), 2);
   HIPCHK(gemm_f64(g3, c->stream));
   return MPSK_OK;
 }
@@ -810,27 +892,20 @@ static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t slab = (size_t)Dlo * d * Dr;
-  if (int rc = ensure_ws(c, sizeof(double) * slab * (Wl + Wr))) return rc;
-  double* T1 = (double*)c->ws;
-  double* T2 = T1 + slab * Wl;
+  Ws ws;
+  const size_t o_t1 = ws.take(slab * Wl), o_t2 = ws.take(slab * Wr);
+  if (int rc = ws.ensure(c)) return rc;
+  double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
   // stage 1: T1[w] = GL[w] * x     (batched over w)
-  const int kb = Dl / nblk;
-  GemmArgs g1 = mk((const double*)GL, (const double*)x, T1, Dlo, d * Dr, kb, Dlo, kb, Dlo);
-  g1.batch = Wl; g1.bsA = (int64_t)Dlo * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
-  g1.nseg = nblk;
-  for (int q = 0; q < nblk; ++q) { g1.segA[q] = (int64_t)q * kb * Dlo; g1.segB[q] = (int64_t)q * kb * d * Dr; }
-  g1.tag = 1;
-  HIPCHK(gemm_f64(g1, c->stream));
+  HIPCHK(stage1(c, Wl, Dlo, Dl, d * Dr, (const double*)GL, (const double*)x, T1, 1, nblk));
   // stage 2: T2[v][:,t,:] = sum_{w,s} O[w,t,s,v] T1[w][:,s,:]
-  SlabIndex ix{d, 1 << 30, (int64_t)Dlo, (int64_t)slab, 0, (int64_t)Dlo * d};
-  HIPCHK(mix_apply(H->fwd, T1, ix, T2, ix, Dlo, Dr, c->stream));
+  HIPCHK(mix_levels(c, H->fwd, d, Dlo, Dr, T1, T2));
   // stage 3: y = sum_v T2[v] * GR[v]   (K-segments over v)
-  std::vector<int64_t> sa, sb;
-  for (int v = 0; v < Wr; ++v) if (H->col_used[v]) { sa.push_back((int64_t)v * slab); sb.push_back((int64_t)v * Dr * Dro); }
-  if (sa.empty()) { HIPCHK(zero_async(y, sizeof(double) * Dlo * d * Dro, c->stream)); return MPSK_OK; }
+  Segs sg;
+  if (!level_segs(sg, Wr, (int64_t)slab, (int64_t)Dr * Dro, &H->col_used)) return zero_fill(c, y, sizeof(double) * Dlo * d * Dro);
   GemmArgs g3 = mk(T2, (const double*)GR, (double*)y, Dlo * d, Dro, Dr, (int64_t)Dlo * d, Dr, (int64_t)Dlo * d);
   g3.tag = 1;
-  HIPCHK(gemm_segments(g3, sa, sb, c->stream));
+  HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
 
@@ -855,21 +930,19 @@ static bool dense_route(const mpsk_mposlice* H) {
   return std::min(H->Wl, H->Wr) * H->d >= MPSK_DENSE_MIN_CHID;
 }
 
-// device table [2][Wl d]: tab[z] = w P, tab[Wl d + z] = s Q for z = s + d w (stage-1 batch offsets of GL / x)
-static int dense_tab(const mpsk_mposlice* H, int64_t P, int64_t Q, const int64_t** out) {
+// device tables [2][W d] of a stage 1 batched over z = s + d w, cached on the slice per (P, Q).  Left (W = Wl, offsets of
+// GL / x): tab[z] = w P, tab[W d + z] = s Q.  Right (W = Wr, offsets of the site tensor / GR): tab[z] = s P, tab[W d + z] = v Q.
+static int dense_tab(const mpsk_mposlice* H, bool right, int64_t P, int64_t Q, const int64_t** out) {
+  auto& cache = right ? H->dtabR : H->dtab;
   auto key = std::make_pair(P, Q);
-  auto it = H->dtab.find(key);
-  if (it != H->dtab.end()) { *out = it->second; return MPSK_OK; }
-  const int nz = H->Wl * H->d;
+  auto it = cache.find(key);
+  if (it != cache.end()) { *out = it->second; return MPSK_OK; }
+  const int d = H->d, nz = (right ? H->Wr : H->Wl) * d;
   std::vector<int64_t> h((size_t)2 * nz);
-  for (int z = 0; z < nz; ++z) { h[z] = (int64_t)(z / H->d) * P; h[nz + z] = (int64_t)(z % H->d) * Q; }
+  for (int z = 0; z < nz; ++z) { h[z] = (int64_t)(right ? z % d : z / d) * P; h[nz + z] = (int64_t)(right ? z / d : z % d) * Q; }
   int64_t* p = nullptr;
-  if (hipMalloc(&p, sizeof(int64_t) * h.size()) != hipSuccess) return fail(MPSK_ERR_NOMEM, "dense offset table hipMalloc failed");
-  if (hipMemcpy(p, h.data(), sizeof(int64_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(p);
-    return fail(MPSK_ERR_HIP, "dense offset table upload failed");
-  }
-  H->dtab.emplace(key, p);
+  if (int rc = upload_table(h, "dense offset table", &p)) return rc;
+  cache.emplace(key, p);
   *out = p;
   return MPSK_OK;
 }
@@ -878,7 +951,7 @@ static int dense_tab(const mpsk_mposlice* H, int64_t P, int64_t Q, const int64_t
 static int dense_stage1(mpsk_ctx* c, const mpsk_mposlice* H, int R, int Dk, int Nb, const double* G, const double* X, double* T) {
   const int d = H->d;
   const int64_t* tab = nullptr;
-  if (int rc = dense_tab(H, (int64_t)R * Dk, Dk, &tab)) return rc;
+  if (int rc = dense_tab(H, false, (int64_t)R * Dk, Dk, &tab)) return rc;
   GemmArgs g1 = mk(G, X, T, R, Nb, Dk, R, (int64_t)Dk * d, R);
   g1.batch = H->Wl * d; g1.bsC = (int64_t)R * Nb;
   g1.tabA = tab; g1.tabB = tab + (size_t)H->Wl * d;
@@ -902,19 +975,19 @@ static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int D
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t slab = (size_t)Dlo * Dr;               // one (s,w) / (t,v) column of the intermediates
-  if (int rc = ensure_ws(c, sizeof(double) * slab * d * (Wl + Wr))) return rc;
-  double* T1 = (double*)c->ws;
-  double* T2 = T1 + slab * d * Wl;
+  Ws ws;
+  const size_t o_t1 = ws.take(slab * d * Wl), o_t2 = ws.take(slab * d * Wr);
+  if (int rc = ws.ensure(c)) return rc;
+  double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
   if (int rc = dense_stage1(c, H, Dlo, Dl, Dr, GL, x, T1)) return rc;
   if (int rc = dense_stage2(c, H, (int64_t)slab, T1, T2)) return rc;
   // stage 3: y[:, t, :] = sum_v T2[:, :, t, v] GR[v]    (batch over t; K-segments over v)
-  std::vector<int64_t> sa, sb;
-  for (int v = 0; v < Wr; ++v) if (H->col_used[v]) { sa.push_back((int64_t)v * d * slab); sb.push_back((int64_t)v * Dr * Dro); }
-  if (sa.empty()) { HIPCHK(zero_async(y, sizeof(double) * Dlo * d * Dro, c->stream)); return MPSK_OK; }
+  Segs sg;
+  if (!level_segs(sg, Wr, (int64_t)d * slab, (int64_t)Dr * Dro, &H->col_used)) return zero_fill(c, y, sizeof(double) * Dlo * d * Dro);
   GemmArgs g3 = mk(T2, GR, y, Dlo, Dro, Dr, Dlo, Dr, (int64_t)Dlo * d);
   g3.batch = d; g3.bsA = (int64_t)slab; g3.bsB = 0; g3.bsC = Dlo;
   g3.tag = 1;
-  HIPCHK(gemm_segments(g3, sa, sb, c->stream));
+  HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
 
@@ -923,20 +996,22 @@ static int transfer_left_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int 
                                const double* A, const double* Ab, double* GLout) {
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t slab = (size_t)Dlb * Dr;
-  if (int rc = ensure_ws(c, sizeof(double) * slab * d * (Wl + Wr))) return rc;
-  double* T1 = (double*)c->ws;
-  double* T2 = T1 + slab * d * Wl;
+  Ws ws;
+  const size_t o_t1 = ws.take(slab * d * Wl), o_t2 = ws.take(slab * d * Wr);
+  if (int rc = ws.ensure(c)) return rc;
+  double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
   if (int rc = dense_stage1(c, H, Dlb, Dl, Dr, GLin, A, T1)) return rc;
   if (int rc = dense_stage2(c, H, (int64_t)slab, T1, T2)) return rc;
   // GLout[v][q,b] = sum_t sum_p Ab[p,t,q] T2[(p,b), (t,v)]     (batch over v; K-segments over t)
-  std::vector<int64_t> sa, sb;
-  for (int t = 0; t < d; ++t) { sa.push_back((int64_t)t * Dlb); sb.push_back((int64_t)t * slab); }
+  Segs sg;
+  phys_segs(sg, d, Dlb, (int64_t)slab);
   GemmArgs g3 = mk(Ab, T2, GLout, Drb, Dr, Dlb, (int64_t)Dlb * d, Dlb, Drb, 1, 0);
   g3.batch = Wr; g3.bsA = 0; g3.bsB = (int64_t)slab * d; g3.bsC = (int64_t)Drb * Dr;
-  HIPCHK(gemm_segments(g3, sa, sb, c->stream));
+  HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
 
+extern "C" {
 int mpsk_dAC(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
              const void* x, void* y) {
   REQUIRE(c && H && GL && GR && x && y, "NULL argument");
@@ -970,6 +1045,8 @@ int mpsk_dAC_proj(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, 
   if (dense_route(H)) return dAC_dense(c, H, Dlo, Dl, Dr, Dro, (const double*)GL, (const double*)GR, (const double*)x, (double*)y);
   return dAC_impl(c, H, Dlo, Dl, Dr, Dro, GL, GR, x, 1, y);
 }
+
+}  // extern "C"
 
 // ---- prepared operator ---------------------------------------------------------------------------
 static int pool_take(mpsk_ctx* c, size_t bytes, void** p, int* idx) {
@@ -1048,6 +1125,7 @@ static hipError_t hac_jordan_prepare(mpsk_ctx* c, mpsk_hac* h, const double* GL,
   return e;
 }
 
+extern "C" {
 int mpsk_hac_create(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
                     mpsk_hac** out) {
   return mpsk_hac_create_ex(c, H, Dlo, Dl, Dr, GL, GR, 0, out);
@@ -1073,7 +1151,7 @@ int mpsk_hac_create_ex(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int
   h->ctx = c; h->H = H; h->Dlo = Dlo; h->Dl = Dl; h->Dr = Dr; h->GL = (const double*)GL; h->GR = (const double*)GR;
   // Jordan form: only on the caller's promise that level 0 of GL and level W-1 of GR are identities
   const bool jordan = (flags & MPSK_HAC_CANONICAL) && H->jordan && H->dtype == MPSK_F64 && Dlo == Dl;
-  if (jordan && getenv("MPSK_HAC_CHECK") && getenv("MPSK_HAC_CHECK")[0] == '1') {
+  if (jordan && hac_check_on()) {
     double dl = 0.0, dr = 0.0;
     int rc = identity_deviation(c, (const double*)GL, Dl, &dl);
     if (!rc) rc = identity_deviation(c, (const double*)GR + (size_t)(Wr - 1) * Dr * Dr, Dr, &dr);
@@ -1106,7 +1184,7 @@ int mpsk_hac_create_ex(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int
       HIPCHK(hipStreamSynchronize(c->stream));
       for (int i = 0; i < nbk; ++i) { dl = std::max(dl, c->h_scal[i]); dr = std::max(dr, c->h_scal[nbk + i]); }
       if (!(dl <= 1e-10 && dr <= 1e-10)) {
-        if (getenv("MPSK_HAC_CHECK") && getenv("MPSK_HAC_CHECK")[0] == '1') {
+        if (hac_check_on()) {
           delete h;
           char msg[160];
           snprintf(msg, sizeof(msg), "MPSK_HAC_CHECK: environments are not canonical (max|GL[0] - I| = %.3e, max|GR[W-1] - I| = %.3e)", dl, dr);
@@ -1154,8 +1232,7 @@ int mpsk_hac_create_ex(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int
     // forces the two-launch form (A/B switch)
     const char* ev = getenv("MPSK_HAC_LAUNCHES");
     h->launches = (Dl == Dr && !(ev && ev[0] == '2')) ? 1 : 2;
-    auto up = [](size_t n) { return (n + 31) & ~(size_t)31; };      // 256-B aligned parts
-    const size_t nR = up((size_t)d * d * Dr * Dr), nL = up((size_t)d * d * Dlo * Dl);
+    const size_t nR = up32((size_t)d * d * Dr * Dr), nL = up32((size_t)d * d * Dlo * Dl);      // 256-B aligned parts
     const size_t bytes = sizeof(double) * (nR + nL) + sizeof(int64_t) * 2 * d * (H->jr_nseg + H->jl_nseg);
     void* buf = nullptr;
     if (int rc = pool_take(c, bytes, &buf, &h->pool_idx)) { delete h; return rc; }
@@ -1226,6 +1303,8 @@ int mpsk_hac_info(const mpsk_hac* h, int* mode, int* nslabs) {
   return MPSK_OK;
 }
 
+}  // extern "C"
+
 // complex mode 3: y[:, t, :] = sum_s x[:, s, :] GRc0[(s, t)] + sum_s GLc[(s, t)] x[:, s, :], two launches batched over t with
 // all d values of s as K-segments (re and im plane of the B operand each, the second through the J loader): 16 d^2 D^3
 // real flops, against 16 (Wl + Wr) d D^3 of the mix form
@@ -1234,27 +1313,25 @@ static int hac_apply_jordan_c128(mpsk_hac* h, const double* x, double* y) {
   const int d = h->H->d, Dlo = h->Dlo, Dl = h->Dl, Dr = h->Dr;
   HIPCHK(hipSetDevice(c->device));
   const size_t nx = (size_t)Dl * d * Dr, nR = (size_t)d * d * Dr * Dr;
-  if (int rc = ensure_ws(c, sizeof(double) * 2 * ev2(nx))) return rc;
-  double* xp = (double*)c->ws;
-  HIPCHK(cx_planes(x, nx, xp, xp + ev2(nx), c->stream));
-  std::vector<int64_t> sa, sb;
-  std::vector<int> sj;
-  for (int si = 0; si < d; ++si)
-    for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)si * 2 * Dl); sb.push_back((int64_t)(pl * ev2(nR) + (size_t)si * Dr * Dr)); sj.push_back(pl); }
+  Ws ws;
+  const CxPlanes xpl(ws, nx);
+  if (int rc = ws.ensure(c)) return rc;
+  HIPCHK(xpl.split(c, x));
+  Segs s1, s2;      // over the physical index s, both planes of the B operand
+  level_segs(s1, d, (int64_t)2 * Dl, (int64_t)Dr * Dr, nullptr, 2, (int64_t)ev2(nR));
   GemmArgs g1 = mk(x, h->GRc, y, 2 * Dlo, Dr, Dr, (int64_t)2 * Dl * d, Dr, (int64_t)2 * Dlo * d);
   g1.batch = d; g1.bsA = 0; g1.bsB = (int64_t)d * Dr * Dr; g1.bsC = (int64_t)2 * Dlo;
   g1.cplx = 1;
-  HIPCHK(gemm_segments(g1, sa, sb, c->stream, &sj));
-  sa.clear(); sb.clear(); sj.clear();
-  for (int si = 0; si < d; ++si)
-    for (int pl = 0; pl < 2; ++pl) { sa.push_back((int64_t)si * 2 * Dlo * Dl); sb.push_back((int64_t)(pl * ev2(nx) + (size_t)si * Dl)); sj.push_back(pl); }
-  GemmArgs g2 = mk(h->GLc, xp, y, 2 * Dlo, Dr, Dl, (int64_t)2 * Dlo, (int64_t)Dl * d, (int64_t)2 * Dlo * d);
+  HIPCHK(gemm_segments(g1, s1, c->stream));
+  level_segs(s2, d, (int64_t)2 * Dlo * Dl, Dl, nullptr, 2, xpl.stride());
+  GemmArgs g2 = mk(h->GLc, xpl.at(c), y, 2 * Dlo, Dr, Dl, (int64_t)2 * Dlo, (int64_t)Dl * d, (int64_t)2 * Dlo * d);
   g2.batch = d; g2.bsA = (int64_t)d * 2 * Dlo * Dl; g2.bsB = 0; g2.bsC = (int64_t)2 * Dlo;
   g2.cplx = 1; g2.beta = 1.0;
-  HIPCHK(gemm_segments(g2, sa, sb, c->stream, &sj));
+  HIPCHK(gemm_segments(g2, s2, c->stream));
   return MPSK_OK;
 }
 
+extern "C" {
 int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
   REQUIRE(h && x && y, "NULL argument");
   mpsk_ctx* c = h->ctx;
@@ -1300,16 +1377,12 @@ int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
   }
   const int d = H->d, Wl = H->Wl, ns = H->rc_nseg;
   const size_t slab = (size_t)Dlo * d * Dr;
-  if (int rc = ensure_ws(c, sizeof(double) * slab * Wl)) return rc;
-  double* T1 = (double*)c->ws;
+  Ws ws;
+  const size_t o_t1 = ws.take(slab * Wl);
+  if (int rc = ws.ensure(c)) return rc;
+  double* T1 = Ws::at(c, o_t1);
   // stage 1: T1[w] = GL[w] * x     (batched over w; x possibly in row blocks = K segments)
-  const int kb = Dl / nblk;
-  GemmArgs g1 = mk(h->GL, (const double*)x, T1, Dlo, d * Dr, kb, Dlo, kb, Dlo);
-  g1.batch = Wl; g1.bsA = (int64_t)Dlo * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
-  g1.nseg = nblk;
-  for (int q = 0; q < nblk; ++q) { g1.segA[q] = (int64_t)q * kb * Dlo; g1.segB[q] = (int64_t)q * kb * d * Dr; }
-  g1.tag = 1;
-  HIPCHK(gemm_f64(g1, c->stream));
+  HIPCHK(stage1(c, Wl, Dlo, Dl, d * Dr, h->GL, (const double*)x, T1, 1, nblk));
   // stage 3: y[:, t, :] = sum_{c: t_c = t} T1[w_c][:, s_c, :] GRc[c]      (batch over t, per-batch K-segment tables)
   GemmArgs g3 = mk(T1, h->GRc, (double*)y, Dlo, Dr, Dr, (int64_t)Dlo * d, Dr, (int64_t)Dlo * d);
   g3.batch = d; g3.bsA = 0; g3.bsB = 0; g3.bsC = (int64_t)Dlo;
@@ -1375,26 +1448,28 @@ int mpsk_hac_eigsolve_fixed(mpsk_hac* h, const void* x0, int m, void* const* V, 
   return mpsk_vnormalize_dev(c, n, V[m + 1], y, nullptr);
 }
 
+}  // extern "C"
+
 // y = sum_w GL[w] c GR[w] with GR slabs [Dr, Dro]: one batched GEMM T[w] = GL[w] c, then the segmented-K GEMM over (w, b).
 // mpsk_dC passes Dro = Dr, mpsk_dC_proj the bond dimension of the state below.
 static int dC_f64(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, int Dro, const double* GL, const double* GR, const double* cm,
                   double* y) {
   HIPCHK(hipSetDevice(c->device));
   const size_t slab = (size_t)Dlo * Dr;
-  if (int rc = ensure_ws(c, sizeof(double) * slab * W)) return rc;
-  double* T1 = (double*)c->ws;
-  GemmArgs g1 = mk(GL, cm, T1, Dlo, Dr, Dl, Dlo, Dl, Dlo);
-  g1.batch = W; g1.bsA = (int64_t)Dlo * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
-  g1.tag = 1;
-  HIPCHK(gemm_f64(g1, c->stream));
-  std::vector<int64_t> sa, sb;
-  for (int w = 0; w < W; ++w) { sa.push_back((int64_t)w * slab); sb.push_back((int64_t)w * Dr * Dro); }
+  Ws ws;
+  const size_t o_t1 = ws.take(slab * W);
+  if (int rc = ws.ensure(c)) return rc;
+  double* T1 = Ws::at(c, o_t1);
+  HIPCHK(stage1(c, W, Dlo, Dl, Dr, GL, cm, T1, 1));
+  Segs sg;
+  level_segs(sg, W, (int64_t)slab, (int64_t)Dr * Dro);
   GemmArgs g3 = mk(T1, GR, y, Dlo, Dro, Dr, Dlo, Dr, Dlo);
   g3.tag = 1;
-  HIPCHK(gemm_segments(g3, sa, sb, c->stream));
+  HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
 
+extern "C" {
 int mpsk_dC(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, const void* GL, const void* GR, const void* cm, void* y) {
   REQUIRE(c && GL && GR && cm && y, "NULL argument");
   REQUIRE(W > 0 && Dlo > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
@@ -1413,41 +1488,6 @@ int mpsk_dC_proj(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, int Dro, const voi
   return dC_f64(c, W, Dlo, Dl, Dr, Dro, (const double*)GL, (const double*)GR, (const double*)cm, (double*)y);
 }
 
-static int pair_plan(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, const MixPlan** out) {
-  auto key = std::make_pair(H1, H2);
-  auto it = c->pair_plans.find(key);
-  if (it != c->pair_plans.end()) { *out = &it->second; return MPSK_OK; }
-  const int d1 = H1->d, d2 = H2->d, Wl = H1->Wl, Wm = H1->Wr, Wr = H2->Wr;
-  // O12[(t1,t2,v) <- (s1,s2,w)] = sum_u O1[w,t1,s1,u] O2[u,t2,s2,v]   (derivatives.jl:128-147)
-  std::map<std::pair<int, int>, std::pair<double, double>> acc;
-  for (int u = 0; u < Wm; ++u)
-    for (int w = 0; w < Wl; ++w)
-      for (int t1 = 0; t1 < d1; ++t1)
-        for (int s1 = 0; s1 < d1; ++s1) {
-          const double a = H1->O(w, t1, s1, u), ai = H1->Oi(w, t1, s1, u);
-          if (a == 0.0 && ai == 0.0) continue;
-          for (int v = 0; v < Wr; ++v)
-            for (int t2 = 0; t2 < d2; ++t2)
-              for (int s2 = 0; s2 < d2; ++s2) {
-                const double b = H2->O(u, t2, s2, v), bi = H2->Oi(u, t2, s2, v);
-                if (b == 0.0 && bi == 0.0) continue;
-                int o = t1 + d1 * (t2 + d2 * v), in = s1 + d1 * (s2 + d2 * w);
-                auto& e = acc[{o, in}];
-                e.first += a * b - ai * bi;
-                e.second += a * bi + ai * b;
-              }
-        }
-  std::vector<MixTerm> terms;
-  for (auto& kv : acc)
-    if (kv.second.first != 0.0 || kv.second.second != 0.0)
-      terms.push_back({kv.first.first, kv.first.second, kv.second.first, kv.second.second});
-  MixPlan p;
-  HIPCHK(mix_plan_create(terms, d1 * d2 * Wr, d1 * d2 * Wl, &p));
-  auto res = c->pair_plans.emplace(key, p);
-  *out = &res.first->second;
-  return MPSK_OK;
-}
-
 int mpsk_dAC2(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dlo, int Dl, int Dr,
               const void* GL, const void* GR, const void* x2, void* y2) {
   REQUIRE(c && H1 && H2 && GL && GR && x2 && y2, "NULL argument");
@@ -1460,26 +1500,25 @@ int mpsk_dAC2(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int
   const int d1 = H1->d, d2 = H2->d, Wl = H1->Wl, Wr = H2->Wr;
   const size_t plane = (size_t)Dlo * d1 * Dr;      // one s2-plane
   const size_t slab = plane * d2;                  // one w
-  if (int rc = ensure_ws(c, sizeof(double) * slab * (Wl + Wr))) return rc;
-  double* T1 = (double*)c->ws;
-  double* T2 = T1 + slab * Wl;
+  Ws ws;
+  const size_t o_t1 = ws.take(slab * Wl), o_t2 = ws.take(slab * Wr);
+  if (int rc = ws.ensure(c)) return rc;
+  double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
   const MixPlan* plan = nullptr;
   if (int rc = pair_plan(c, H1, H2, &plan)) return rc;
-  GemmArgs g1 = mk((const double*)GL, (const double*)x2, T1, Dlo, d1 * Dr * d2, Dl, Dlo, Dl, Dlo);
-  g1.batch = Wl; g1.bsA = (int64_t)Dlo * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
-  g1.tag = 1;
-  HIPCHK(gemm_f64(g1, c->stream));
+  HIPCHK(stage1(c, Wl, Dlo, Dl, d1 * Dr * d2, (const double*)GL, (const double*)x2, T1, 1));
   SlabIndex ix{d1, d2, (int64_t)Dlo, (int64_t)plane, (int64_t)slab, (int64_t)Dlo * d1};
   HIPCHK(mix_apply(*plan, T1, ix, T2, ix, Dlo, Dr, c->stream));
-  std::vector<int64_t> sa, sb;
-  for (int v = 0; v < Wr; ++v) if (H2->col_used[v]) { sa.push_back((int64_t)v * slab); sb.push_back((int64_t)v * Dr * Dr); }
-  if (sa.empty()) { HIPCHK(zero_async(y2, sizeof(double) * slab, c->stream)); return MPSK_OK; }
+  Segs sg;
+  if (!level_segs(sg, Wr, (int64_t)slab, (int64_t)Dr * Dr, &H2->col_used)) return zero_fill(c, y2, sizeof(double) * slab);
   GemmArgs g3 = mk(T2, (const double*)GR, (double*)y2, Dlo * d1, Dr, Dr, (int64_t)Dlo * d1, Dr, (int64_t)Dlo * d1);
   g3.tag = 1;
   g3.batch = d2; g3.bsA = (int64_t)plane; g3.bsB = 0; g3.bsC = (int64_t)plane;
-  HIPCHK(gemm_segments(g3, sa, sb, c->stream));
+  HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
+
+}  // extern "C"
 
 // --------------------------------------------------------------------------------------------
 // transfers
@@ -1497,8 +1536,6 @@ int mpsk_dAC2(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int
 // alone, X[w][:,t,:] = sum_s O[w,t,s,W-1] A[:,s,:], level 0 from the right fold, X[0][:,t,:] = sum_s A[:,s,:] GRc0[(s,t)]
 // (start level, C blocks and the D block), and GRout[w][a,p] = sum_{t,b} X[w][a,t,b] A[p,t,b] is one batched NT GEMM.
 // MPSK_TRANSFER_MODE=0 keeps the dense three-stage route (A/B runs).
-static size_t up32(size_t n) { return (n + 31) & ~(size_t)31; }      // 256-B aligned parts of the workspace
-
 static bool transfer_canonical_ok(const mpsk_mposlice* H, int flags, const void* A, const void* Ab, int Dl, int Dr,
                                   int Dlb, int Drb) {
   if (!(flags & MPSK_TRANSFER_CANONICAL) || !H || !H->jordan || H->dtype != MPSK_F64 || dense_route(H)) return false;
@@ -1507,8 +1544,6 @@ static bool transfer_canonical_ok(const mpsk_mposlice* H, int flags, const void*
   return !(ev && ev[0] == '0');
 }
 
-static bool hac_check_on() { const char* ev = getenv("MPSK_HAC_CHECK"); return ev && ev[0] == '1'; }
-
 // MPSK_HAC_CHECK=1 (debug, synchronises): the promises behind MPSK_TRANSFER_CANONICAL -- the identity level of the input
 // environment (n x n at G) and the isometry of A on the contracted side (Gram matrix through c->ws) -- hold to 1e-10
 static int transfer_canonical_check(mpsk_ctx* c, const char* who, const double* G, int n, const double* A, int d, int Dl,
@@ -1516,16 +1551,18 @@ static int transfer_canonical_check(mpsk_ctx* c, const char* who, const double* 
   double dg = 0.0, da = 0.0;
   if (int rc = identity_deviation(c, G, n, &dg)) return rc;
   const int m = left ? Dr : Dl;
-  if (int rc = ensure_ws(c, sizeof(double) * (size_t)m * m)) return rc;
-  double* gram = (double*)c->ws;
+  Ws ws;
+  const size_t o_gram = ws.take((size_t)m * m);
+  if (int rc = ws.ensure(c)) return rc;
+  double* gram = Ws::at(c, o_gram);
   if (left) {        // A^T A over (p, t)
     GemmArgs g = mk(A, A, gram, Dr, Dr, Dl * d, (int64_t)Dl * d, (int64_t)Dl * d, Dr, 1, 0);
     HIPCHK(gemm_f64(g, c->stream));
   } else {           // A A^T over (t, b)
-    std::vector<int64_t> sa;
-    for (int t = 0; t < d; ++t) sa.push_back((int64_t)t * Dl);
+    Segs sg;
+    phys_segs(sg, d, Dl, Dl);
     GemmArgs g = mk(A, A, gram, Dl, Dl, Dr, (int64_t)Dl * d, (int64_t)Dl * d, Dl, 0, 1);
-    HIPCHK(gemm_segments(g, sa, sa, c->stream));
+    HIPCHK(gemm_segments(g, sg, c->stream));
   }
   if (int rc = identity_deviation(c, gram, m, &da)) return rc;
   if (!(dg <= 1e-10 && da <= 1e-10)) {
@@ -1552,11 +1589,7 @@ static int jordan_tab(const mpsk_mposlice* H, bool left, int Dl, int Dr, const i
       else { h[(size_t)t * n + k] = (int64_t)si * Dl; h[(size_t)(d + t) * n + k] = tt * tR + (int64_t)si * Dr; }          // A[:,s,:], GRc0[(s,tt)]
     }
   int64_t* p = nullptr;
-  if (hipMalloc(&p, sizeof(int64_t) * h.size()) != hipSuccess) return fail(MPSK_ERR_NOMEM, "transfer segment table hipMalloc failed");
-  if (hipMemcpy(p, h.data(), sizeof(int64_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(p);
-    return fail(MPSK_ERR_HIP, "transfer segment table upload failed");
-  }
+  if (int rc = upload_table(h, "transfer segment table", &p)) return rc;
   if (left) H->jtabL.emplace(Dl, p); else H->jtabR.emplace(std::make_pair((int64_t)Dl, (int64_t)Dr), p);
   *out = p;
   return MPSK_OK;
@@ -1569,12 +1602,14 @@ static int transfer_left_canonical(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, 
     if (int rc = transfer_canonical_check(c, "mpsk_transfer_left_ex", GLin, Dl, A, d, Dl, Dr, true)) return rc;
   const size_t slab = (size_t)Dl * d * Dr;                  // one level of T2
   const int64_t tL = (int64_t)Dl * d * Dl;                  // one t-group of GLc
-  const size_t nL = up32((size_t)d * tL);
-  if (int rc = ensure_ws(c, sizeof(double) * (nL + slab * (Wr - 1)))) return rc;
+  const size_t nL = (size_t)d * tL;
+  Ws ws;
+  const size_t o_glc = ws.take(nL, 32), o_t2 = ws.take(slab * (Wr - 1));
+  if (int rc = ws.ensure(c)) return rc;
   const int64_t* tab = nullptr;
   if (int rc = jordan_tab(H, true, Dl, Dr, &tab)) return rc;
-  double* GLc = (double*)c->ws;
-  double* T2 = GLc + nL;                                    // slab v - 1 for v = 1 .. Wr-1
+  double* GLc = Ws::at(c, o_glc);
+  double* T2 = Ws::at(c, o_t2);                             // slab v - 1 for v = 1 .. Wr-1
   double* T = T2 + slab * (Wr - 2);
   // GLc[(s,t)] = sum_{w>0} O[w,t,s,W-1] GLin[w]
   SlabIndex il{1 << 30, 1, (int64_t)Dl * Dl, 0, 0, (int64_t)Dl}, ol{d, 1 << 30, (int64_t)Dl, tL, 0, (int64_t)d * Dl};
@@ -1606,12 +1641,14 @@ static int transfer_right_canonical(mpsk_ctx* c, const mpsk_mposlice* H, int Dl,
       return rc;
   const size_t slab = (size_t)Dl * d * Dr;                  // one level of X
   const int64_t tR = (int64_t)Dr * d * Dr;                  // one t-group of GRc0
-  const size_t nR = up32((size_t)d * tR);
-  if (int rc = ensure_ws(c, sizeof(double) * (nR + slab * (Wl - 1)))) return rc;
+  const size_t nR = (size_t)d * tR;
+  Ws ws;
+  const size_t o_grc = ws.take(nR, 32), o_x = ws.take(slab * (Wl - 1));
+  if (int rc = ws.ensure(c)) return rc;
   const int64_t* tab = nullptr;
   if (int rc = jordan_tab(H, false, Dl, Dr, &tab)) return rc;
-  double* GRc = (double*)c->ws;
-  double* X = GRc + nR;                                     // slab w for w = 0 .. Wl-2
+  double* GRc = Ws::at(c, o_grc);
+  double* X = Ws::at(c, o_x);                               // slab w for w = 0 .. Wl-2
   // GRc0[(s,t)] = sum_v O[0,t,s,v] GRin[v]
   SlabIndex ir{1 << 30, 1, (int64_t)Dr * Dr, 0, 0, (int64_t)Dr}, orr{d, 1 << 30, (int64_t)Dr, tR, 0, (int64_t)d * Dr};
   HIPCHK(mix_apply(H->jr, GRin, ir, GRc, orr, Dr, Dr, c->stream));
@@ -1627,14 +1664,37 @@ static int transfer_right_canonical(mpsk_ctx* c, const mpsk_mposlice* H, int Dl,
   HIPCHK(gemm_f64(g, c->stream));
   HIPCHK(identity_slab(GRout + (size_t)(Wl - 1) * Dl * Dl, Dl, c->stream));
   // GRout[w][a,p] = sum_t sum_b X[w][a,t,b] A[p,t,b]     w = 0 .. Wl-2
-  std::vector<int64_t> sa;
-  for (int t = 0; t < d; ++t) sa.push_back((int64_t)t * Dl);
+  Segs sg;
+  phys_segs(sg, d, Dl, Dl);
   GemmArgs g3 = mk(X, A, GRout, Dl, Dl, Dr, (int64_t)Dl * d, (int64_t)Dl * d, Dl, 0, 1);
   g3.batch = Wl - 1; g3.bsA = (int64_t)slab; g3.bsB = 0; g3.bsC = (int64_t)Dl * Dl;
-  HIPCHK(gemm_segments(g3, sa, sa, c->stream));
+  HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
 
+// gram (pass-through only, Dr == Drb): gram[w][t,s] = sum Ab[p,t,b] T1[w][p,s,b] of the stage-1 product, partials after
+// T1 in the workspace; GLout == nullptr then skips stage 2 (mpsk_transfer_left_gram)
+static int transfer_left_f64(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr, int d, int Dl, int Dr, int Dlb, int Drb,
+                             const void* GLin, const void* A, const void* Ab, void* GLout, double* gram) {
+  const size_t slab = (size_t)Dlb * d * Dr;
+  Ws ws;
+  const size_t o_t = ws.take(slab * (Wl + (H ? Wr : 0)), gram ? 32 : 1);      // T1, then T2 when there is a mix
+  const size_t o_part = ws.take(gram ? site_gram_partial_doubles(Wl, d, false) : 0);
+  if (int rc = ws.ensure(c)) return rc;
+  double* T1 = Ws::at(c, o_t);
+  double* T2 = H ? T1 + slab * Wl : T1;
+  HIPCHK(stage1(c, Wl, Dlb, Dl, d * Dr, (const double*)GLin, (const double*)A, T1, 0));      // T1[w][p,s,b] = sum_a GLin[w][p,a] A[a,s,b]
+  if (H) HIPCHK(mix_levels(c, H->fwd, d, Dlb, Dr, T1, T2));
+  if (gram) HIPCHK(site_gram(Wl, d, Dlb, Dr, T1, (const double*)Ab, false, gram, Ws::at(c, o_part), c->stream));
+  if (!GLout) return MPSK_OK;
+  // GLout[v][q,b] = sum_{(p,t)} Ab[(p,t),q] T2[v][(p,t),b]
+  GemmArgs g3 = mk((const double*)Ab, T2, (double*)GLout, Drb, Dr, Dlb * d, (int64_t)Dlb * d, (int64_t)Dlb * d, Drb, 1, 0);
+  g3.batch = Wr; g3.bsA = 0; g3.bsB = (int64_t)slab; g3.bsC = (int64_t)Drb * Dr;
+  HIPCHK(gemm_f64(g3, c->stream));
+  return MPSK_OK;
+}
+
+extern "C" {
 int mpsk_transfer_left_ex(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
                           const void* GLin, const void* A, const void* Ab, int flags, void* GLout) {
   REQUIRE(c && GLin && A && Ab && GLout, "NULL argument");
@@ -1659,47 +1719,19 @@ int mpsk_transfer_right_ex(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, in
   return mpsk_transfer_right(c, H, W, d, Dl, Dr, Dlb, Drb, A, Ab, GRin, GRout);
 }
 
-static int transfer_left_f64(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr, int d, int Dl, int Dr, int Dlb, int Drb,
-                             const void* GLin, const void* A, const void* Ab, void* GLout, double* gram);
-
 int mpsk_transfer_left(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
                        const void* GLin, const void* A, const void* Ab, void* GLout) {
   REQUIRE(c && GLin && A && Ab && GLout, "NULL argument");
   HIPCHK(hipSetDevice(c->device));
-  int Wl = W, Wr = W;
-  if (H) { Wl = H->Wl; Wr = H->Wr; d = H->d; }
+  int Wl, Wr;
+  site_dims(H, W, Wl, Wr, d);
   REQUIRE(Wl > 0 && d > 0 && Dl > 0 && Dr > 0 && Dlb > 0 && Drb > 0, "dimensions must be positive");
   if ((H ? H->dtype : c->dtype) == MPSK_C128)
-    return transfer_left_c128(c, H, W, d, Dl, Dr, Dlb, Drb, (const double*)GLin, (const double*)A, (const double*)Ab, (double*)GLout);
+    return transfer_left_c128(c, H, Wl, Wr, d, Dl, Dr, Dlb, Drb, (const double*)GLin, (const double*)A, (const double*)Ab,
+                              (double*)GLout);
   if (dense_route(H))
     return transfer_left_dense(c, H, Dl, Dr, Dlb, Drb, (const double*)GLin, (const double*)A, (const double*)Ab, (double*)GLout);
   return transfer_left_f64(c, H, Wl, Wr, d, Dl, Dr, Dlb, Drb, GLin, A, Ab, GLout, nullptr);
-}
-
-// gram (pass-through only, Dr == Drb): gram[w][t,s] = sum Ab[p,t,b] T1[w][p,s,b] of the stage-1 product, partials after
-// T1 in the workspace; GLout == nullptr then skips stage 2 (mpsk_transfer_left_gram)
-static int transfer_left_f64(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr, int d, int Dl, int Dr, int Dlb, int Drb,
-                             const void* GLin, const void* A, const void* Ab, void* GLout, double* gram) {
-  const size_t slab = (size_t)Dlb * d * Dr, o_part = up32(slab * (Wl + (H ? Wr : 0)));
-  if (int rc = ensure_ws(c, sizeof(double) * (gram ? o_part + site_gram_partial_doubles(Wl, d, false) : slab * (Wl + (H ? Wr : 0)))))
-    return rc;
-  double* T1 = (double*)c->ws;
-  double* T2 = H ? T1 + slab * Wl : T1;
-  // T1[w][p,s,b] = sum_a GLin[w][p,a] A[a,s,b]
-  GemmArgs g1 = mk((const double*)GLin, (const double*)A, T1, Dlb, d * Dr, Dl, Dlb, Dl, Dlb);
-  g1.batch = Wl; g1.bsA = (int64_t)Dlb * Dl; g1.bsB = 0; g1.bsC = (int64_t)slab;
-  HIPCHK(gemm_f64(g1, c->stream));
-  if (H) {
-    SlabIndex ix{d, 1 << 30, (int64_t)Dlb, (int64_t)slab, 0, (int64_t)Dlb * d};
-    HIPCHK(mix_apply(H->fwd, T1, ix, T2, ix, Dlb, Dr, c->stream));
-  }
-  if (gram) HIPCHK(site_gram(Wl, d, Dlb, Dr, T1, (const double*)Ab, false, gram, T1 + o_part, c->stream));
-  if (!GLout) return MPSK_OK;
-  // GLout[v][q,b] = sum_{(p,t)} Ab[(p,t),q] T2[v][(p,t),b]
-  GemmArgs g3 = mk((const double*)Ab, T2, (double*)GLout, Drb, Dr, Dlb * d, (int64_t)Dlb * d, (int64_t)Dlb * d, Drb, 1, 0);
-  g3.batch = Wr; g3.bsA = 0; g3.bsB = (int64_t)slab; g3.bsC = (int64_t)Drb * Dr;
-  HIPCHK(gemm_f64(g3, c->stream));
-  return MPSK_OK;
 }
 
 // The pass-through left transfer plus the site Gram of its stage-1 product: one site of a correlator
@@ -1711,7 +1743,7 @@ int mpsk_transfer_left_gram(mpsk_ctx* c, int W, int d, int Dl, int Dr, int Dlb, 
   REQUIRE(Dr == Drb, "the Gram of the intermediate needs Dr == Drb");
   HIPCHK(hipSetDevice(c->device));
   if (c->dtype == MPSK_C128)
-    return transfer_left_c128(c, nullptr, W, d, Dl, Dr, Dlb, Drb, (const double*)Vin, (const double*)A, (const double*)Ab,
+    return transfer_left_c128(c, nullptr, W, W, d, Dl, Dr, Dlb, Drb, (const double*)Vin, (const double*)A, (const double*)Ab,
                               (double*)Vout, (double*)dev_gram);
   return transfer_left_f64(c, nullptr, W, W, d, Dl, Dr, Dlb, Drb, Vin, A, Ab, Vout, (double*)dev_gram);
 }
@@ -1723,8 +1755,10 @@ int mpsk_site_gram(mpsk_ctx* c, int W, int d, int Dl, int Dr, const void* X, con
   REQUIRE(W > 0 && d > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
   HIPCHK(hipSetDevice(c->device));
   const bool cplx = c->dtype == MPSK_C128;
-  if (int rc = ensure_ws(c, sizeof(double) * site_gram_partial_doubles(W, d, cplx))) return rc;
-  HIPCHK(site_gram(W, d, Dl, Dr, (const double*)X, (const double*)Ab, cplx, (double*)dev_out, (double*)c->ws, c->stream));
+  Ws ws;
+  const size_t o_part = ws.take(site_gram_partial_doubles(W, d, cplx));
+  if (int rc = ws.ensure(c)) return rc;
+  HIPCHK(site_gram(W, d, Dl, Dr, (const double*)X, (const double*)Ab, cplx, (double*)dev_out, Ws::at(c, o_part), c->stream));
   return MPSK_OK;
 }
 
@@ -1732,16 +1766,18 @@ int mpsk_transfer_right(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int D
                         const void* A, const void* Ab, const void* GRin, void* GRout) {
   REQUIRE(c && GRin && A && Ab && GRout, "NULL argument");
   HIPCHK(hipSetDevice(c->device));
-  int Wl = W, Wr = W;
-  if (H) { Wl = H->Wl; Wr = H->Wr; d = H->d; }
+  int Wl, Wr;
+  site_dims(H, W, Wl, Wr, d);
   REQUIRE(Wl > 0 && d > 0 && Dl > 0 && Dr > 0 && Dlb > 0 && Drb > 0, "dimensions must be positive");
   if ((H ? H->dtype : c->dtype) == MPSK_C128)
-    return transfer_right_c128(c, H, W, d, Dl, Dr, Dlb, Drb, (const double*)A, (const double*)Ab, (const double*)GRin, (double*)GRout);
+    return transfer_right_c128(c, H, Wl, Wr, d, Dl, Dr, Dlb, Drb, (const double*)A, (const double*)Ab, (const double*)GRin,
+                               (double*)GRout);
   const size_t plane = (size_t)Dr * Dlb;   // one physical index
   const size_t slab = plane * d;
-  if (int rc = ensure_ws(c, sizeof(double) * slab * (Wr + (H ? Wl : 0)))) return rc;
-  double* U = (double*)c->ws;
-  double* V = H ? U + slab * Wr : U;
+  Ws ws;
+  const size_t o_u = ws.take(slab * Wr), o_v = ws.take(H ? slab * Wl : 0);
+  if (int rc = ws.ensure(c)) return rc;
+  double *U = Ws::at(c, o_u), *V = H ? Ws::at(c, o_v) : U;
   // U[v][b,p,t] = sum_q GRin[v][b,q] Ab[(p,t),q]
   GemmArgs g1 = mk((const double*)GRin, (const double*)Ab, U, Dr, Dlb * d, Drb, Dr, (int64_t)Dlb * d, Dr, 0, 1);
   g1.batch = Wr; g1.bsA = (int64_t)Dr * Drb; g1.bsB = 0; g1.bsC = (int64_t)slab;
@@ -1755,11 +1791,11 @@ int mpsk_transfer_right(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int D
     HIPCHK(mix_apply(H->bwd, U, ix, V, ix, Dr, Dlb, c->stream));
   }
   // GRout[w][a,p] = sum_s sum_b A[a,s,b] V[w][s][b,p]
-  std::vector<int64_t> sa, sb;
-  for (int s = 0; s < d; ++s) { sa.push_back((int64_t)s * Dl); sb.push_back((int64_t)s * plane); }
+  Segs sg;
+  phys_segs(sg, d, Dl, (int64_t)plane);
   GemmArgs g3 = mk((const double*)A, V, (double*)GRout, Dl, Dlb, Dr, (int64_t)Dl * d, Dr, Dl);
   g3.batch = Wl; g3.bsA = 0; g3.bsB = (int64_t)slab; g3.bsC = (int64_t)Dl * Dlb;
-  HIPCHK(gemm_segments(g3, sa, sb, c->stream));
+  HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
 
@@ -3291,6 +3327,8 @@ int mpsk_vzero(mpsk_ctx* c, int64_t n, void* x) {
   return MPSK_OK;
 }
 
+}  // extern "C"
+
 // --------------------------------------------------------------------------------------------
 // bond expansion of a uniform state (changebonds/optimalexpand.jl:16-67, changebonds.jl:13-38)
 // --------------------------------------------------------------------------------------------
@@ -3318,31 +3356,8 @@ static int product_tab(mpsk_ctx* c, int d1, int d2, int64_t sa, int64_t sb, int6
     h[z] = t1 * sa; h[nz + z] = t2 * sb; h[2 * nz + z] = t1 * sc1 + t2 * sc2;
   }
   int64_t* p = nullptr;
-  if (hipMalloc(&p, sizeof(int64_t) * h.size()) != hipSuccess) return fail(MPSK_ERR_NOMEM, "product offset table hipMalloc failed");
-  if (hipMemcpy(p, h.data(), sizeof(int64_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(p);
-    return fail(MPSK_ERR_HIP, "product offset table upload failed");
-  }
+  if (int rc = upload_table(h, "product offset table", &p)) return rc;
   c->prod_tabs.emplace(key, p);
-  *out = p;
-  return MPSK_OK;
-}
-
-// device table [2][Wr d]: tab[z] = s P, tab[Wr d + z] = v Q for z = s + d v (stage-1 batch offsets of the site tensor / GR)
-static int dense_tab_right(const mpsk_mposlice* H, int64_t P, int64_t Q, const int64_t** out) {
-  auto key = std::make_pair(P, Q);
-  auto it = H->dtabR.find(key);
-  if (it != H->dtabR.end()) { *out = it->second; return MPSK_OK; }
-  const int nz = H->Wr * H->d;
-  std::vector<int64_t> h((size_t)2 * nz);
-  for (int z = 0; z < nz; ++z) { h[z] = (int64_t)(z % H->d) * P; h[nz + z] = (int64_t)(z / H->d) * Q; }
-  int64_t* p = nullptr;
-  if (hipMalloc(&p, sizeof(int64_t) * h.size()) != hipSuccess) return fail(MPSK_ERR_NOMEM, "dense offset table hipMalloc failed");
-  if (hipMemcpy(p, h.data(), sizeof(int64_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(p);
-    return fail(MPSK_ERR_HIP, "dense offset table upload failed");
-  }
-  H->dtabR.emplace(key, p);
   *out = p;
   return MPSK_OK;
 }
@@ -3360,12 +3375,8 @@ static int half_left(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int D
     return MPSK_OK;
   }
   const int64_t slab = (int64_t)Dlo * d * Dm;
-  GemmArgs g1 = mk(GL, AC, T1, Dlo, d * Dm, Dl, Dlo, Dl, Dlo);                    // T1[w] = GL[w] AC
-  g1.batch = H->Wl; g1.bsA = (int64_t)Dlo * Dl; g1.bsB = 0; g1.bsC = slab;
-  g1.tag = 1;
-  HIPCHK(gemm_f64(g1, c->stream));
-  SlabIndex ix{d, 1 << 30, (int64_t)Dlo, slab, 0, (int64_t)Dlo * d};
-  HIPCHK(mix_apply(H->fwd, T1, ix, L2, ix, Dlo, Dm, c->stream));                 // L2[u][a,t,m]
+  HIPCHK(stage1(c, H->Wl, Dlo, Dl, d * Dm, GL, AC, T1, 1));                        // T1[w] = GL[w] AC
+  HIPCHK(mix_levels(c, H->fwd, d, Dlo, Dm, T1, L2));                             // L2[u][a,t,m]
   *v = HalfView{L2, Dlo, slab, (int64_t)Dlo * d};
   return MPSK_OK;
 }
@@ -3377,7 +3388,7 @@ static int half_right(mpsk_ctx* c, const mpsk_mposlice* H, int Dm, int Dr, int D
   if (dense_route(H)) {
     const int64_t col = (int64_t)Dm * Dro;
     const int64_t* tab = nullptr;
-    if (int rc = dense_tab_right(H, Dm, (int64_t)Dr * Dro, &tab)) return rc;
+    if (int rc = dense_tab(H, true, Dm, (int64_t)Dr * Dro, &tab)) return rc;
     GemmArgs g1 = mk(AR, GR, T1, Dm, Dro, Dr, (int64_t)Dm * d, Dr, Dm);          // T1[(m,b), (s,v)] = AR[:,s,:] GR[v]
     g1.batch = H->Wr * d; g1.bsC = col;
     g1.tabA = tab; g1.tabB = tab + (size_t)H->Wr * d;
@@ -3395,8 +3406,7 @@ static int half_right(mpsk_ctx* c, const mpsk_mposlice* H, int Dm, int Dr, int D
   g1.batch = H->Wr; g1.bsA = 0; g1.bsB = (int64_t)Dr * Dro; g1.bsC = slab;
   g1.tag = 1;
   HIPCHK(gemm_f64(g1, c->stream));
-  SlabIndex ix{d, 1 << 30, (int64_t)Dm, slab, 0, (int64_t)Dm * d};
-  HIPCHK(mix_apply(H->rgt, T1, ix, R2, ix, Dm, Dro, c->stream));                 // R2[u][m,t,b]
+  HIPCHK(mix_levels(c, H->rgt, d, Dm, Dro, T1, R2));                             // R2[u][m,t,b]
   *v = HalfView{R2, Dm, slab, (int64_t)Dm * d};
   return MPSK_OK;
 }
@@ -3407,23 +3417,18 @@ static int dAC2_factorised(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mpos
                            int Dro, const void* GL, const void* GR, const void* AC, const void* AR, void* Y) {
   HIPCHK(hipSetDevice(c->device));
   const int d1 = H1->d, d2 = H2->d, Wl = H1->Wl, Wm = H1->Wr, Wr = H2->Wr;
-  const auto ev = [](size_t v) { return (v + 1) & ~(size_t)1; };
-  const size_t l1 = ev((size_t)Wl * d1 * Dlo * Dm), l2 = ev((size_t)Wm * d1 * Dlo * Dm);
-  const size_t r1 = ev((size_t)Wr * d2 * Dm * Dro), r2 = ev((size_t)Wm * d2 * Dm * Dro);
-  if (int rc = ensure_ws(c, sizeof(double) * (l1 + l2 + r1 + r2))) return rc;
-  double* TL = (double*)c->ws;
-  double* L2 = TL + l1;
-  double* TR = L2 + l2;
-  double* R2 = TR + r1;
+  Ws ws;
+  const size_t o_tl = ws.take((size_t)Wl * d1 * Dlo * Dm, 2), o_l2 = ws.take((size_t)Wm * d1 * Dlo * Dm, 2);
+  const size_t o_tr = ws.take((size_t)Wr * d2 * Dm * Dro, 2), o_r2 = ws.take((size_t)Wm * d2 * Dm * Dro, 2);
+  if (int rc = ws.ensure(c)) return rc;
+  double *TL = Ws::at(c, o_tl), *L2 = Ws::at(c, o_l2), *TR = Ws::at(c, o_tr), *R2 = Ws::at(c, o_r2);
   HalfView hl, hr;
   if (int rc = half_left(c, H1, Dlo, Dl, Dm, (const double*)GL, (const double*)AC, TL, L2, &hl)) return rc;
   if (int rc = half_right(c, H2, Dm, Dr, Dro, (const double*)AR, (const double*)GR, TR, R2, &hr)) return rc;
   // Y[a,t1,b,t2] = sum_u sum_m Lh(t1,u)[a,m] Rh(t2,u)[m,b]
   const int64_t plane = (int64_t)Dlo * d1 * Dro;
-  std::vector<int64_t> sa, sb;
-  for (int u = 0; u < Wm; ++u)
-    if (H1->col_used[u] && H2->row_used[u]) { sa.push_back(u * hl.su); sb.push_back(u * hr.su); }
-  if (sa.empty()) { HIPCHK(zero_async(Y, sizeof(double) * plane * d2, c->stream)); return MPSK_OK; }
+  Segs sg;
+  if (!level_segs(sg, Wm, hl.su, hr.su, &H1->col_used, 1, 0, &H2->row_used)) return zero_fill(c, Y, sizeof(double) * plane * d2);
   const int64_t* tab = nullptr;
   bool even = false;
   if (int rc = product_tab(c, d1, d2, hl.st, hr.st, Dlo, plane, &tab, &even)) return rc;
@@ -3432,10 +3437,11 @@ static int dAC2_factorised(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mpos
   g.tabA = tab; g.tabB = tab + (size_t)d1 * d2; g.tabC = tab + (size_t)2 * d1 * d2;
   g.tabs_even = even ? 1 : 0;
   g.tag = 1;
-  HIPCHK(gemm_segments(g, sa, sb, c->stream));
+  HIPCHK(gemm_segments(g, sg, c->stream));
   return MPSK_OK;
 }
 
+extern "C" {
 int mpsk_dAC2_product(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dl, int Dm, int Dr, const void* GL,
                       const void* GR, const void* AC, const void* AR, void* Y) {
   REQUIRE(c && H1 && H2 && GL && GR && AC && AR && Y, "NULL argument");
@@ -3444,6 +3450,8 @@ int mpsk_dAC2_product(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice*
   REQUIRE(H1->dtype == MPSK_F64 && H2->dtype == MPSK_F64, "MPSK_F64 slices only");
   return dAC2_factorised(c, H1, H2, Dl, Dl, Dm, Dr, Dr, GL, GR, AC, AR, Y);
 }
+
+}  // extern "C"
 
 // mpsk_complement_tsvd: the k leading singular triplets of X = (1 - QL QL^T) Y (1 - QR^T QR) without null-space bases
 // (NL NL' = 1 - AL AL', NR' NR = 1 - AR' AR in optimalexpand.jl:22-29).  X is formed with four thin GEMMs; the triplets come
@@ -3463,6 +3471,7 @@ static int ex_scratch(mpsk_ctx* c, size_t bytes, double** out) {
   return MPSK_OK;
 }
 
+extern "C" {
 // ac2_proj (derivatives.jl:218-226).  MPSK_F64: the factorised contraction above, the two-site tensor of the state above
 // is never formed.  MPSK_C128: theta = AC AR is built in a scratch buffer of its own (d2 complex GEMMs, one per physical
 // index of the right site) and the rectangular form of the complex two-site matvec runs on it.
