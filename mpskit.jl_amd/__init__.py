@@ -20,6 +20,7 @@ from .quasiparticle import QuasiparticleAnsatz, LeftGaugedQP  # noqa: F401,E402
 from .toolbox import (variance, entropy, entanglement_spectrum, transfer_spectrum, marek_gap, correlation_length,  # noqa: F401,E402
                       exact_diagonalization)
 from .statmech import DenseMPO, PerMPOInfEnv, leading_boundary, classical_ising, sixvertex, dot  # noqa: F401,E402
+from .multiline import MPSMultiline, MPOMultiline, MultilineEnv  # noqa: F401,E402
 from . import native_cplx  # noqa: F401,E402   (complex128 states on interleaved storage: NativeFiniteMPS, dmrg, tdvp_step)
 from .measure import correlator, decompose_localmpo  # noqa: F401,E402   (local expectation values: expectation_value above)
 from .propagator import propagator, DynamicalDMRG, NaiveInvert, Jeckelmann, GMRES, LinearCombination  # noqa: F401,E402

@@ -181,7 +181,8 @@ def expectation_value(psi, H, envs=None, *, device=None):
     if measure.is_local_operator(H, envs):
         return measure.expectation_value(psi, H, envs, device=device)
     from .statmech import DenseMPO, expectation_value as _expval_dense
-    if isinstance(H, DenseMPO):
+    from .multiline import MPSMultiline
+    if isinstance(H, DenseMPO) or isinstance(psi, MPSMultiline):        # an MPSMultiline: the R x n array of expval.jl:165-173
         return _expval_dense(psi, H, envs)
     be = psi.be
     if isinstance(envs, MultipleEnvironments):          # expval of a LazySum: sum of the terms' (lazysum.jl)

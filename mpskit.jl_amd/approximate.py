@@ -10,7 +10,8 @@ formed two-site tensor, two norms) -- the pattern changebonds uses for dAC2_prod
 
 approximate for InfiniteMPS (src/algorithms/approximate/vomps.jl): the VOMPS power method on the mixed environments of
 statmech.PerMPOInfEnv -- per site one ac_proj (mpsk_dAC_proj) and one c_proj (mpsk_dC_proj), then a regauge.  The IDMRG1 / IDMRG2
-forms (approximate/idmrg.jl), MPSMultiline / MPOMultiline with more than one row and complex tensors are not implemented."""
+forms (approximate/idmrg.jl) and complex tensors are not implemented.  An MPSMultiline with (MPOMultiline, MPSMultiline):
+multiline.approximate, the same loop over all rows of a column at once."""
 from __future__ import annotations
 
 import math
@@ -37,9 +38,13 @@ def _sandwich(be, GL: DTensor, x: DTensor, GR: DTensor):
     return be.gemm(t.reshape(t.size // Dr, Dr), DTensor(GR.buf, (Dr, Dro)))
 
 
-def ac_proj(pos, below, envs):
+def ac_proj(pos, below, envs, *rest):
     """ac_proj(pos, below, envs)  (derivatives.jl:210-219): dAC of above.AC[pos] with the environments of `below`
-    (FinEnvPair, or statmech.PerMPOInfEnv on uniform states)."""
+    (FinEnvPair, or statmech.PerMPOInfEnv on uniform states).  ac_proj(row, col, below, envs): the two-index form on the
+    environments of an MPSMultiline (derivatives.jl:216-219)."""
+    if rest:
+        row, col, below, envs = pos, below, envs, rest[0]
+        return envs.ac_proj(row, col, below)
     if isinstance(envs, PerMPOInfEnv):
         return envs.ac_proj(pos, below)
     be = below.be
@@ -53,9 +58,11 @@ def ac_proj(pos, below, envs):
     return be.dAC(H, GL, GR, x, out=be.empty(Dlo, d, Dro))
 
 
-def c_proj(pos, below, envs: PerMPOInfEnv):
+def c_proj(pos, below, envs, *rest):
     """c_proj(pos, below, envs)  (derivatives.jl:204-207): dC of above.CR[pos] with the environments of `below` (uniform
-    states; mpsk_dC_proj)."""
+    states; mpsk_dC_proj).  c_proj(row, col, below, envs): the two-index form on the environments of an MPSMultiline."""
+    if rest:
+        return rest[0].c_proj(pos, below, envs)
     return envs.c_proj(pos, below)
 
 
@@ -108,8 +115,11 @@ def approximate(psi0, toapprox, alg, envs=None):
     environment.  Complex states / operators: native_cplx.approximate.
     psi0 an InfiniteMPS: toapprox = (O, above) with O a DenseMPO or a real SparseMPO (make_time_mpo of an infinite
     Hamiltonian), alg = VOMPS() (approximate/vomps.jl; a VUMPS is converted, as the reference's deprecation does); eps is the
-    Galerkin error.  Not implemented for uniform states: IDMRG1 / IDMRG2 (approximate/idmrg.jl), more than one row, complex
-    tensors."""
+    Galerkin error.  psi0 an MPSMultiline: toapprox = (MPOMultiline, MPSMultiline), alg = VOMPS() (multiline.approximate).
+    Not implemented for uniform states: IDMRG1 / IDMRG2 (approximate/idmrg.jl), complex tensors."""
+    from . import multiline
+    if isinstance(psi0, multiline.MPSMultiline):
+        return multiline.approximate(psi0, toapprox, alg, envs)
     if isinstance(psi0, InfiniteMPS):
         return _approximate_inf(psi0, toapprox, alg, envs)
     _no_cplx(psi0, "approximate")

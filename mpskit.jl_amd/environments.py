@@ -197,6 +197,9 @@ def environments(psi, H, **kw):
         return _mixed(psi, H, **kw)
     if isinstance(H, DenseMPO):
         return PerMPOInfEnv(psi, H, **kw)
+    from .multiline import MPSMultiline
+    if isinstance(psi, MPSMultiline):                                           # permpoinfenv.jl:23-27
+        return PerMPOInfEnv(psi, H, **kw)
     if isinstance(H, LazySum):
         return MultipleEnvironments(H, [environments(psi, h, **kw) for h in H])
     if isinstance(psi, FiniteMPS):

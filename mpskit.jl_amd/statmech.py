@@ -8,8 +8,10 @@ krylov.eigsolve_lm_real on the host.
 
 Environments with above != below (permpoinfenv.jl:29-63, :138-189) serve approximate(psi::InfiniteMPS, (O, above), VOMPS())
 (approximate.py): O a DenseMPO or a real SparseMPO, both environments rectangular, the tangent-space projections ac_proj /
-c_proj (derivatives.jl:204-219) on mpsk_dAC_proj / mpsk_dC_proj.  One row only (no MPSMultiline / MPOMultiline with more
-rows), real tensors only."""
+c_proj (derivatives.jl:204-219) on mpsk_dAC_proj / mpsk_dC_proj.  Real tensors only.
+
+More than one row: MPSMultiline / MPOMultiline and their environments and algorithms live in multiline.py; every entry point
+here (PerMPOInfEnv, environments, calc_galerkin, expectation_value, leading_boundary) hands an MPSMultiline over to it."""
 from __future__ import annotations
 
 import math
@@ -119,6 +121,12 @@ class PerMPOInfEnv:
     right environments of site i in the slab layout, W = the MPO bond at that side of the site.  above = None: above == below,
     slabs (W, D, D).  above = an InfiniteMPS: the state the operator is applied to (permpoinfenv.jl:29-42), fixed for the life
     of the object, lw[i] (W, D_below, D_above) and rw[i] (W, D_above, D_below); `psi` is then the state below."""
+
+    def __new__(cls, psi=None, *args, **kw):
+        from .multiline import MPSMultiline, MultilineEnv
+        if cls is PerMPOInfEnv and isinstance(psi, MPSMultiline):      # (MPSMultiline, MPOMultiline): the multi-row form
+            return object.__new__(MultilineEnv)
+        return object.__new__(cls)
 
     def __init__(self, psi, mpo, tol=1e-12, krylovdim=30, maxiter=100, rng=None, above=None):
         if not isinstance(mpo, (DenseMPO, SparseMPO)):
@@ -254,7 +262,10 @@ class PerMPOInfEnv:
 
 def environments(psi, mpo, **kw):
     """environments(psi::InfiniteMPS, opp::DenseMPO)  (permpoinfenv.jl:20-29) and environments(below, (opp, above))
-    (permpoinfenv.jl:29-42), opp a DenseMPO or a real SparseMPO."""
+    (permpoinfenv.jl:29-42), opp a DenseMPO or a real SparseMPO.  An MPSMultiline: multiline.environments."""
+    from . import multiline
+    if isinstance(psi, multiline.MPSMultiline):
+        return multiline.environments(psi, mpo, **kw)
     if isinstance(mpo, tuple):
         opp, above = mpo
         if not isinstance(above, InfiniteMPS):
@@ -267,6 +278,9 @@ def calc_galerkin(psi, envs: PerMPOInfEnv, pos=None):
     """|| (1 - AL AL^T) normalize(H_AC AC) ||, maximum over the unit cell when pos is None (toolbox.jl:26-38).  Environments
     with a state above: the operator is applied to above.AC and the result projected with the AL of `psi` (the state below)."""
     from .algorithms import _galerkin
+    from . import multiline
+    if isinstance(psi, multiline.MPSMultiline):
+        return multiline.calc_galerkin(psi, envs)
     locs = range(len(psi)) if pos is None else [pos]
     if envs.above is not None:
         return max(_galerkin(psi.be, None, None, psi.AL[loc], g=envs.ac_proj(loc, psi)) for loc in locs)
@@ -275,7 +289,10 @@ def calc_galerkin(psi, envs: PerMPOInfEnv, pos=None):
 
 def expectation_value(psi, mpo: DenseMPO, envs: PerMPOInfEnv | None = None):
     """Per-site leading eigenvalue lambda_i = <AC_i, H_AC_i AC_i> on environments normalised per column
-    (expval.jl:156-172)."""
+    (expval.jl:156-172); an MPSMultiline gives the R x n array of expval.jl:165-173."""
+    from . import multiline
+    if isinstance(psi, multiline.MPSMultiline):
+        return multiline.expectation_value(psi, mpo, envs)
     envs = environments(psi, mpo) if envs is None else envs
     be = psi.be
     out = np.zeros(len(psi))
@@ -288,8 +305,12 @@ def expectation_value(psi, mpo: DenseMPO, envs: PerMPOInfEnv | None = None):
 def leading_boundary(psi, mpo: DenseMPO, alg=None, envs=None):
     """leading_boundary(psi, opp, alg = VUMPS())  (statmech/vumps.jl:15-92): the leading boundary MPS of the column
     transfer operator; returns (psi, envs, eps) with eps the Galerkin error.  alg = VOMPS(): the power method
-    (statmech/vomps.jl:27-87), ONE application of H_AC / H_C per site in place of the eigensolves."""
+    (statmech/vomps.jl:27-87), ONE application of H_AC / H_C per site in place of the eigensolves.  An MPSMultiline with an
+    MPOMultiline: multiline.leading_boundary."""
     from .algorithms import VOMPS, VUMPS, updatetol, regauge, _log
+    from . import multiline
+    if isinstance(psi, multiline.MPSMultiline):
+        return multiline.leading_boundary(psi, mpo, alg, envs)
     alg = VUMPS() if alg is None else alg
     if not isinstance(alg, (VUMPS, VOMPS)):
         raise TypeError(f"leading_boundary takes VUMPS or VOMPS, not {type(alg).__name__}")
