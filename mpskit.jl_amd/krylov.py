@@ -56,13 +56,14 @@ def eigsolve_sr(be: Backend, matvec, x0: DTensor, tol=1e-12, krylovdim=30, maxit
         # benchmark sweep have dimension 4 < 8)
         m = max(1, min(fixed_matvecs, x0.size))
         stride = 2 * m + 1
+        steps = m            # applications made, reported as n_matvecs (the host Ritz route shrinks m at its cut)
         if not values and m <= 32 and hasattr(matvec, "eigsolve_fixed"):
             # the whole solve as ONE library call (mpsk_hac_eigsolve_fixed): same kernels in the same order as below,
             # without the ~30 entry-point calls per site the host otherwise makes (they starve the stream at small D)
             out = be.empty(*shape)
             scal = ws.get((m * stride + 40, 1), 1, tag="eigscal")[0]
             if matvec.eigsolve_fixed(start, m, V[:m + 1] + [ritz], scal, out, first_image) is not None:
-                return None, out, fixed_matvecs, None
+                return None, out, steps, None
         slot = ws.get((m * stride,), 1, tag="eigslot")[0]
         be.normalize_dev(start, out=V[0])              # no host round trip: the solve has ONE synchronisation, below
         for k in range(m):
@@ -77,7 +78,7 @@ def eigsolve_sr(be: Backend, matvec, x0: DTensor, tol=1e-12, krylovdim=30, maxit
             be.lincomb_dev(V[:m], rb, out=ritz)
             out = be.empty(*shape)
             be.normalize_dev(ritz, out=out)
-            return None, out, fixed_matvecs, None
+            return None, out, steps, None
         co = be.download(slot)
         Hm = np.zeros((m + 1, m))
         for k in range(m):
@@ -95,11 +96,13 @@ def eigsolve_sr(be: Backend, matvec, x0: DTensor, tol=1e-12, krylovdim=30, maxit
         Hk = Hm[:m, :m]
         ev, S = np.linalg.eigh((Hk + Hk.T) / 2)
         lam, sv = ev[0], S[:, 0]
+        if sv[0] < 0:                                  # sign: positive component on the start vector, as mpsk_vritz_dev
+            sv = -sv
         res = abs(Hm[m, m - 1] * sv[-1])
         be.lincomb(V[:m], sv, out=ritz)
         out = be.empty(*shape)
         be.normalize_dev(ritz, out=out)
-        return lam, out, fixed_matvecs, res
+        return lam, out, steps, res
     # Thick restart (Krylov-Schur for a Hermitian operator, what KrylovKit's eigsolve does with an Arnoldi / Lanczos
     # factorization; the `keep` rule below is recalled from KrylovKit's source, which is not vendored in the reference:
     # "parity unpinned", only the converged eigenpair is compared anywhere).  After krylovdim steps the basis is SHRUNK to
