@@ -222,6 +222,37 @@ int mpsk_hac_apply_axpby(mpsk_hac* h, const double* a1, const void* x, int nblk,
 int mpsk_hac_eigsolve_fixed(mpsk_hac* hac, const void* x0, int m, void* const* V, void* scal, void* y, void* first_image);
 int mpsk_hac_destroy(mpsk_hac* h);
 int mpsk_hac_info(const mpsk_hac* h, int* mode, int* nslabs);
+/* Summed prepared operator: y = sum_k coefs[k] H_k x for n effective Hamiltonians of ONE site, 1 <= n <= 8 -- the
+ * derivative of a LazySum of MultipliedOperators (derivatives.jl:283-323), whose coefficients change with the evaluation
+ * time while the operators do not.  H, GL, GR: HOST arrays of n slices / left / right environments; the slices may differ
+ * in W and in their block pattern and share d and dtype (else MPSK_ERR_INVALID).  `flags` are those of
+ * mpsk_hac_create_ex, applied to every term.  The coefficients are REAL for both dtypes and start as 1.
+ *   Route 1 (folded): every term is prepared in mode 3 under the flag (MPSK_HAC_CANONICAL for MPSK_F64,
+ *   MPSK_HAC_CANONICAL_C128 with its device-side identity check for MPSK_C128; Jordan-form slice, Dlo == Dl).  Mode 3 is
+ *   linear in its two folds, so the sum is ONE mode-3 operator with GRc0 = sum_k coefs[k] GRc0_k and GLc likewise:
+ *   mpsk_hsum_set_coefs combines both fold buffers in one memory-bound launch (terms added in the order k = 0 .. n-1,
+ *   bit-reproducible; the coefficients travel by value: no upload, no synchronisation), and an application is exactly the
+ *   launches of one mode-3 mpsk_hac_apply of that dtype and shape, whatever n is.  The segment tables cover the union of
+ *   the terms' non-zero (s,t) slabs; a term without a slab at some (s,t) contributes nothing there.  The per-term folds
+ *   are KEPT, not recomputed from the environments (n 2 d^2 D^2 elements, folded once at create time), and the combined
+ *   pair takes another 2 d^2 D^2; an application needs no workspace (complex: the planar copy of x, as mode 3 does).
+ *   Route 2 (accumulated): everything else (non-canonical environments, slices with A blocks, infinite-MPS environments,
+ *   Dlo != Dl).  The terms are applied one after another on their own preparation, term k with alpha = coefs[k] and, for
+ *   k > 0, beta = 1 in its last GEMM stage: no vector pass and no temporary beyond the stage workspace the terms share.
+ *   Every mode accumulates in its last stage, so no term falls back to mpsk_vaxpby.
+ * mpsk_hsum_set_coefs: n host reals, copied before it returns; stream-ordered, so it may be called between applications;
+ * a coefficient 0 is legal.  n == 1 with coefs = {1} is mpsk_hac_apply (nblk = 1) bit for bit on both routes.
+ * mpsk_hsum_apply_axpby: y = a0 x + a1 (sum x), the application followed by the one fused pass of mpsk_hac_apply_axpby.
+ * mpsk_hsum_info: route (1 / 2) and the GEMM launches of one application (route 2: summed over the terms).
+ * GL / GR must stay valid and unchanged while the object lives; x and y must not alias. */
+typedef struct mpsk_hsum mpsk_hsum;
+int mpsk_hsum_create(mpsk_ctx* ctx, int n, const mpsk_mposlice* const* H, int Dlo, int Dl, int Dr,
+                     const void* const* GL, const void* const* GR, int flags, mpsk_hsum** out);
+int mpsk_hsum_set_coefs(mpsk_hsum* h, const double* coefs);
+int mpsk_hsum_apply(mpsk_hsum* h, const void* x, void* y);
+int mpsk_hsum_apply_axpby(mpsk_hsum* h, const double* a1, const void* x, const double* a0, void* y);
+int mpsk_hsum_info(const mpsk_hsum* h, int* route, int* launches_per_apply);
+int mpsk_hsum_destroy(mpsk_hsum* h);
 /* mpsk_dC == dC(x, leftenv::Vector, rightenv::Vector)   derivatives.jl:171-193
  *   y[p,q] = sum_w GL[w][p,a] c[a,b] GR[w][b,q] */
 int mpsk_dC(mpsk_ctx* ctx, int W, int Dlo, int Dl, int Dr, const void* GL, const void* GR,

@@ -62,6 +62,12 @@ SIGNATURES = {
     "mpsk_hac_apply": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
     "mpsk_hac_destroy": [C.c_void_p],
     "mpsk_hac_info": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "mpsk_hsum_create": [C.c_void_p, C.c_int, c_void_pp, C.c_int, C.c_int, C.c_int, c_void_pp, c_void_pp, C.c_int, c_void_pp],
+    "mpsk_hsum_set_coefs": [C.c_void_p, c_double_p],
+    "mpsk_hsum_apply": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "mpsk_hsum_apply_axpby": [C.c_void_p, c_double_p, C.c_void_p, c_double_p, C.c_void_p],
+    "mpsk_hsum_info": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "mpsk_hsum_destroy": [C.c_void_p],
     "mpsk_dC": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                 C.c_void_p],
     "mpsk_dAC2": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

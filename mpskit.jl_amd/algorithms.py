@@ -185,6 +185,11 @@ def expectation_value(psi, H, envs=None, *, device=None):
     if isinstance(H, DenseMPO) or isinstance(psi, MPSMultiline):        # an MPSMultiline: the R x n array of expval.jl:165-173
         return _expval_dense(psi, H, envs)
     be = psi.be
+    from .operators import MultipliedOperator, istimed
+    if istimed(H):
+        raise ValueError("expectation_value of a time-dependent operator: evaluate it first, H(t)")
+    if isinstance(H, MultipliedOperator):
+        return H.f * expectation_value(psi, H.op, envs)
     if isinstance(envs, MultipleEnvironments):          # expval of a LazySum: sum of the terms' (lazysum.jl)
         return sum(f * expectation_value(psi, h, e) for f, h, e in zip(H.fs, H, envs.envs))
     if hasattr(envs, "vector"):                         # ProjectionOperator term (excitations.py)
@@ -259,6 +264,9 @@ def find_groundstate(psi, H, alg=None, envs=None, *, tol=None, maxiter=None, ver
     """find_groundstate(psi, H, alg[, envs]) -> (psi, envs, eps)  (find_groundstate.jl:19-41).  Without alg and without
     keywords: DMRG() / VUMPS().  Without alg and with any keyword: the reference's composite (_default_algorithm).
     A UnionAlg leaves the stages it ran in envs.stages = [(name, history), ...]."""
+    from .operators import istimed
+    if istimed(H):
+        raise ValueError("find_groundstate needs a time-independent operator: evaluate the time-dependent one first, H(t)")
     if alg is None:
         if tol is None and maxiter is None and verbosity is None and trscheme is None:
             alg = DMRG() if isinstance(psi, FiniteMPS) else VUMPS()
@@ -543,6 +551,9 @@ def integrate(be, f, y0, t, dt, alg, ws=None, cplx=False):
     Real states: only steps with real -im*dt (imaginary time, dt = -1j*tau) keep the tensors real.
     Embedded complex states (cplx.py): any complex dt;  exp(z f) with z = -im*dt = zr + i zi is the exponential of
     the real generator  x -> zr f(x) + zi (i f(x))  on the embedded tensors (general Arnoldi)."""
+    if hasattr(f, "at"):                      # time-dependent generator: evaluated at the midpoint (integrators.jl:20-25)
+        te = complex(t) + complex(dt) / 2
+        f = f.at(te.real if te.imag == 0.0 else te)
     z = -1j * complex(dt)
     enc = getattr(f, "encode", None)
     if enc is not None and cplx:

@@ -264,6 +264,11 @@ class Backend:
         the identities itself and keeps mode 2 when they do not hold."""
         return PreparedHAC(self, H, GL, GR, flags=(1 if canonical else 0) | (2 if canonical_c128 else 0))
 
+    def hsum_create(self, Hs, GLs, GRs, canonical: bool = False, canonical_c128: bool = False):
+        """mpsk_hsum_create: the prepared sum of n effective Hamiltonians of one site, y = sum_k coefs[k] H_k x.  Hs: the
+        terms' slices, GLs / GRs their environments; the flags are those of hac_create_ex.  Returns a PreparedHSum."""
+        return PreparedHSum(self, Hs, GLs, GRs, flags=(1 if canonical else 0) | (2 if canonical_c128 else 0))
+
     def dC(self, GL: DTensor, GR: DTensor, c: DTensor, out: DTensor = None, cplx=False):
         if cplx:
             Dl2, Dr = c.shape
@@ -976,6 +981,63 @@ class PreparedHAC:
     def close(self):
         if getattr(self, "handle", None) and self.be.ctx:
             self.be.lib.mpsk_hac_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PreparedHSum:
+    """Owner of an mpsk_hsum handle (include/mpsk.h): set_coefs(c) then apply(x, out) is y = sum_k c[k] H_k x."""
+
+    def __init__(self, be: Backend, Hs, GLs, GRs, flags: int = 0):
+        n = len(Hs)
+        assert n == len(GLs) == len(GRs) and n >= 1
+        self.cplx = bool(getattr(Hs[0], "cplx", False))
+        m = 2 if self.cplx else 1
+        _, Dlo, Dl = GLs[0].shape
+        _, _, Dr = GRs[0].shape
+        self.be, self.Hs, self.GLs, self.GRs = be, list(Hs), list(GLs), list(GRs)      # keep the operands alive
+        self.n, self.Dlo, self.Dl, self.Dr, self.d = n, Dlo // m, Dl, Dr, Hs[0].d
+        arr = lambda ps: (C.c_void_p * n)(*ps)
+        h = C.c_void_p()
+        check(be.lib.mpsk_hsum_create(be.ctx, n, arr([H.handle.value for H in Hs]), self.Dlo, Dl, Dr,
+                                      arr([g.ptr for g in GLs]), arr([g.ptr for g in GRs]), int(flags), C.byref(h)),
+              "mpsk_hsum_create")
+        self.handle = h
+
+    def info(self):
+        route, ln = C.c_int(), C.c_int()
+        check(self.be.lib.mpsk_hsum_info(self.handle, C.byref(route), C.byref(ln)), "mpsk_hsum_info")
+        return {"route": route.value, "launches": ln.value}
+
+    def set_coefs(self, coefs):
+        assert len(coefs) == self.n
+        check(self.be.lib.mpsk_hsum_set_coefs(self.handle, (C.c_double * self.n)(*[float(c) for c in coefs])),
+              "mpsk_hsum_set_coefs")
+        return self
+
+    def apply(self, x: DTensor, out: DTensor = None):
+        m = 2 if self.cplx else 1
+        assert x.shape == (m * self.Dl, self.d, self.Dr), (x.shape, (m * self.Dl, self.d, self.Dr))
+        y = self.be.empty(m * self.Dlo, self.d, self.Dr) if out is None else out
+        check(self.be.lib.mpsk_hsum_apply(self.handle, x.ptr, y.ptr), "mpsk_hsum_apply")
+        return y
+
+    def apply_axpby(self, a1, x: DTensor, a0, out: DTensor = None):
+        m = 2 if self.cplx else 1
+        assert x.shape == (m * self.Dl, self.d, self.Dr), (x.shape, (m * self.Dl, self.d, self.Dr))
+        y = self.be.empty(m * self.Dlo, self.d, self.Dr) if out is None else out
+        check(self.be.lib.mpsk_hsum_apply_axpby(self.handle, Backend._c2(a1), x.ptr, Backend._c2(a0), y.ptr),
+              "mpsk_hsum_apply_axpby")
+        return y
+
+    def close(self):
+        if getattr(self, "handle", None) and self.be.ctx:
+            self.be.lib.mpsk_hsum_destroy(self.handle)
         self.handle = None
 
     def __del__(self):

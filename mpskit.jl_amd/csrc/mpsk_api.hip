@@ -164,6 +164,11 @@ struct mpsk_hac {
   std::vector<int64_t> zseg_host;   // source of the asynchronous upload of zseg: lives as long as the handle (no sync)
   hipEvent_t ev_up = nullptr;       // completion of that upload (waited for before the handle is freed)
   int pool_idx = -1;
+  // mode 3, MPSK_F64: segments per batch of the two families and their per-t slab lists [d][jn1] / [d][jn2] -- the slice's
+  // own (jr_p / jl_p), or the union over the terms of a summed operator (mpsk_hsum)
+  int jn1 = 0, jn2 = 0;
+  const std::vector<int>* jp1 = nullptr;
+  const std::vector<int>* jp2 = nullptr;
 };
 constexpr int MAXK = 256;
 constexpr int MAXCOEF = 1024;   // coefficient staging: MAXK for mpsk_vlincomb, 32 x 32 for mpsk_vmultilincomb
@@ -721,7 +726,8 @@ struct CxPlanes {
 // Dro: columns of the GR slabs [Dr, Dro] = last dimension of y (the square matvec passes Dro = Dr; mpsk_dAC_proj the bond
 // dimension of the state below).
 static int dAC_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const double* GL, const double* GR,
-                    const double* GRp, const double* x, double* y) {   // GRp planes are ev2(Wr Dr Dro) doubles apart
+                    const double* GRp, const double* x, double* y, double alpha = 1.0, double beta = 0.0) {
+  // GRp planes are ev2(Wr Dr Dro) doubles apart; alpha / beta: y = alpha H x + beta y, folded into the last GEMM (mpsk_hsum)
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t nx = (size_t)Dl * d * Dr, nG = (size_t)Wr * Dr * Dro, slab = (size_t)2 * Dlo * d * Dr;
@@ -737,9 +743,9 @@ static int dAC_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   HIPCHK(mix_levels(c, H->fwd, d, 2 * Dlo, Dr, T1, T2));
   Segs sg;
   if (!level_segs(sg, Wr, (int64_t)slab, (int64_t)Dr * Dro, &H->col_used, 2, (int64_t)ev2(nG)))
-    return zero_fill(c, y, sizeof(double) * 2 * Dlo * d * Dro);
+    return beta == 1.0 ? MPSK_OK : zero_fill(c, y, sizeof(double) * 2 * Dlo * d * Dro);
   GemmArgs g3 = mk(T2, gr, y, 2 * Dlo * d, Dro, Dr, (int64_t)2 * Dlo * d, Dr, (int64_t)2 * Dlo * d);
-  g3.cplx = 1;
+  g3.cplx = 1; g3.alpha = alpha; g3.beta = beta;
   HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
@@ -888,7 +894,7 @@ static int transfer_right_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int 
 // tensor): the blocks become K-segments of the stage-1 GEMM, nothing is re-interleaved (mpsk_dAC_blocked).
 // GR: Wr slabs [Dr, Dro], y: [Dlo, d, Dro]; the square matvec is Dro = Dr.
 static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR,
-                    const void* x, int nblk, void* y) {
+                    const void* x, int nblk, void* y, double alpha = 1.0, double beta = 0.0) {
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t slab = (size_t)Dlo * d * Dr;
@@ -902,9 +908,10 @@ static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   HIPCHK(mix_levels(c, H->fwd, d, Dlo, Dr, T1, T2));
   // stage 3: y = sum_v T2[v] * GR[v]   (K-segments over v)
   Segs sg;
-  if (!level_segs(sg, Wr, (int64_t)slab, (int64_t)Dr * Dro, &H->col_used)) return zero_fill(c, y, sizeof(double) * Dlo * d * Dro);
+  if (!level_segs(sg, Wr, (int64_t)slab, (int64_t)Dr * Dro, &H->col_used))
+    return beta == 1.0 ? MPSK_OK : zero_fill(c, y, sizeof(double) * Dlo * d * Dro);
   GemmArgs g3 = mk(T2, (const double*)GR, (double*)y, Dlo * d, Dro, Dr, (int64_t)Dlo * d, Dr, (int64_t)Dlo * d);
-  g3.tag = 1;
+  g3.tag = 1; g3.alpha = alpha; g3.beta = beta;
   HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
@@ -971,7 +978,7 @@ static int dense_stage2(mpsk_ctx* c, const mpsk_mposlice* H, int64_t rows, const
 }
 
 static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const double* GL, const double* GR,
-                     const double* x, double* y) {
+                     const double* x, double* y, double alpha = 1.0, double beta = 0.0) {
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t slab = (size_t)Dlo * Dr;               // one (s,w) / (t,v) column of the intermediates
@@ -983,10 +990,11 @@ static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int D
   if (int rc = dense_stage2(c, H, (int64_t)slab, T1, T2)) return rc;
   // stage 3: y[:, t, :] = sum_v T2[:, :, t, v] GR[v]    (batch over t; K-segments over v)
   Segs sg;
-  if (!level_segs(sg, Wr, (int64_t)d * slab, (int64_t)Dr * Dro, &H->col_used)) return zero_fill(c, y, sizeof(double) * Dlo * d * Dro);
+  if (!level_segs(sg, Wr, (int64_t)d * slab, (int64_t)Dr * Dro, &H->col_used))
+    return beta == 1.0 ? MPSK_OK : zero_fill(c, y, sizeof(double) * Dlo * d * Dro);
   GemmArgs g3 = mk(T2, GR, y, Dlo, Dro, Dr, Dlo, Dr, (int64_t)Dlo * d);
   g3.batch = d; g3.bsA = (int64_t)slab; g3.bsB = 0; g3.bsC = Dlo;
-  g3.tag = 1;
+  g3.tag = 1; g3.alpha = alpha; g3.beta = beta;
   HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
 }
@@ -1090,16 +1098,21 @@ static int identity_deviation(mpsk_ctx* c, const double* G, int n, double* dev) 
 // mode 3 (Jordan form): fold GRc0 / GLc into the pool buffer and upload the per-batch segment tables, on the ctx stream.
 // Tables (element offsets), one launch: A[d][n1 + n2], B[d][n1 + n2] -- segments k < n1 relative to (x, GRc0), the others
 // to (GLc, x); two launches: A1[d][n1], B1[d][n1], A2[d][n2], B2[d][n2].
+// GL == nullptr: tables only (the folds of a summed operator are combined from its terms', mpsk_hsum_set_coefs).
 static hipError_t hac_jordan_prepare(mpsk_ctx* c, mpsk_hac* h, const double* GL, const double* GR) {
   const mpsk_mposlice* H = h->H;
-  const int d = H->d, n1 = H->jr_nseg, n2 = H->jl_nseg;
+  const int d = H->d, n1 = h->jn1, n2 = h->jn2;
+  const std::vector<int>&p1 = *h->jp1, &p2 = *h->jp2;
   const int Dlo = h->Dlo, Dl = h->Dl, Dr = h->Dr;
   const int64_t tR = (int64_t)Dr * d * Dr, tL = (int64_t)Dlo * d * Dl;     // one t-group of GRc0 / GLc
   // GRc0[(s,t)] = sum_v O[0,t,s,v] GR[v] ;  GLc[(s,t)] = sum_{w>0} O[w,t,s,W-1] GL[w]   (slab p = s + d t)
   SlabIndex ir{1 << 30, 1, (int64_t)Dr * Dr, 0, 0, (int64_t)Dr}, orr{d, 1 << 30, (int64_t)Dr, tR, 0, (int64_t)d * Dr};
   SlabIndex il{1 << 30, 1, (int64_t)Dlo * Dl, 0, 0, (int64_t)Dlo}, ol{d, 1 << 30, (int64_t)Dlo, tL, 0, (int64_t)d * Dlo};
-  hipError_t e = mix_apply(H->jr, GR, ir, h->GRc, orr, Dr, Dr, c->stream);
-  if (e == hipSuccess) e = mix_apply(H->jl, GL, il, h->GLc, ol, Dlo, Dl, c->stream);
+  hipError_t e = hipSuccess;
+  if (GL) {
+    e = mix_apply(H->jr, GR, ir, h->GRc, orr, Dr, Dr, c->stream);
+    if (e == hipSuccess) e = mix_apply(H->jl, GL, il, h->GLc, ol, Dlo, Dl, c->stream);
+  }
   if (e != hipSuccess) return e;
   const int n = n1 + n2;
   h->zseg_host.assign((size_t)2 * d * n, 0);
@@ -1109,12 +1122,12 @@ static hipError_t hac_jordan_prepare(mpsk_ctx* c, mpsk_hac* h, const double* GL,
   if (h->launches == 2) { b1 = tab + (size_t)d * n1; a2 = tab + (size_t)2 * d * n1; b2 = a2 + (size_t)d * n2; st1 = n1; st2 = n2; }
   for (int t = 0; t < d; ++t) {
     for (int k = 0; k < n1; ++k) {
-      const int p = H->jr_p[(size_t)t * n1 + k], si = p % d, tt = p / d;
+      const int p = p1[(size_t)t * n1 + k], si = p % d, tt = p / d;
       a1[t * st1 + k] = (int64_t)si * Dl;                               // x[:, s, :]
       b1[t * st1 + k] = tt * tR + (int64_t)si * Dr;                     // GRc0[(s, tt)]
     }
     for (int k = 0; k < n2; ++k) {
-      const int p = H->jl_p[(size_t)t * n2 + k], si = p % d, tt = p / d;
+      const int p = p2[(size_t)t * n2 + k], si = p % d, tt = p / d;
       a2[t * st2 + k] = tt * tL + (int64_t)si * Dlo;                    // GLc[(s, tt)]
       b2[t * st2 + k] = (int64_t)si * Dl;                               // x[:, s, :]
     }
@@ -1232,6 +1245,7 @@ int mpsk_hac_create_ex(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int
     // forces the two-launch form (A/B switch)
     const char* ev = getenv("MPSK_HAC_LAUNCHES");
     h->launches = (Dl == Dr && !(ev && ev[0] == '2')) ? 1 : 2;
+    h->jn1 = H->jr_nseg; h->jn2 = H->jl_nseg; h->jp1 = &H->jr_p; h->jp2 = &H->jl_p;
     const size_t nR = up32((size_t)d * d * Dr * Dr), nL = up32((size_t)d * d * Dlo * Dl);      // 256-B aligned parts
     const size_t bytes = sizeof(double) * (nR + nL) + sizeof(int64_t) * 2 * d * (H->jr_nseg + H->jl_nseg);
     void* buf = nullptr;
@@ -1308,7 +1322,7 @@ int mpsk_hac_info(const mpsk_hac* h, int* mode, int* nslabs) {
 // complex mode 3: y[:, t, :] = sum_s x[:, s, :] GRc0[(s, t)] + sum_s GLc[(s, t)] x[:, s, :], two launches batched over t with
 // all d values of s as K-segments (re and im plane of the B operand each, the second through the J loader): 16 d^2 D^3
 // real flops, against 16 (Wl + Wr) d D^3 of the mix form
-static int hac_apply_jordan_c128(mpsk_hac* h, const double* x, double* y) {
+static int hac_apply_jordan_c128(mpsk_hac* h, const double* x, double* y, double alpha = 1.0, double beta = 0.0) {
   mpsk_ctx* c = h->ctx;
   const int d = h->H->d, Dlo = h->Dlo, Dl = h->Dl, Dr = h->Dr;
   HIPCHK(hipSetDevice(c->device));
@@ -1321,43 +1335,42 @@ static int hac_apply_jordan_c128(mpsk_hac* h, const double* x, double* y) {
   level_segs(s1, d, (int64_t)2 * Dl, (int64_t)Dr * Dr, nullptr, 2, (int64_t)ev2(nR));
   GemmArgs g1 = mk(x, h->GRc, y, 2 * Dlo, Dr, Dr, (int64_t)2 * Dl * d, Dr, (int64_t)2 * Dlo * d);
   g1.batch = d; g1.bsA = 0; g1.bsB = (int64_t)d * Dr * Dr; g1.bsC = (int64_t)2 * Dlo;
-  g1.cplx = 1;
+  g1.cplx = 1; g1.alpha = alpha; g1.beta = beta;
   HIPCHK(gemm_segments(g1, s1, c->stream));
   level_segs(s2, d, (int64_t)2 * Dlo * Dl, Dl, nullptr, 2, xpl.stride());
   GemmArgs g2 = mk(h->GLc, xpl.at(c), y, 2 * Dlo, Dr, Dl, (int64_t)2 * Dlo, (int64_t)Dl * d, (int64_t)2 * Dlo * d);
   g2.batch = d; g2.bsA = (int64_t)d * 2 * Dlo * Dl; g2.bsB = 0; g2.bsC = (int64_t)2 * Dlo;
-  g2.cplx = 1; g2.beta = 1.0;
+  g2.cplx = 1; g2.alpha = alpha; g2.beta = 1.0;
   HIPCHK(gemm_segments(g2, s2, c->stream));
   return MPSK_OK;
 }
 
-extern "C" {
-int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
-  REQUIRE(h && x && y, "NULL argument");
+// y = alpha H x + beta y with alpha / beta in the last GEMM stage of every mode (beta: 0 or 1).  alpha = 1, beta = 0 is
+// mpsk_hac_apply; the other values are the accumulated route of mpsk_hsum_apply.
+static int hac_apply_ab(mpsk_hac* h, const void* x, int nblk, void* y, double alpha, double beta) {
   mpsk_ctx* c = h->ctx;
   const mpsk_mposlice* H = h->H;
   const int Dlo = h->Dlo, Dl = h->Dl, Dr = h->Dr;
-  REQUIRE(nblk >= 1 && nblk <= MAXSEG && Dl % nblk == 0, "nblk must divide Dl (and be <= 32)");
   if (h->mode == 3 && H->dtype == MPSK_C128) {
     if (nblk != 1) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_hac_apply: the blocked layout is implemented for MPSK_F64 only");
-    return hac_apply_jordan_c128(h, (const double*)x, (double*)y);
+    return hac_apply_jordan_c128(h, (const double*)x, (double*)y, alpha, beta);
   }
   if (h->mode == 2) {
     if (nblk != 1) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_hac_apply: the blocked layout is implemented for MPSK_F64 only");
-    return dAC_c128(c, H, Dlo, Dl, Dr, Dr, h->GL, h->GR, h->GRc, (const double*)x, (double*)y);
+    return dAC_c128(c, H, Dlo, Dl, Dr, Dr, h->GL, h->GR, h->GRc, (const double*)x, (double*)y, alpha, beta);
   }
-  if (h->mode == 0 || (h->mode == 4 && nblk != 1)) return dAC_impl(c, H, Dlo, Dl, Dr, Dr, h->GL, h->GR, x, nblk, y);
-  if (h->mode == 4) return dAC_dense(c, H, Dlo, Dl, Dr, Dr, h->GL, h->GR, (const double*)x, (double*)y);
+  if (h->mode == 0 || (h->mode == 4 && nblk != 1)) return dAC_impl(c, H, Dlo, Dl, Dr, Dr, h->GL, h->GR, x, nblk, y, alpha, beta);
+  if (h->mode == 4) return dAC_dense(c, H, Dlo, Dl, Dr, Dr, h->GL, h->GR, (const double*)x, (double*)y, alpha, beta);
   HIPCHK(hipSetDevice(c->device));
   if (h->mode == 3) {
     // y[:, t, :] = sum_k x[:, s_k, :] GRc0[(s_k, t)] + sum_k GLc[(s_k, t)] x[:, s_k, :]     (batch over t)
     if (nblk != 1) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_hac_apply: the Jordan-form operator takes the plain vector layout only");
-    const int d = H->d, n1 = H->jr_nseg, n2 = H->jl_nseg;
+    const int d = H->d, n1 = h->jn1, n2 = h->jn2;
     const bool even = Dlo % 2 == 0 && Dl % 2 == 0 && Dr % 2 == 0;
     GemmArgs g = mk((const double*)x, h->GRc, (double*)y, Dlo, Dr, Dr, (int64_t)Dl * d, (int64_t)Dr * d, (int64_t)Dlo * d);
     g.batch = d; g.bsA = 0; g.bsB = 0; g.bsC = (int64_t)Dlo;
     g.tabs_even = even;
-    g.tag = 1;
+    g.tag = 1; g.alpha = alpha; g.beta = beta;
     if (h->launches == 1) {        // Dl == Dr: the (GLc, x) family has the same lda / ldb / K
       g.A2 = h->GLc; g.B2 = (const double*)x; g.nseg1 = n1;
       g.nseg = n1 + n2; g.zsegA = h->zseg; g.zsegB = h->zseg + (size_t)d * (n1 + n2);
@@ -1368,7 +1381,7 @@ int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
     HIPCHK(gemm_f64(g, c->stream));
     GemmArgs g2 = mk(h->GLc, (const double*)x, (double*)y, Dlo, Dr, Dl, (int64_t)Dlo * d, (int64_t)Dl * d, (int64_t)Dlo * d);
     g2.batch = d; g2.bsA = 0; g2.bsB = 0; g2.bsC = (int64_t)Dlo;
-    g2.beta = 1.0;
+    g2.alpha = alpha; g2.beta = 1.0;
     g2.tabs_even = even;
     g2.tag = 1;
     g2.nseg = n2; g2.zsegA = h->zseg + (size_t)2 * d * n1; g2.zsegB = g2.zsegA + (size_t)d * n2;
@@ -1388,9 +1401,16 @@ int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
   g3.batch = d; g3.bsA = 0; g3.bsB = 0; g3.bsC = (int64_t)Dlo;
   g3.nseg = ns; g3.zsegA = h->zseg; g3.zsegB = h->zseg + (size_t)d * ns;
   g3.tabs_even = (Dlo % 2 == 0) && (Dr % 2 == 0);
-  g3.tag = 1;
+  g3.tag = 1; g3.alpha = alpha; g3.beta = beta;
   HIPCHK(gemm_f64(g3, c->stream));
   return MPSK_OK;
+}
+
+extern "C" {
+int mpsk_hac_apply(mpsk_hac* h, const void* x, int nblk, void* y) {
+  REQUIRE(h && x && y, "NULL argument");
+  REQUIRE(nblk >= 1 && nblk <= MAXSEG && h->Dl % nblk == 0, "nblk must divide Dl (and be <= 32)");
+  return hac_apply_ab(h, x, nblk, y, 1.0, 0.0);
 }
 
 // y = a0 x + a1 (H_AC x): the shifted operator of linsolve(H_AC, b, x0, alg, a0, a1) (corvector.jl:68, :123).  The
@@ -1414,6 +1434,188 @@ int mpsk_hac_apply_axpby(mpsk_hac* h, const double* a1, const void* x, int nblk,
   } else {
     HIPCHK(vec_scal(a1[0], (double*)y, n, c->stream));
   }
+  return MPSK_OK;
+}
+
+// ---- summed prepared operator (mpsk_hsum): y = sum_k coefs[k] H_k x for n operators on one site ------------------------
+// Route 1 (folded): every term is a mode-3 operator.  Mode 3 is linear in its two folds, so sum_k c_k H_k is ONE mode-3
+// operator with the folds sum_k c_k GRc0_k / sum_k c_k GLc_k: the terms keep their folds (their own mpsk_hac), `sum` owns
+// the combined pair and the segment tables of the union pattern; mpsk_hsum_set_coefs is one fold_lincomb launch.
+// Route 2 (accumulated): the terms are applied one after another, coefs[k] and beta = 1 in the last GEMM of each.
+struct mpsk_hsum {
+  mpsk_ctx* ctx = nullptr;
+  int n = 0, route = 2;
+  mpsk_hac* term[MPSK_HSUM_MAX] = {};
+  double coef[MPSK_HSUM_MAX] = {};
+  mpsk_hac* sum = nullptr;                 // route 1: the combined operator
+  std::vector<int> up1, up2;               // route 1, MPSK_F64: per-t slab lists of the union pattern
+};
+
+static void hsum_free(mpsk_hsum* s) {
+  if (s->sum) (void)mpsk_hac_destroy(s->sum);
+  for (int k = 0; k < s->n; ++k) if (s->term[k]) (void)mpsk_hac_destroy(s->term[k]);
+  delete s;
+}
+
+// route 1: combine the terms' folds into s->sum with the current coefficients (one launch on the ctx stream)
+static int hsum_combine(mpsk_hsum* s) {
+  const mpsk_hac* h = s->sum;
+  const int d = h->H->d;
+  const size_t nR = (size_t)d * d * h->Dr * h->Dr, nL = (size_t)d * d * h->Dlo * h->Dl;
+  FoldLincombArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.n = s->n;
+  for (int k = 0; k < s->n; ++k) { a.srcR[k] = s->term[k]->GRc; a.srcL[k] = s->term[k]->GLc; a.coef[k] = s->coef[k]; }
+  a.dstR = h->GRc; a.dstL = h->GLc;
+  // complex: the two planes of GRc0 (ev2(nR) doubles apart) and the interleaved GLc
+  const bool cx = h->H->dtype == MPSK_C128;
+  a.nR = (int64_t)(cx ? 2 * ev2(nR) : nR);
+  a.nL = (int64_t)(cx ? 2 * nL : nL);
+  HIPCHK(hipSetDevice(s->ctx->device));
+  HIPCHK(fold_lincomb(a, s->ctx->stream));
+  return MPSK_OK;
+}
+
+int mpsk_hsum_create(mpsk_ctx* c, int n, const mpsk_mposlice* const* H, int Dlo, int Dl, int Dr, const void* const* GL,
+                     const void* const* GR, int flags, mpsk_hsum** out) {
+  REQUIRE(c && H && GL && GR && out, "NULL argument");
+  REQUIRE(n >= 1 && n <= MPSK_HSUM_MAX, "needs 1 <= n <= 8 terms");
+  REQUIRE((flags & ~(MPSK_HAC_CANONICAL | MPSK_HAC_CANONICAL_C128)) == 0, "unknown flags");
+  REQUIRE(Dlo > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
+  for (int k = 0; k < n; ++k) {
+    REQUIRE(H[k] && GL[k] && GR[k], "NULL term");
+    REQUIRE(H[k]->d == H[0]->d && H[k]->dtype == H[0]->dtype, "the terms must share d and dtype");
+  }
+  auto* s = new mpsk_hsum();
+  s->ctx = c;
+  for (int k = 0; k < n; ++k) {
+    if (int rc = mpsk_hac_create_ex(c, H[k], Dlo, Dl, Dr, GL[k], GR[k], flags, &s->term[k])) { hsum_free(s); return rc; }
+    s->n = k + 1;
+    s->coef[k] = 1.0;
+  }
+  bool folded = true;
+  for (int k = 0; k < n; ++k) folded = folded && s->term[k]->mode == 3 && s->term[k]->launches == s->term[0]->launches;
+  if (folded) {
+    const int d = H[0]->d;
+    const bool cx = H[0]->dtype == MPSK_C128;
+    auto* h = new mpsk_hac();
+    h->ctx = c; h->H = H[0]; h->Dlo = Dlo; h->Dl = Dl; h->Dr = Dr; h->GL = nullptr; h->GR = nullptr;
+    h->mode = 3; h->launches = s->term[0]->launches;
+    s->sum = h;
+    const size_t nR = (size_t)d * d * Dr * Dr, nL = (size_t)d * d * Dlo * Dl;
+    void* buf = nullptr;
+    if (cx) {
+      if (int rc = pool_take(c, sizeof(double) * (2 * ev2(nR) + 2 * nL), &buf, &h->pool_idx)) { hsum_free(s); return rc; }
+      h->GRc = (double*)buf;
+      h->GLc = h->GRc + 2 * ev2(nR);
+      // the combine runs over the two planes of GRc0 as one range of 2 ev2(nR) doubles: for odd nR that includes the pad
+      // double behind each plane, which no fold writes -- zero it in every term so that nothing uninitialised is read
+      if (nR & 1)
+        for (int k = 0; k < n; ++k)
+          for (int pl = 0; pl < 2; ++pl) {
+            hipError_t e = hipMemsetAsync(s->term[k]->GRc + pl * ev2(nR) + nR, 0, sizeof(double), c->stream);
+            if (e != hipSuccess) { hsum_free(s); return fail(MPSK_ERR_HIP, hipGetErrorString(e)); }
+          }
+    } else {
+      // union over the terms of the slabs p = s + d t that carry a fold, per t, padded with a slab empty in every term
+      std::vector<char> ru((size_t)d * d, 0), lu((size_t)d * d, 0);
+      for (int k = 0; k < n; ++k) {
+        const mpsk_mposlice* Hk = H[k];
+        for (int t = 0; t < d; ++t)
+          for (int si = 0; si < d; ++si) {
+            for (int v = 0; v < Hk->Wr; ++v) if (Hk->O(0, t, si, v) != 0.0) ru[si + d * t] = 1;
+            for (int w = 1; w < Hk->Wl; ++w) if (Hk->O(w, t, si, Hk->Wr - 1) != 0.0) lu[si + d * t] = 1;
+          }
+      }
+      auto lists = [&](const std::vector<char>& used, std::vector<int>& o, int& nseg) {
+        int empty = -1;
+        for (int p = 0; p < d * d; ++p) if (!used[p]) { empty = p; break; }
+        for (int t = 0; t < d; ++t) {
+          int m = 0;
+          for (int si = 0; si < d; ++si) m += used[si + d * t];
+          nseg = std::max(nseg, m);
+        }
+        o.assign((size_t)d * nseg, empty);
+        for (int t = 0; t < d; ++t) {
+          int q = 0;
+          for (int si = 0; si < d; ++si) if (used[si + d * t]) o[(size_t)t * nseg + q++] = si + d * t;
+        }
+      };
+      lists(ru, s->up1, h->jn1);
+      lists(lu, s->up2, h->jn2);
+      h->jp1 = &s->up1; h->jp2 = &s->up2;
+      const size_t aR = up32(nR), aL = up32(nL);
+      const size_t bytes = sizeof(double) * (aR + aL) + sizeof(int64_t) * 2 * d * (h->jn1 + h->jn2);
+      if (int rc = pool_take(c, bytes, &buf, &h->pool_idx)) { hsum_free(s); return rc; }
+      h->GRc = (double*)buf;
+      h->GLc = h->GRc + aR;
+      h->zseg = (int64_t*)(h->GLc + aL);
+      hipError_t e = hac_jordan_prepare(c, h, nullptr, nullptr);
+      if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); hsum_free(s); return fail(MPSK_ERR_HIP, hipGetErrorString(e)); }
+    }
+    s->route = 1;
+    if (int rc = hsum_combine(s)) { hsum_free(s); return rc; }
+  }
+  *out = s;
+  return MPSK_OK;
+}
+
+int mpsk_hsum_set_coefs(mpsk_hsum* s, const double* coefs) {
+  REQUIRE(s && coefs, "NULL argument");
+  for (int k = 0; k < s->n; ++k) s->coef[k] = coefs[k];
+  return s->route == 1 ? hsum_combine(s) : MPSK_OK;
+}
+
+int mpsk_hsum_apply(mpsk_hsum* s, const void* x, void* y) {
+  REQUIRE(s && x && y, "NULL argument");
+  REQUIRE(x != y, "x and y must not alias");
+  if (s->route == 1) return hac_apply_ab(s->sum, x, 1, y, 1.0, 0.0);
+  for (int k = 0; k < s->n; ++k)
+    if (int rc = hac_apply_ab(s->term[k], x, 1, y, s->coef[k], k ? 1.0 : 0.0)) return rc;
+  return MPSK_OK;
+}
+
+int mpsk_hsum_apply_axpby(mpsk_hsum* s, const double* a1, const void* x, const double* a0, void* y) {
+  REQUIRE(s && x && y && a0 && a1, "NULL argument");
+  const mpsk_hac* h = s->term[0];
+  const bool cplx = h->H->dtype == MPSK_C128;
+  const bool shift = a0[0] != 0.0 || (cplx && a0[1] != 0.0);
+  const bool scale = a1[0] != 1.0 || (cplx && a1[1] != 0.0);
+  REQUIRE(!shift || h->Dlo == h->Dl, "a shift needs a square operator (Dlo == Dl)");
+  if (int rc = mpsk_hsum_apply(s, x, y)) return rc;
+  if (!shift && !scale) return MPSK_OK;
+  const int64_t nel = (int64_t)h->Dlo * h->H->d * h->Dr;
+  if (cplx) {
+    HIPCHK(vec_axpby_c(a0, shift ? (const double*)x : nullptr, a1, (double*)y, nel, s->ctx->stream));
+  } else if (shift) {
+    HIPCHK(vec_axpby(a0[0], (const double*)x, a1[0], (double*)y, nel, s->ctx->stream));
+  } else {
+    HIPCHK(vec_scal(a1[0], (double*)y, nel, s->ctx->stream));
+  }
+  return MPSK_OK;
+}
+
+// GEMM launches of one application (the planar copy of x of a complex operator and the slab mix are not GEMMs)
+static int hac_gemm_launches(const mpsk_hac* h) {
+  if (h->mode == 3) return h->H->dtype == MPSK_C128 ? 2 : h->launches;
+  if (h->mode == 4) return 3;
+  return 2;
+}
+
+int mpsk_hsum_info(const mpsk_hsum* s, int* route, int* launches_per_apply) {
+  REQUIRE(s, "hsum is NULL");
+  if (route) *route = s->route;
+  if (launches_per_apply) {
+    int m = 0;
+    if (s->route == 1) m = hac_gemm_launches(s->sum);
+    else for (int k = 0; k < s->n; ++k) m += hac_gemm_launches(s->term[k]);
+    *launches_per_apply = m;
+  }
+  return MPSK_OK;
+}
+
+int mpsk_hsum_destroy(mpsk_hsum* s) {
+  if (s) hsum_free(s);
   return MPSK_OK;
 }
 

@@ -174,6 +174,19 @@ hipError_t vec_multiaxpy_c(const double* const* xs, const double* d_coefs, int k
 hipError_t vec_cgs2_c(const double* const* xs, int k, double* y, int64_t n, double* d_out, double* d_partial, hipStream_t s);
 hipError_t vec_axpby_c(const double a[2], const double* x, const double b[2], double* y, int64_t n, hipStream_t s);
 hipError_t identity_dev_c(const double* G, int n, double* d_out, int nblocks, hipStream_t s);   // d_out[b]: per-block max|G - I|
+// dstR = sum_k coef[k] srcR[k] (nR doubles) and dstL = sum_k coef[k] srcL[k] (nL doubles) in ONE launch, terms in the order
+// k = 0 .. n-1 (bit-reproducible); everything is passed by value.  All pointers 16-byte aligned.  The fold pair of a summed
+// mode-3 operator (mpsk_hsum_set_coefs).
+constexpr int MPSK_HSUM_MAX = 8;
+struct FoldLincombArgs {
+  const double* srcR[MPSK_HSUM_MAX];
+  const double* srcL[MPSK_HSUM_MAX];
+  double coef[MPSK_HSUM_MAX];
+  double *dstR, *dstL;
+  int64_t nR, nL;
+  int n;
+};
+hipError_t fold_lincomb(const FoldLincombArgs& a, hipStream_t s);
 // d_out[w][t,s] = sum_{p,b} conj(Ab[p,t,b]) X[w][p,s,b]: X W tensors [Dl,d,Dr], Ab [Dl,d,Dr] (interleaved when cplx), d_out
 // W column-major d x d matrices; d_partial: site_gram_partial_doubles(W, d, cplx) doubles of scratch.  Asynchronous,
 // deterministic (fixed-order partial sums + dot_final_kernel).

@@ -1080,4 +1080,57 @@ hipError_t identity_dev_c(const double* G, int n, double* d_out, int nblocks, hi
   return hipGetLastError();
 }
 
+// Fold pair of a summed Jordan-form operator: dst = sum_k coef[k] src[k] over both fold buffers in one launch.  The work is
+// cut into chunks of FOLD_CHUNK 16-byte pairs (the R buffer's chunks first, then the L buffer's); a block takes whole
+// chunks, grid-strided.  Every element is summed in the term order k = 0 .. n-1 by one thread, so the result does not depend on the
+// grid.  Sources, destinations and coefficients arrive by value (no upload, nothing to wait for).
+constexpr int FOLD_CHUNK = 1024;
+__device__ __forceinline__ double fold_term(const FoldLincombArgs& a, bool left, int k, int64_t e) {
+  return (left ? a.srcL[k] : a.srcR[k])[e];
+}
+__global__ __launch_bounds__(256) void fold_lincomb_kernel(const FoldLincombArgs a) {
+  const int64_t vR = a.nR / 2, vL = a.nL / 2;                    // whole 16-byte pairs; an odd last element: below
+  const int64_t cR = (vR + FOLD_CHUNK - 1) / FOLD_CHUNK, cL = (vL + FOLD_CHUNK - 1) / FOLD_CHUNK;
+  for (int64_t ch = blockIdx.x; ch < cR + cL; ch += gridDim.x) {
+    const bool left = ch >= cR;
+    const int64_t base = (left ? ch - cR : ch) * FOLD_CHUNK, nv = left ? vL : vR;
+    d2* __restrict__ dst = reinterpret_cast<d2*>(left ? a.dstL : a.dstR);
+    for (int i = threadIdx.x; i < FOLD_CHUNK; i += 256) {
+      const int64_t e = base + i;
+      if (e >= nv) break;
+      d2 acc;
+      acc.x = 0.0; acc.y = 0.0;
+#pragma unroll
+      for (int k = 0; k < MPSK_HSUM_MAX; ++k)
+        if (k < a.n) {
+          const d2 v = reinterpret_cast<const d2*>(left ? a.srcL[k] : a.srcR[k])[e];
+          if (k == 0) { acc.x = a.coef[0] * v.x; acc.y = a.coef[0] * v.y; }
+          else { acc.x = fma(a.coef[k], v.x, acc.x); acc.y = fma(a.coef[k], v.y, acc.y); }
+        }
+      dst[e] = acc;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 2) {
+    const bool left = threadIdx.x == 1;
+    const int64_t nn = left ? a.nL : a.nR;
+    if (nn & 1) {
+      const int64_t e = nn - 1;
+      double acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < MPSK_HSUM_MAX; ++k)
+        if (k < a.n) acc = k == 0 ? a.coef[0] * fold_term(a, left, 0, e) : fma(a.coef[k], fold_term(a, left, k, e), acc);
+      (left ? a.dstL : a.dstR)[e] = acc;
+    }
+  }
+}
+
+hipError_t fold_lincomb(const FoldLincombArgs& a, hipStream_t s) {
+  if (a.n < 1 || a.n > MPSK_HSUM_MAX) return hipErrorInvalidValue;
+  const int64_t chunks = (a.nR / 2 + FOLD_CHUNK - 1) / FOLD_CHUNK + (a.nL / 2 + FOLD_CHUNK - 1) / FOLD_CHUNK;
+  int64_t nb = chunks < 1 ? 1 : chunks;
+  if (nb > 2048) nb = 2048;
+  hipLaunchKernelGGL(fold_lincomb_kernel, dim3((unsigned)nb), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace mpsk

@@ -3,6 +3,8 @@ Same names and call convention as the reference: `h = ddAC(pos, psi, H, envs); y
 `h * x`; every application is ONE call into libmpsk (mpsk_dAC / mpsk_dC / mpsk_dAC2)."""
 from __future__ import annotations
 
+import os
+
 from .backend import DTensor
 
 
@@ -88,7 +90,124 @@ class LazyDerivativeSum:  # derivatives.jl:310-323 : (h::LazySum{<:DerivativeOpe
     __mul__ = __call__
 
 
+class _ComposedAt:
+    """sum_k c_k h_k(x) at fixed numbers c_k, term by term (the composed route of a timed sum): every term writes into a
+    buffer that is kept, the first one straight into `out`."""
+
+    def __init__(self, be, terms, coefs, owner):
+        self.be, self.terms, self.coefs, self.owner = be, terms, coefs, owner
+
+    def __call__(self, x: DTensor, out: DTensor = None):
+        be = self.be
+        y = self.terms[0](x, out=out)
+        if self.coefs[0] != 1.0:
+            be.scal(self.coefs[0], y)
+        for c, h in zip(self.coefs[1:], self.terms[1:]):
+            tmp = self.owner._tmp
+            if tmp is None or tmp.shape != y.shape:
+                tmp = self.owner._tmp = be.empty(*y.shape)
+            be.axpby(c, h(x, out=tmp), 1.0, y)
+        return y
+
+    __mul__ = __call__
+
+
+class _HSumAt:
+    """the prepared sum (mpsk_hsum) with the coefficients it was last given: one library call per application."""
+
+    def __init__(self, hsum):
+        self.hsum = hsum
+
+    def __call__(self, x: DTensor, out: DTensor = None):
+        return self.hsum.apply(x, out=out)
+
+    __mul__ = __call__
+
+    def apply_axpby(self, a1, x: DTensor, a0, out: DTensor = None):
+        return self.hsum.apply_axpby(a1, x, a0, out=out)
+
+
+class TimedDerivativeSum:  # derivatives.jl:283-323
+    """Effective Hamiltonian of a MultipliedOperator / of a LazySum with prefactors f_k that may depend on time: callable
+    as h(x, t) (and as h(x) when no f_k is a function); h.at(t) is the operator at the fixed time t, which is what an
+    integrator applies many times.  With `hsum` (a zero-argument factory of a backend PreparedHSum over the same terms) and
+    real f_k(t) the fixed-time operator is the device-side sum: built once per site visit, set_coefs once per time."""
+
+    def __init__(self, be, terms, fs, hsum=None, wrap=None):
+        self.be, self.terms, self.fs = be, list(terms), list(fs)
+        self.timed = any(callable(f) for f in self.fs)
+        self._make, self._hsum, self._tmp = hsum, None, None
+        self._wrap = wrap                # embedded complex states: the device sum iterates on half-embedded vectors
+
+    def coefs(self, t=None):
+        if self.timed and t is None:
+            raise ValueError("a time-dependent effective Hamiltonian needs its time: h(x, t).  Only the time-evolution "
+                             "drivers pass one; every other driver takes the evaluated operator H(t)")
+        return [f(t) if callable(f) else f for f in self.fs]
+
+    def at(self, t=None):
+        cs = self.coefs(t)
+        if self._make is not None and all(complex(c).imag == 0.0 for c in cs):
+            if self._hsum is None:
+                self._hsum = self._make()
+            self._hsum.set_coefs([complex(c).real for c in cs])
+            op = _HSumAt(self._hsum)
+            return op if self._wrap is None else self._wrap(op)
+        cs = [complex(c).real if complex(c).imag == 0.0 else complex(c) for c in cs]
+        if any(isinstance(c, complex) for c in cs):
+            raise NotImplementedError("complex-valued prefactors f(t) are not implemented, on any kind of state: with an "
+                                      "imaginary step the midpoint t + dt/2 is complex, so f must return a real number there")
+        return _ComposedAt(self.be, self.terms, cs, self)
+
+    def __call__(self, x: DTensor, t=None, out: DTensor = None):
+        if isinstance(t, DTensor):                           # h(x, out) of the untimed case
+            t, out = None, t
+        return self.at(t)(x, out=out)
+
+    __mul__ = __call__
+
+    def info(self):
+        """route of the device-side sum (mpsk_hsum_info), None while / where the composed route is used."""
+        return None if self._hsum is None else self._hsum.info()
+
+
+def _timed_lazy(fn, pos, psi, H, envs):
+    """derivative of a timed LazySum: the terms as a sum builds them, the prefactors kept as functions.  ddAC on plain
+    finite / infinite Hamiltonian environments of a real state goes through mpsk_hsum (folded on canonical finite
+    environments, accumulated otherwise); everything else is composed."""
+    from .environments import FinEnv, MPOHamInfEnv
+    be = psi.be
+    cx = getattr(psi, "cplx", False)
+    es = envs.envs
+    make = wrap = None
+    on = os.environ.get("MPSK_HSUM", "1") != "0"              # "0": always the composed route (A/B switch)
+    if (fn is ddAC and on and hasattr(be, "hsum_create") and len(es) <= 8
+            and (all(type(e) is FinEnv for e in es) or all(type(e) is MPOHamInfEnv for e in es))):
+        opps = [e.opp[pos] if hasattr(e, "opp") else h[pos] for h, e in zip(H, es)]
+        GLs = [e.leftenv(pos, psi) for e in es]
+        GRs = [e.rightenv(pos, psi) for e in es]
+        if not cx:
+            canonical = all(type(e) is FinEnv and e._canonical(psi) for e in es)
+            make = lambda: be.hsum_create(opps, GLs, GRs, canonical=canonical)
+        elif not any(_native_cplx(psi, gl, gr) for gl, gr in zip(GLs, GRs)):
+            # embedded complex state: the real slices on the embedded (doubled) environments, accumulated route
+            make = lambda: be.hsum_create(opps, GLs, GRs)
+            wrap = lambda op: _half_space(psi, op, "AC", GRs[0])
+    kw = {"canonical": False} if fn is ddAC else {}
+    terms = [fn(pos, psi, h, e, **kw) for h, e in zip(H, es)]
+    if cx and any(hasattr(e, "vector") for e in es):
+        raise NotImplementedError("a timed sum with a projector term on an embedded complex state")
+    return TimedDerivativeSum(be, terms, H._fs, hsum=make, wrap=wrap)
+
+
+def _multiplied(fn, pos, psi, H, envs):
+    """derivative of a MultipliedOperator f * op (derivatives.jl:283-308): f times the derivative of op."""
+    return TimedDerivativeSum(psi.be, [fn(pos, psi, H.op, envs)], [H.f])
+
+
 def _lazy(fn, pos, psi, H, envs):
+    if getattr(H, "timed", False):
+        return _timed_lazy(fn, pos, psi, H, envs)
     kw = {"canonical": False} if fn is ddAC else {}          # the terms of a sum keep the dense operator
     op = LazyDerivativeSum(psi.be, [fn(pos, psi, h, e, **kw) for h, e in zip(H, envs.envs)], H.fs)
     if getattr(psi, "cplx", False) and any(hasattr(e, "vector") for e in envs.envs):
@@ -102,7 +221,12 @@ def _lazy(fn, pos, psi, H, envs):
 
 
 def _is_lazy(H, envs):
-    return hasattr(envs, "envs") and hasattr(H, "fs")
+    return hasattr(envs, "envs") and (hasattr(H, "_fs") or hasattr(H, "fs"))
+
+
+def _is_multiplied(H):
+    from .operators import MultipliedOperator
+    return isinstance(H, MultipliedOperator)
 
 
 NATIVE_CPLX_MIN_D = 384     # embedded bond dimension 2 D below which the embedded matvec wins (launch-bound regime:
@@ -112,7 +236,6 @@ NATIVE_CPLX_MIN_D = 384     # embedded bond dimension 2 D below which the embedd
 def _native_cplx(psi, *envs_):
     """complex (embedded) state on a backend with the MPSK_C128 kernels: apply through cplx.HalfEmbeddedOp when the
     tensors are large enough for the halved flop count to matter."""
-    import os
     if not (getattr(psi, "cplx", False) and hasattr(psi.be, "hac_create")):
         return False
     mode = os.environ.get("MPSK_NATIVE_CPLX", "auto")          # "0": always embedded, "1": always native (A/B switch)
@@ -136,6 +259,8 @@ def _half_space(psi, op, kind, GR):
 
 
 def ddC(pos, psi, H, envs):  # ∂∂C  derivatives.jl:34-36
+    if _is_multiplied(H):
+        return _multiplied(ddC, pos, psi, H, envs)
     if _is_lazy(H, envs):
         return _lazy(ddC, pos, psi, H, envs)
     if _native_cplx(psi, envs.leftenv(pos + 1, psi), envs.rightenv(pos, psi)):
@@ -149,6 +274,8 @@ def ddAC(pos, psi, H, envs, canonical=None):  # ∂∂AC  derivatives.jl:44-46
     """canonical: None = decide here -- only the environments of a plain FinEnv on a real state are canonical (level 0 of
     GL and level W-1 of GR identities); every other kind (sums, projectors, infinite / sharded environments) and every
     complex state keeps the dense operator."""
+    if _is_multiplied(H):
+        return _multiplied(ddAC, pos, psi, H, envs)
     if _is_lazy(H, envs):
         return _lazy(ddAC, pos, psi, H, envs)
     if hasattr(envs, "vector"):          # ProjectionOperator term (excitations.py): rank-one |v><v|
@@ -166,6 +293,8 @@ def ddAC(pos, psi, H, envs, canonical=None):  # ∂∂AC  derivatives.jl:44-46
 
 
 def ddAC2(pos, psi, H, envs):  # ∂∂AC2  derivatives.jl:55-58
+    if _is_multiplied(H):
+        return _multiplied(ddAC2, pos, psi, H, envs)
     if _is_lazy(H, envs):
         return _lazy(ddAC2, pos, psi, H, envs)
     o1 = envs.opp[pos] if hasattr(envs, "opp") else H[pos]

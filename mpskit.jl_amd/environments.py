@@ -173,6 +173,8 @@ class MultipleEnvironments:
 
     def __init__(self, H, envs):
         self.H, self.envs = H, list(envs)
+        if getattr(H, "timed", False):       # a timed sum folds its terms on canonical environments (mpsk_hsum, route 1)
+            return
         for e in self.envs:                  # the terms of a sum keep the dense transfers (as ddAC keeps their dense operator)
             if isinstance(e, FinEnv):
                 e.canonical = False
@@ -187,8 +189,10 @@ def environments(psi, H, **kw):
     """environments(psi, H)  (FinEnv.jl:41-70 / mpohaminfenv.jl:40-44 / multipleenv.jl:30-34; a DenseMPO:
     permpoinfenv.jl:20-29, an InfiniteMPS with H = (O, above): permpoinfenv.jl:29-42, both statmech.PerMPOInfEnv)."""
     from .states import FiniteMPS
-    from .operators import LazySum
+    from .operators import LazySum, MultipliedOperator
     from .statmech import DenseMPO, PerMPOInfEnv
+    if isinstance(H, MultipliedOperator):                                       # multipliedoperator.jl:50-52
+        return environments(psi, H.op, **kw)
     if isinstance(psi, FiniteMPS) and isinstance(H, (tuple, FiniteMPS)):       # FinEnv.jl:21-23, :91-99
         O, above = H if isinstance(H, tuple) else (None, H)
         return FinEnvPair(psi, O, above)

@@ -17,6 +17,8 @@ representation; the Krylov solvers are shared (real inner products on the 2n dou
 Hermitian Lanczos / Arnoldi iteration needs, and multiplication by i is mpsk_vtimes_i)."""
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 from .backend import Backend, DTensor
@@ -189,6 +191,108 @@ class NativeFinEnv:
         return 8 * sum(t.size for t in self.GL + self.GR if t is not None)
 
 
+def _sum_terms(H):
+    """(operators, prefactors) of a LazySum / MultipliedOperator, None for a plain operator."""
+    from .operators import LazySum, MultipliedOperator
+    if isinstance(H, LazySum):
+        return list(H), list(H._fs)
+    if isinstance(H, MultipliedOperator):
+        return [H.op], [H.f]
+    return None
+
+
+class NativeMultipleEnv:
+    """MultipleEnvironments (multipleenv.jl) for interleaved states: one NativeFinEnv per term of a LazySum (or the one of a
+    MultipliedOperator), moved together; `fs` are the prefactors, numbers or functions of time.  The environments of a
+    NativeFiniteMPS are canonical, so the one-site generator of the sum is the folded mpsk_hsum (MPSK_HAC_CANONICAL_C128)."""
+
+    def __init__(self, psi: NativeFiniteMPS, H):
+        ops, self.fs = _sum_terms(H)
+        self.be, self.H = psi.be, H
+        self.envs = [NativeFinEnv(psi, o) for o in ops]
+        self.timed = any(callable(f) for f in self.fs)
+        self.routes = set()              # routes the device-side sums took so far (mpsk_hsum_info), for inspection
+
+    def extend_left(self, psi, j):
+        for e in self.envs:
+            e.extend_left(psi, j)
+
+    def extend_right(self, psi, j):
+        for e in self.envs:
+            e.extend_right(psi, j)
+
+    @property
+    def n_transfers(self):
+        return sum(e.n_transfers for e in self.envs)
+
+    def coefs(self, t):
+        if self.timed and t is None:
+            raise ValueError("a time-dependent sum needs its time")
+        cs = [f(t) if callable(f) else f for f in self.fs]
+        if any(complex(c).imag != 0.0 for c in cs):
+            raise NotImplementedError("complex-valued prefactors f(t) on interleaved states are not implemented")
+        return [complex(c).real for c in cs]
+
+
+class _SumOp:
+    """sum_k c_k op_k(x) at fixed real numbers c_k, term by term, on interleaved vectors."""
+
+    def __init__(self, be, ops, coefs):
+        self.be, self.ops, self.coefs, self._tmp = be, ops, coefs, None
+
+    def __call__(self, x, out=None):
+        be = self.be
+        y = self.ops[0](x, out=out)
+        if self.coefs[0] != 1.0:
+            be.scal(self.coefs[0], y)
+        for c, op in zip(self.coefs[1:], self.ops[1:]):
+            if self._tmp is None or self._tmp.shape != y.shape:
+                self._tmp = be.empty(*y.shape)
+            be.axpby(c, op(x, out=self._tmp), 1.0, y)
+        return y
+
+
+def _eval_time(t, dt, frac):
+    """t + frac dt, a float when it is real (integrators.jl:20-25: the midpoint of the sub-step)"""
+    te = complex(t) + frac * complex(dt)
+    return te.real if te.imag == 0.0 else te
+
+
+def _gen_ac(be, envs, pos, te):
+    """H_AC of site pos at the evaluation time te"""
+    if not isinstance(envs, NativeMultipleEnv):
+        return _HAC(be, envs, pos)
+    cs = envs.coefs(te)
+    es = envs.envs
+    if hasattr(be, "hsum_create") and len(es) <= 8 and os.environ.get("MPSK_HSUM", "1") != "0":
+        h = be.hsum_create([e.opp[pos] for e in es], [e.GL[pos] for e in es], [e.GR[pos + 1] for e in es],
+                           canonical_c128=True)
+        h.set_coefs(cs)
+        envs.routes.add(h.info()["route"])
+        return lambda x, out=None: h.apply(x, out=out)
+    return _SumOp(be, [_HAC(be, e, pos) for e in es], cs)
+
+
+def _gen_c(be, envs, GLi, GRi, te):
+    """H_C on the bond whose environments are GL[GLi] and GR[GRi]"""
+    def one(e):
+        hc = _HC.__new__(_HC)
+        hc.be, hc.GL, hc.GR = be, e.GL[GLi], e.GR[GRi]
+        return hc
+    if not isinstance(envs, NativeMultipleEnv):
+        return one(envs)
+    return _SumOp(be, [one(e) for e in envs.envs], envs.coefs(te))
+
+
+def _gen_ac2(be, envs, pos, te):
+    def one(e):
+        h1, h2, GL, GR = e.opp[pos], e.opp[pos + 1], e.GL[pos], e.GR[pos + 2]
+        return lambda x, out=None: be.dAC2(h1, h2, GL, GR, x, out=out)
+    if not isinstance(envs, NativeMultipleEnv):
+        return one(envs)
+    return _SumOp(be, [one(e) for e in envs.envs], envs.coefs(te))
+
+
 class _HAC:
     """H_AC of the centre site on interleaved vectors (derivatives.jl:77-93): prepared operator, one call per application."""
 
@@ -209,11 +313,12 @@ class _HC:
         return self.be.dC(self.GL, self.GR, x, out=out, cplx=True)
 
 
-def energy(psi: NativeFiniteMPS, envs: NativeFinEnv):
-    """<psi|H|psi> / <psi|psi> at the current centre (Re <AC, H_AC AC>; the imaginary part vanishes for Hermitian H)."""
+def energy(psi: NativeFiniteMPS, envs: NativeFinEnv, t=None):
+    """<psi|H|psi> / <psi|psi> at the current centre (Re <AC, H_AC AC>; the imaginary part vanishes for Hermitian H).
+    t: the time of a time-dependent sum (NativeMultipleEnv)."""
     be = psi.be
     ac = psi.A[psi.center]
-    return be.dot(ac, _HAC(be, envs, psi.center)(ac)) / be.dot(ac, ac)
+    return be.dot(ac, _gen_ac(be, envs, psi.center, t)(ac)) / be.dot(ac, ac)
 
 
 def dmrg_sweep(psi: NativeFiniteMPS, H, envs: NativeFinEnv, eigalg, ws=None):
@@ -264,31 +369,31 @@ def tdvp_step(psi: NativeFiniteMPS, H, envs: NativeFinEnv, t, dt, alg, ws=None):
     ws = krylov.KrylovWorkspace(be) if ws is None else ws
     psi.move_center(0)
     fwd, bwd = -1j * complex(dt) / 2, 1j * complex(dt) / 2
+    # evaluation times of a time-dependent generator (tdvp.jl:61-91 through integrators.jl:20-25)
+    t_ac1, t_c1, t_ac2, t_c2 = (_eval_time(t, dt, f) for f in (0.25, -0.25, 0.75, 0.25))
     for i in range(L - 1):
-        psi.A[i] = _integrate_embedded(be, _HAC(be, envs, i), psi.A[i], fwd, alg, ws)
+        psi.A[i] = _integrate_embedded(be, _gen_ac(be, envs, i, t_ac1), psi.A[i], fwd, alg, ws)
         Dl, d, Dr = psi.dims(i)
         Q, R = be.qrpos_c(_mat(psi.A[i], 2 * Dl * d, Dr))
         psi.A[i] = Q.reshape(2 * Dl, d, R.shape[1])
         envs.extend_left(psi, i)
-        C = _integrate_embedded(be, _HC(be, envs, i), R, bwd, alg, ws)
+        C = _integrate_embedded(be, _gen_c(be, envs, i + 1, i + 1, t_c1), R, bwd, alg, ws)
         Dn, dn, Drn = psi.dims(i + 1)
         psi.A[i + 1] = be.gemm_c(C, _mat(psi.A[i + 1], 2 * Dn, dn * Drn)).reshape(2 * C.shape[0] // 2, dn, Drn)
         psi.center = i + 1
-    psi.A[L - 1] = _integrate_embedded(be, _HAC(be, envs, L - 1), psi.A[L - 1], fwd, alg, ws)
+    psi.A[L - 1] = _integrate_embedded(be, _gen_ac(be, envs, L - 1, t_ac1), psi.A[L - 1], fwd, alg, ws)
     for i in range(L - 1, 0, -1):
-        psi.A[i] = _integrate_embedded(be, _HAC(be, envs, i), psi.A[i], fwd, alg, ws)
+        psi.A[i] = _integrate_embedded(be, _gen_ac(be, envs, i, t_ac2), psi.A[i], fwd, alg, ws)
         Dl, d, Dr = psi.dims(i)
         Lm, Q = be.lqpos_c(_mat(psi.A[i], 2 * Dl, d * Dr))
         psi.A[i] = Q.reshape(2 * Lm.shape[1], d, Dr)
         envs.extend_right(psi, i)
         # the bond matrix between i - 1 and i: H_C with GL[i] and GR[i]
-        hc = _HC.__new__(_HC)
-        hc.be, hc.GL, hc.GR = be, envs.GL[i], envs.GR[i]
-        C = _integrate_embedded(be, hc, Lm, bwd, alg, ws)
+        C = _integrate_embedded(be, _gen_c(be, envs, i, i, t_c2), Lm, bwd, alg, ws)
         Dp, dp, Drp = psi.dims(i - 1)
         psi.A[i - 1] = be.gemm_c(_mat(psi.A[i - 1], 2 * Dp * dp, Drp), C).reshape(2 * Dp, dp, C.shape[1])
         psi.center = i - 1
-    psi.A[0] = _integrate_embedded(be, _HAC(be, envs, 0), psi.A[0], fwd, alg, ws)
+    psi.A[0] = _integrate_embedded(be, _gen_ac(be, envs, 0, t_ac2), psi.A[0], fwd, alg, ws)
     return psi, envs
 
 
@@ -364,11 +469,11 @@ def tdvp2_step(psi: NativeFiniteMPS, H, envs: NativeFinEnv, t, dt, alg, trunc_di
     ws = krylov.KrylovWorkspace(be) if ws is None else ws
     psi.move_center(0)
     fwd, bwd = -1j * complex(dt) / 2, 1j * complex(dt) / 2
+    # evaluation times of a time-dependent generator (tdvp.jl:113-146 through integrators.jl:20-25)
+    t_f2, t_f1, t_b2, t_b1 = (_eval_time(t, dt, f) for f in (0.25, -0.25, 0.75, 0.25))
 
-    def evolve_and_split(pos, theta):
-        h1, h2, GL, GR = envs.opp[pos], envs.opp[pos + 1], envs.GL[pos], envs.GR[pos + 2]
-        op = lambda x, out=None: be.dAC2(h1, h2, GL, GR, x, out=out)
-        new = _integrate_embedded(be, op, theta, fwd, alg, ws)
+    def evolve_and_split(pos, theta, te):
+        new = _integrate_embedded(be, _gen_ac2(be, envs, pos, te), theta, fwd, alg, ws)
         Dl2, d1, Dr, d2 = new.shape
         al, c, arm, _, _ = _split(be, new.reshape(Dl2 * d1, Dr * d2), trunc_dim, trunc_err)
         k = c.shape[1]
@@ -378,23 +483,23 @@ def tdvp2_step(psi: NativeFiniteMPS, H, envs: NativeFinEnv, t, dt, alg, trunc_di
         return al.reshape(Dl2, d1, k), c, ar
 
     for i in range(L - 1):
-        al, c, ar = evolve_and_split(i, _two_site(be, psi.A[i], psi.A[i + 1]))
+        al, c, ar = evolve_and_split(i, _two_site(be, psi.A[i], psi.A[i + 1]), t_f2)
         k, d2, Dr = c.shape[1], ar.shape[1], ar.shape[2]
         psi.A[i] = al
         psi.A[i + 1] = be.gemm_c(c, ar.reshape(2 * k, d2 * Dr)).reshape(2 * k, d2, Dr)
         psi.center = i + 1
         envs.extend_left(psi, i)
         if i != L - 2:
-            psi.A[i + 1] = _integrate_embedded(be, _HAC(be, envs, i + 1), psi.A[i + 1], bwd, alg, ws)
+            psi.A[i + 1] = _integrate_embedded(be, _gen_ac(be, envs, i + 1, t_f1), psi.A[i + 1], bwd, alg, ws)
     for i in range(L - 1, 0, -1):
-        al, c, ar = evolve_and_split(i - 1, _two_site(be, psi.A[i - 1], psi.A[i]))
+        al, c, ar = evolve_and_split(i - 1, _two_site(be, psi.A[i - 1], psi.A[i]), t_b2)
         Dl2, d1, k = al.shape
         psi.A[i] = ar
         psi.A[i - 1] = be.gemm_c(al.reshape(Dl2 * d1, k), c).reshape(Dl2, d1, k)
         psi.center = i - 1
         envs.extend_right(psi, i)
         if i != 1:
-            psi.A[i - 1] = _integrate_embedded(be, _HAC(be, envs, i - 1), psi.A[i - 1], bwd, alg, ws)
+            psi.A[i - 1] = _integrate_embedded(be, _gen_ac(be, envs, i - 1, t_b1), psi.A[i - 1], bwd, alg, ws)
     return psi, envs
 
 
@@ -573,9 +678,11 @@ def propagator(psi0: NativeFiniteMPS, z, H, alg=None, init: NativeFiniteMPS = No
 
 
 def timestep(psi: NativeFiniteMPS, H, t, dt, alg, envs: NativeFinEnv = None):
-    """timestep(psi, H, t, dt, TDVP() | TDVP2(...))  (tdvp.jl:61-94, :113-146).  Returns (psi, envs)."""
+    """timestep(psi, H, t, dt, TDVP() | TDVP2(...))  (tdvp.jl:61-94, :113-146).  H: an MPOHamiltonian, or a LazySum /
+    MultipliedOperator of them, timed or not (environments: NativeMultipleEnv).  Returns (psi, envs)."""
     from .algorithms import TDVP, TDVP2
-    envs = NativeFinEnv(psi, H) if envs is None else envs
+    if envs is None:
+        envs = NativeFinEnv(psi, H) if _sum_terms(H) is None else NativeMultipleEnv(psi, H)
     if isinstance(alg, TDVP2):
         trunc_err = alg.trunc_err if alg.trunc_dim <= 0 else 0.0
         return tdvp2_step(psi, H, envs, t, dt, alg, alg.trunc_dim, trunc_err=trunc_err)

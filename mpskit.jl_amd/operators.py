@@ -91,6 +91,11 @@ class MPOHamiltonian:
                 raise ValueError(f"periodicity should match {self.period} != {other.period}")
             data, dims = _mpo_product_data(other._src(), self._src(), self.d)
             return MPOHamiltonian(data, d=self.d, chis=dims, be=self.be)
+        if isinstance(other, (MultipliedOperator, LazySum)):      # both are callable, neither is a prefactor
+            raise TypeError("the product of an MPOHamiltonian with a MultipliedOperator / LazySum is not defined: "
+                            "multiply the operators first, then attach the prefactor")
+        if callable(other):                              # op * f(t): a TimedOperator (multipliedoperator.jl:40-46)
+            return MultipliedOperator(self, other)
         data = []
         for sl in self.slices:
             blk = dict(sl.blocks)
@@ -107,6 +112,8 @@ class MPOHamiltonian:
 
     def __add__(self, e):
         """H + e (mpohamiltonian.jl:78-94): e[c] * identity added to the on-site block (1, odim) of site c; H + H' is LazySum's job."""
+        if isinstance(e, (MultipliedOperator, LazySum)):  # H + f * H': their __radd__ builds the LazySum
+            return NotImplemented
         e = np.broadcast_to(np.asarray(e, dtype=float), (self.period,))
         data = []
         for c, sl in enumerate(self.slices):
@@ -372,18 +379,133 @@ def hubbard(t=1.0, U=4.0, be=None):
                            (0, 3): -t * (cd.T @ F), (3, 5): cd, (0, 4): t * (cd @ F), (4, 5): cd.T}, be=be)
 
 
-class LazySum(list):
-    """LazySum(ops[, fs])  (src/operators/lazysum.jl:16-59): a sum of operators that is never formed; every
-    effective Hamiltonian / expectation value is the (weighted) sum of the terms' own (multipleenv.jl,
-    derivatives.jl:310-323).  fs: optional scalar prefactors (MultipliedOperator with constant factors)."""
+def _untimed_error():
+    # the reference's ArgumentError of lazysum.jl:36-43
+    return ValueError("LazySum is untimed: it has no time argument (and a timed LazySum has no fixed prefactors: "
+                      "evaluate it first, H(t))")
 
-    def __init__(self, ops, fs=None):
-        super().__init__(ops)
-        self.fs = [1.0] * len(self) if fs is None else [float(f) for f in fs]
-        if len(self.fs) != len(self):
-            raise ValueError("LazySum: one prefactor per operator")
+
+class MultipliedOperator:
+    """MultipliedOperator(op, f)  (src/operators/multipliedoperator.jl:1-52): the operator f * op that is never formed.
+    f is a number (UntimedOperator) or a callable t -> number (TimedOperator, timedependence.jl).  x(t) on a timed operator
+    is the untimed one with the number f(t); x() on an untimed one is the plain product f * op."""
+
+    def __init__(self, op, f=1.0):
+        if isinstance(op, MultipliedOperator):          # (f g) * op
+            g = op.f
+            op = op.op
+            if callable(f) and callable(g):
+                f = (lambda a, b: lambda t: a(t) * b(t))(f, g)
+            elif callable(f):
+                f = (lambda a, b: lambda t: a(t) * b)(f, g)
+            elif callable(g):
+                f = (lambda a, b: lambda t: a * b(t))(f, g)
+            else:
+                f = f * g
+        self.op, self.f = op, f
+
+    @property
+    def timed(self):
+        return callable(self.f)
+
+    def __call__(self, *t):
+        if self.timed:
+            if len(t) != 1:
+                raise ValueError("a TimedOperator is evaluated at one time: x(t)")
+            return MultipliedOperator(self.op, self.f(t[0]))
+        if t:
+            raise ValueError("an UntimedOperator has no time argument: x()")
+        return self.op * self.f
+
+    def __mul__(self, b):                                # multipliedoperator.jl:40-46
+        if isinstance(b, (MultipliedOperator, LazySum)):
+            return NotImplemented
+        if callable(b) or np.isscalar(b):
+            return MultipliedOperator(self, b)
+        return NotImplemented
+
+    __rmul__ = __mul__
 
     def __add__(self, other):
         if isinstance(other, LazySum):
-            return LazySum(list(self) + list(other), self.fs + other.fs)
-        return LazySum(list(self) + [other], self.fs + [1.0])
+            return LazySum([self.op] + list(other), [self.f] + list(other._fs))
+        if isinstance(other, MultipliedOperator):
+            return LazySum([self.op, other.op], [self.f, other.f])
+        return LazySum([self.op, other], [self.f, 1.0])
+
+    def __radd__(self, other):
+        return LazySum([other, self.op], [1.0, self.f])
+
+    def repeat(self, n):
+        return MultipliedOperator(self.op.repeat(n), self.f)
+
+
+def TimedOperator(op, f=None):
+    """TimedOperator(op[, f])  (timedependence.jl): f(t) * op; without f the constant function 1."""
+    return MultipliedOperator(op, (lambda t: 1.0) if f is None else f)
+
+
+def UntimedOperator(op, f=1.0):
+    """UntimedOperator(op[, f])  (timedependence.jl): the number f times op, kept unformed."""
+    if callable(f):
+        raise TypeError("UntimedOperator takes a number; a function of time makes a TimedOperator")
+    return MultipliedOperator(op, f)
+
+
+def istimed(x):
+    """istimed(x)  (timedependence.jl): does x carry an explicit time dependence?"""
+    if isinstance(x, MultipliedOperator):
+        return x.timed
+    if isinstance(x, LazySum):
+        return x.timed
+    return False
+
+
+class LazySum(list):
+    """LazySum(ops[, fs])  (src/operators/lazysum.jl:16-59): a sum of operators that is never formed; every
+    effective Hamiltonian / expectation value is the (weighted) sum of the terms' own (multipleenv.jl,
+    derivatives.jl:310-323).  fs: optional prefactors (MultipliedOperator terms): numbers, or callables t -> number,
+    which make the sum timed: H(t) is then the untimed sum with the numbers f_k(t), and H.fs does not exist."""
+
+    def __init__(self, ops, fs=None):
+        ops = list(ops)
+        fs = [1.0] * len(ops) if fs is None else list(fs)
+        if len(fs) != len(ops):
+            raise ValueError("LazySum: one prefactor per operator")
+        for k, o in enumerate(ops):                      # MultipliedOperator terms hand their factor to the sum
+            if isinstance(o, MultipliedOperator):
+                m = MultipliedOperator(o, fs[k])
+                ops[k], fs[k] = m.op, m.f
+        super().__init__(ops)
+        self.timed = any(callable(f) for f in fs)
+        self._fs = fs if self.timed else [float(f) for f in fs]
+
+    @property
+    def fs(self):
+        if self.timed:
+            raise _untimed_error()
+        return self._fs
+
+    def coefs(self, t=None):
+        """the numbers f_k(t) (timed) / f_k (untimed, t ignored)."""
+        if self.timed and t is None:
+            raise ValueError("a timed LazySum needs a time: H(t)")
+        return [f(t) if callable(f) else f for f in self._fs]
+
+    def __call__(self, *t):
+        if not self.timed or len(t) != 1:
+            raise _untimed_error()
+        return LazySum(list(self), self.coefs(t[0]))
+
+    def __add__(self, other):
+        if isinstance(other, LazySum):
+            return LazySum(list(self) + list(other), self._fs + other._fs)
+        if isinstance(other, MultipliedOperator):
+            return LazySum(list(self) + [other.op], self._fs + [other.f])
+        return LazySum(list(self) + [other], self._fs + [1.0])
+
+    def __radd__(self, other):
+        return LazySum([other] + list(self), [1.0] + self._fs)
+
+    def repeat(self, n):
+        return LazySum([o.repeat(n) for o in self], self._fs)
