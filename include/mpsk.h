@@ -383,7 +383,11 @@ int mpsk_regularize(mpsk_ctx* ctx, int W, int D1, int D2, void* v, const void* l
 
 /* ---- gauge steps: TensorKit leftorth!(QRpos) / rightorth!(LQpos) / tsvd! ----------------------
  * call sites: src/states/orthoview.jl:52,56 ; finitemps.jl:149 ; ortho.jl:128-136 ; dmrg.jl:96 */
-/* A (m x n, m >= n, lda) = Q (m x n, ldq) * R (n x n upper, ldr), diag(R) > 0.  A is not modified. */
+/* A (m x n, m >= n, lda) = Q (m x n, ldq) * R (n x n upper, ldr), diag(R) > 0.  A is not modified.
+ * Row limit: a call that takes the blocked Householder route -- every call with n <= 64 (complex: n <= 32), qr mode 1, and
+ * the last fallback of the CholeskyQR ladder -- needs m <= 19712 (complex: m <= 9856, the embedding doubles the rows): one
+ * panel column has to fit the LDS.  Above it the call fails with MPSK_ERR_INVALID.  The limit reaches
+ * mpsk_qrpos2, mpsk_qrlq_pair and mpsk_lqpos (there: n <= 19712 columns) through the same route. */
 int mpsk_qrpos(mpsk_ctx* ctx, int m, int n, const void* A, int lda, void* Q, int ldq, void* R, int ldr);
 /* two independent QRpos of equal shape issued together (two streams inside the ctx): the sweep needs
  * leftorth of the old AC (toolbox.jl:17-22) and of the new AC (orthoview.jl:56) at the same moment */
@@ -402,7 +406,10 @@ int mpsk_lqpos(mpsk_ctx* ctx, int m, int n, const void* A, int lda, void* L, int
  * the fallbacks where it asks for them).  *redone: bit 0 / bit 1 = the first / second factorization of the pair was
  * corrected after its enqueue -- whatever was computed from the speculative factor has to be recomputed.  Between the
  * two calls only entry points that do not use the ctx workspace are accepted (mpsk_gemm, mpsk_v*): the DMRG sweep
- * enqueues the galerkin evaluation of the site there (toolbox.jl:17-22), so the stream has work while the host waits. */
+ * enqueues the galerkin evaluation of the site there (toolbox.jl:17-22), so the stream has work while the host waits.
+ * A deferral armed before a call that does NOT take the CholeskyQR3 path -- the sequential branch of mpsk_qrpos2 (qr mode 1
+ * or n <= 64), mpsk_lqpos with qr mode 1 or m <= 64, mpsk_qrpos, mpsk_qrlq_pair -- is consumed by that call, which
+ * completes at once: its outputs are final when it returns, nothing is pending, and mpsk_qr_commit returns *redone = 0. */
 int mpsk_ctx_qr_defer(mpsk_ctx* ctx);
 /* Side stream: mpsk_ctx_side_mark records "now" on the ctx stream; after mpsk_ctx_side_begin every mpsk_* call of the ctx
  * runs on its second stream, ordered after the mark only; mpsk_ctx_side_end switches back and makes the main stream wait

@@ -2107,7 +2107,8 @@ __global__ __launch_bounds__(256) void cx_embed_kernel(const double* __restrict_
   }
 }
 // H = structured part of the (nearly) embedded E: re = (E00 + E11) / 2, im = (E10 - E01) / 2; D (optional) = E - embed(H);
-// upper != 0: complex entries below the diagonal are zeroed and the diagonal is made real (triangular factors)
+// upper != 0: complex entries below the diagonal are zeroed and the diagonal is made real (triangular factors); upper == 2:
+// and non-negative (R = triu(Q^H A): the diagonal entry of a dependent column is a rounding error of either sign)
 __global__ __launch_bounds__(256) void cx_half_kernel(const double* __restrict__ E, int64_t lde, int m, int n,
                                                       double* __restrict__ H, int64_t ldh, double* __restrict__ D, int64_t ldd,
                                                       int upper) {
@@ -2117,13 +2118,34 @@ __global__ __launch_bounds__(256) void cx_half_kernel(const double* __restrict__
     const double* e0 = E + 2 * a + lde * (2 * (int64_t)b);
     const double* e1 = e0 + lde;
     double re = 0.5 * (e0[0] + e1[1]), im = 0.5 * (e0[1] - e1[0]);
-    if (upper) { if (a > b) re = im = 0.0; else if (a == b) im = 0.0; }
+    if (upper) { if (a > b) re = im = 0.0; else if (a == b) { im = 0.0; if (upper == 2) re = fabs(re); } }
     H[2 * a + ldh * b] = re; H[2 * a + 1 + ldh * b] = im;
     if (D) {
       double* d0 = D + 2 * a + ldd * (2 * (int64_t)b);
       double* d1 = d0 + ldd;
       d0[0] = e0[0] - re; d0[1] = e0[1] - im; d1[0] = e1[0] + im; d1[1] = e1[1] - re;
     }
+  }
+}
+// E2 (embedded 2m x 2n) = embed(H) with the dependent complex columns replaced by fixed pseudo-random ones: column b is
+// dependent when a diagonal entry of its pair in the Householder factor RE is at most thresh
+__global__ __launch_bounds__(256) void cx_embed_independent_kernel(const double* __restrict__ H, int64_t ldh, int m, int n,
+                                                                   const double* __restrict__ RE, int64_t ldr, double thresh,
+                                                                   double amp, double* __restrict__ E, int64_t lde) {
+  const int64_t tot = (int64_t)m * n;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < tot; t += (int64_t)gridDim.x * blockDim.x) {
+    const int a = (int)(t % m), b = (int)(t / m);
+    double re = H[2 * a + ldh * b], im = H[2 * a + 1 + ldh * b];
+    const double d0 = fabs(RE[2 * b + ldr * (2 * (int64_t)b)]), d1 = fabs(RE[2 * b + 1 + ldr * (2 * (int64_t)b + 1)]);
+    if (d0 <= thresh || d1 <= thresh) {
+      uint32_t x = (uint32_t)a * 2654435761u ^ ((uint32_t)b * 40503u + 0x9e3779b9u);
+      x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+      re = amp * ((double)(x & 0xffffu) - 32767.5) / 32768.0;
+      im = amp * ((double)(x >> 16) - 32767.5) / 32768.0;
+    }
+    double* e0 = E + 2 * a + lde * (2 * (int64_t)b);
+    double* e1 = e0 + lde;
+    e0[0] = re; e0[1] = im; e1[0] = -im; e1[1] = re;
   }
 }
 // out (n x m complex) = conjugate transpose of in (m x n complex)
@@ -2169,8 +2191,37 @@ static int qrpos_c128(mpsk_ctx* c, int m, int n, const void* A, int lda, void* Q
                        (double*)nullptr, (int64_t)0, 1);
     return MPSK_OK;
   }
-  // structured part -> re-orthonormalise (well conditioned: structure preserving to rounding) -> R = triu(Q^H A)
-  hipLaunchKernelGGL(cx_embed_kernel, dim3(grid), dim3(256), 0, c->stream, (const double*)Q, (int64_t)2 * ldq, m, n, E2, (int64_t)m2);
+  // Exactly dependent columns (a zero column, a multiple of an earlier one) in front of other columns: the real kernels
+  // complete Q_E by directions whose plane is not invariant under J, every later column is orthogonalised against them and
+  // is no embedding either, and the spans of the structured part are no longer those of A: triu(Q^H A) would drop weight
+  // below the diagonal.  The Householder factor shows such columns (a diagonal entry at rounding level); they are replaced
+  // by fixed independent columns, whose QRpos is unique and so an embedding, with the same spans at every other column.
+  int ndep = 0;
+  double thresh = 0.0, amp = 1.0;
+  if (m2 <= qrpos_max_rows()) {
+    if (c->qr_mode != 1 && n2 > 64) {              // (the ladder's R does not show the rank: factor once more by Householder)
+      const int keep = c->qr_mode;
+      c->qr_mode = 1;
+      const int rc = qrpos_f64(c, m2, n2, E, m2, QE, m2, RE, n2);
+      c->qr_mode = keep;
+      if (rc) return rc;
+    }
+    std::vector<double> dg((size_t)n2);
+    HIPCHK(hipMemcpy2DAsync(dg.data(), sizeof(double), RE, sizeof(double) * (n2 + 1), sizeof(double), n2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    double dmax = 0.0;
+    for (double v : dg) dmax = std::fabs(v) > dmax ? std::fabs(v) : dmax;
+    thresh = 1.0e-13 * dmax;
+    amp = dmax > 0.0 ? dmax : 1.0;
+    for (int j = 0; j < n; ++j) ndep += (std::fabs(dg[2 * j]) <= thresh || std::fabs(dg[2 * j + 1]) <= thresh) ? 1 : 0;
+  }
+  if (ndep > 0) {
+    hipLaunchKernelGGL(cx_embed_independent_kernel, dim3(grid), dim3(256), 0, c->stream, (const double*)A, (int64_t)2 * lda, m, n,
+                       RE, (int64_t)n2, thresh, amp, E2, (int64_t)m2);
+  } else {
+    // structured part -> re-orthonormalise (well conditioned: structure preserving to rounding) -> R = triu(Q^H A)
+    hipLaunchKernelGGL(cx_embed_kernel, dim3(grid), dim3(256), 0, c->stream, (const double*)Q, (int64_t)2 * ldq, m, n, E2, (int64_t)m2);
+  }
   if (int rc = qrpos_f64(c, m2, n2, E2, m2, QE, m2, RE, n2)) return rc;
   hipLaunchKernelGGL(cx_half_kernel, dim3(grid), dim3(256), 0, c->stream, QE, (int64_t)m2, m, n, (double*)Q, (int64_t)2 * ldq,
                      (double*)nullptr, (int64_t)0, 0);
@@ -2178,7 +2229,7 @@ static int qrpos_c128(mpsk_ctx* c, int m, int n, const void* A, int lda, void* Q
   GemmArgs g = mk(QE, E, RE, n2, n2, m2, m2, m2, n2, 1, 0);
   HIPCHK(gemm_f64(g, c->stream));
   hipLaunchKernelGGL(cx_half_kernel, dim3(grid), dim3(256), 0, c->stream, RE, (int64_t)n2, n, n, (double*)R, (int64_t)2 * ldr,
-                     (double*)nullptr, (int64_t)0, 1);
+                     (double*)nullptr, (int64_t)0, ndep > 0 ? 2 : 1);
   return MPSK_OK;
 }
 // A (m x n complex, m <= n) = L Q: the QRpos of A^H, conjugate-transposed back

@@ -345,13 +345,20 @@ hipError_t transpose(const double* in, int ldi, int rows, int cols, double* out,
   return hipGetLastError();
 }
 
+int qrpos_max_rows() { return QR_LDS_DOUBLES - QR_SCRATCH; }
+
 size_t qrpos_workspace_doubles(int m, int n) { return (size_t)2 * m * n + (size_t)QR_NB * n * 2 + n + 64; }
 
 // A (m x n, m >= n) -> Q (m x n), R (n x n).  ws: qrpos_workspace_doubles(m, n) doubles.
 hipError_t qrpos(int m, int n, const double* A, int lda, double* Q, int ldq, double* R, int ldr, double* ws,
                  hipStream_t s, std::string* err) {
   if (m < n) { *err = "qrpos needs m >= n"; return hipErrorInvalidValue; }
-  if (m - 0 > QR_LDS_DOUBLES - QR_SCRATCH) { *err = "qrpos: more rows than fit one LDS-resident panel column"; return hipErrorInvalidValue; }
+  if (m > QR_LDS_DOUBLES - QR_SCRATCH) {
+    *err = "m = " + std::to_string(m) + " is above the row limit of the Householder route (m <= " +
+           std::to_string(QR_LDS_DOUBLES - QR_SCRATCH) + " real rows, complex m <= " +
+           std::to_string((QR_LDS_DOUBLES - QR_SCRATCH) / 2) + ": one panel column has to fit the LDS)";
+    return hipErrorInvalidValue;
+  }
   double* Aw = ws;                         // m x n
   double* Vall = Aw + (size_t)m * n;       // m x n
   double* Sall = Vall + (size_t)m * n;     // QR_NB x n   (block j0 at column j0)

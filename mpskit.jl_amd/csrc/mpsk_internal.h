@@ -199,6 +199,7 @@ size_t regularize_workspace_doubles(int W, int D1, int D2);
 hipError_t regularize(int W, int D1, int D2, double* v, const double* lvec, const double* rvec, double* partial, hipStream_t s);
 hipError_t transpose(const double* in, int ldi, int rows, int cols, double* out, int ldo, hipStream_t s);
 size_t qrpos_workspace_doubles(int m, int n);
+int qrpos_max_rows();   // row limit of the blocked Householder route (one panel column in the LDS)
 hipError_t qrpos(int m, int n, const double* A, int lda, double* Q, int ldq, double* R, int ldr, double* ws,
                  hipStream_t s, std::string* err);
 

@@ -33,6 +33,13 @@ them again and fails when a constant below is stale):
   QR    |R - R_exact| <= C_QR u cond max|R_exact| and |Q - Q_exact| <= C_QR u cond.
         numpy.linalg.qr (LAPACK Householder geqrf) with the QRpos sign fix over qr_cases(): worst ratio LAPACK_QR_RATIO;
         C_QR = 8 x that, rounded up.
+  Tall QR family (qr_stacked: t = m // n permuted, unit-scaled copies of the Hadamard block sum, so that every row stripe
+        of a tall input holds weight; real and complex; house_cases() of tests/test_gpu_house_exact.py).  LAPACK's error
+        against the exact factors grows like sqrt(m) there, so
+        |R - R_exact| / max|R_exact| and |Q - Q_exact| <= C_QR_TALL sqrt(m) u cond,  |Q^H Q - I| <= C_ORTH_TALL sqrt(m) u,
+        |Q R - A| <= C_RES_TALL sqrt(m) u max|R_exact|,  each constant 8 x LAPACK's worst ratio over the list, rounded up;
+        complex R: strictly lower triangle and imag(diag) exactly 0.  house_plan() mirrors the host lines of the blocked
+        Householder QRpos (mpsk_gauge.hip) that choose the outer blocks and inner panels; the case ids name them.
 u = 2^-53 throughout.
 """
 from __future__ import annotations
@@ -57,6 +64,15 @@ LAPACK_SVD_RATIO = 1.021                 # 384 x 384 "int" (1024 x 1024 "int": 1
 C_SVD = 8.2
 LAPACK_QR_RATIO = 0.186                  # 192 x 130, error of Q
 C_QR = 1.5
+# the tall family (qr_stacked) over house_cases(): worst ratios of LAPACK with the sign fix in the units of house_ratios()
+# (err / (sqrt(m) u cond), |Q^H Q - I| / (sqrt(m) u), |Q R - A| / (sqrt(m) u max|R_exact|)), and 8 x each.  The factor
+# ratio of the tall cases for comparison: 0.054 at 5000 x 13, 0.037 at 10000 x 5, 0.010 at 19712 x 3, 0.020 at complex 9856 x 3
+LAPACK_QR_TALL_RATIO = 0.231             # 33 x 1, error of Q (2 x 2: 0.227)
+C_QR_TALL = 1.9
+LAPACK_ORTH_TALL_RATIO = 3.130           # 2 x 2 (4 x 4: 2.250, complex 9 x 8: 1.829)
+C_ORTH_TALL = 25.1
+LAPACK_RES_TALL_RATIO = 1.506            # 2 x 2 (complex 9 x 8: 1.093)
+C_RES_TALL = 12.1
 
 
 def _rng(name):
@@ -171,6 +187,52 @@ def qr_matrix(m, n, log2grade):
 
 
 @functools.lru_cache(maxsize=None)
+def qr_stacked(m, n, log2grade, cplx=False):
+    """(A, Q_exact, R_exact (longdouble / clongdouble), cond) of the tall family: every row stripe of Q0 is occupied.
+    Q0 = t = m // n copies of the block sum of Hadamard matrices of pow2_blocks(n), the rows of each copy permuted and
+    multiplied by units (+-1; {1, i, -1, -i} for complex), m - t n zero rows appended, then all rows and the columns
+    permuted: orthogonal columns of norm sqrt(t k_b) exactly.  R0 as in qr_matrix (a super-diagonal that does not exist is
+    skipped, so n = 1, 2, 3 work); complex: the quarters are Gaussian integers / 4."""
+    assert m >= n >= 1
+    name = f"qrs-{m}x{n}-{log2grade}" + ("-c" if cplx else "")
+    rng = _rng(name)
+    t = m // n
+    H, kcol, o = np.zeros((n, n)), np.zeros(n), 0
+    for k in pow2_blocks(n):
+        H[o:o + k, o:o + k] = hadamard(k)
+        kcol[o:o + k] = k
+        o += k
+    units = np.array([1, 1j, -1, -1j]) if cplx else np.array([1.0, -1.0])
+    Q0 = np.zeros((m, n), dtype=np.complex128 if cplx else np.float64)
+    for i in range(t):
+        Q0[i * n:(i + 1) * n] = units[rng.integers(0, len(units), n)][:, None] * H[rng.permutation(n)]
+    perm = rng.permutation(n)
+    Q0 = Q0[rng.permutation(m)][:, perm]
+    norms = np.sqrt(LD(t) * kcol[perm].astype(LD))
+    dd = 2.0 ** -np.round(log2grade * np.arange(n) / max(n - 1, 1))
+    R0 = np.eye(n, dtype=Q0.dtype)
+    for off in (1, 2, 3):
+        if off < n:
+            q = rng.integers(-2, 3, n - off) / 4.0
+            if cplx:
+                q = q + 1j * (rng.integers(-2, 3, n - off) / 4.0)
+            R0 += np.diag(q, off)
+    R0 = dd[:, None] * R0
+    A = Q0 @ R0
+    assert np.abs(A).max() < LIMIT and log2grade + 12 < 50
+    ldt = np.clongdouble if cplx else LD
+    assert m * n * n <= LD_MAX_WORK, name               # every shape of this family is small enough for the longdouble product
+    assert np.array_equal(A.astype(ldt), Q0.astype(ldt) @ R0.astype(ldt)), f"{name}: fp64 product is not exact"
+    Qx = Q0.astype(ldt) / norms[None, :]
+    Rx = norms[:, None] * R0.astype(ldt)
+    cond = float(np.linalg.cond(A))
+    A = np.ascontiguousarray(A)
+    for a in (A, Qx, Rx):
+        a.setflags(write=False)
+    return A, Qx, Rx, cond
+
+
+@functools.lru_cache(maxsize=None)
 def gauss_small(kind):
     """48 x 40 Gaussian ("gauss") / graded Gaussian over 12 decades ("graded"): the inputs checked against mpmath"""
     rng = _rng("gauss-small-" + kind)
@@ -254,6 +316,23 @@ def qr_plan(m, n, env=None):
     chunk = (mt + 16 - 1) // 16          # row tiles per K-split of the in-step Gram (CQ_GS = 16 splits)
     return {"npad": npad, "nb": nb, "route": "solve" if trsm else "gemm", "gram": gram, "levels": levels,
             "gram_splits_used": (mt + chunk - 1) // chunk}
+
+
+QR_NB, QR_NBI, QR_PANEL_DOUBLES = 32, 8, 19712   # mpsk_gauge.hip: outer block, inner panel, LDS doubles of one panel
+HOUSE_MAX_ROWS = QR_PANEL_DOUBLES                # one panel column must fit: m <= 19712 (complex: 2 m <= 19712)
+
+
+def house_plan(m, n):
+    """((j0, nbo, nbi, ragged_last_panel), ...): the outer blocks of the blocked Householder QRpos of a real m x n matrix
+    (qrpos() in mpsk_gauge.hip): nbo columns from j0, inner panels of nbi columns that share the LDS with PS = m - j0 rows,
+    the last panel narrower than nbi when nbi does not divide nbo"""
+    assert n <= m <= HOUSE_MAX_ROWS
+    out = []
+    for j0 in range(0, n, QR_NB):
+        nbo = min(n - j0, QR_NB)
+        nbi = max(1, min(QR_PANEL_DOUBLES // (m - j0), QR_NBI))
+        out.append((j0, nbo, nbi, nbo % nbi != 0))
+    return tuple(out)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -375,6 +454,95 @@ def qr_cases():
                                                      QrCase(257, 256, 16), QrCase(257, 256, 32)]
 
 
+@dataclass(frozen=True)
+class HouseCase:
+    """One input of tests/test_gpu_house_exact.py.  family "stacked": qr_stacked (bounds C_*_TALL); "matrix": qr_matrix
+    (bound C_QR, as in qr_cases()).  mode: the qr mode of the call (0 default, 1 Householder at every n).  route: what the id
+    claims, checked on the CPU against house_route(): the outer blocks "nbo/nbi" of house_plan ("r": ragged last panel,
+    "k x" k equal blocks in a row) of the real matrix the Householder kernels see -- for complex input the 2m x 2n
+    embedding --, or "cholqr" where the dispatcher takes the CholeskyQR ladder (default mode, more than 64 real columns)."""
+    m: int
+    n: int
+    log2grade: int = 3
+    cplx: bool = False
+    mode: int = 0
+    family: str = "stacked"
+    route: str = ""
+
+    @property
+    def name(self):
+        return (f"{'c' if self.cplx else ''}house{self.mode}-{self.family}-{self.m}x{self.n}-grade2^{self.log2grade}"
+                f"-{self.route}")
+
+    @property
+    def real_shape(self):
+        return (2 * self.m, 2 * self.n) if self.cplx else (self.m, self.n)
+
+    @property
+    def householder(self):
+        return self.mode == 1 or self.real_shape[1] <= 64
+
+    def matrix(self):
+        if self.family == "matrix":
+            return qr_matrix(self.m, self.n, self.log2grade)
+        return qr_stacked(self.m, self.n, self.log2grade, self.cplx)
+
+
+def house_route(case: HouseCase):
+    if not case.householder:
+        return "cholqr"
+    tags = [f"{nbo}/{nbi}{'r' if rg else ''}" for _, nbo, nbi, rg in house_plan(*case.real_shape)]
+    out, i = [], 0
+    while i < len(tags):
+        k = 1
+        while i + k < len(tags) and tags[i + k] == tags[i]:
+            k += 1
+        out.append(tags[i] if k == 1 else f"{k}x{tags[i]}")
+        i += k
+    return "+".join(out)
+
+
+def _h(m, n, route, grade=3, **kw):
+    return HouseCase(m, n, grade, route=route, **kw)
+
+
+def house_real_cases():
+    """default qr mode, n <= 64: the Householder route; every case on the tall family"""
+    return [_h(1, 1, "1/8r"), _h(33, 1, "1/8r"), _h(2, 2, "2/8r"), _h(4, 4, "4/8r"),   # smallest n: skipped super-diagonals
+            _h(9, 8, "8/8"), _h(17, 9, "9/8r"),                         # one full panel; a full panel and a panel of one
+            _h(40, 31, "31/8r"), _h(64, 32, "32/8"), _h(65, 33, "32/8+1/8r"),   # ragged / exact block, a second block of one column
+            _h(100, 37, "32/8+5/8r"), _h(100, 37, "32/8+5/8r", 16), _h(100, 37, "32/8+5/8r", 32),
+            _h(64, 64, "2x32/8"), _h(64, 64, "2x32/8", 16), _h(64, 64, "2x32/8", 32),
+            _h(200, 63, "32/8+31/8r"), _h(200, 63, "32/8+31/8r", 16), _h(200, 63, "32/8+31/8r", 32),
+            _h(2465, 16, "16/7r"),                                      # the first row count with nbi = 7
+            _h(2465, 40, "32/7r+8/8"), _h(2465, 40, "32/7r+8/8", 32),   # nbi changes between the outer blocks
+            _h(5000, 12, "12/3"), _h(5000, 13, "13/3r"),                # nbi = 3: four full panels; a ragged fifth
+            _h(10000, 5, "5/1"),                                        # nbi = 1
+            _h(19712, 3, "3/1")]                                        # the row limit
+
+
+def house_mode1_cases():
+    """qr mode 1 at n > 64 (WY trailing updates and back-accumulation over many outer blocks): shapes of qr_cases()"""
+    kw = dict(mode=1, family="matrix")
+    return [_h(129, 65, "2x32/8+1/8r", **kw), _h(640, 193, "6x32/8+1/8r", **kw),
+            _h(257, 256, "8x32/8", **kw), _h(257, 256, "8x32/8", 32, **kw)]
+
+
+def house_complex_cases():
+    """qrpos_c / lqpos_c: the route of the 2m x 2n embedding"""
+    kw = dict(cplx=True)
+    return [_h(1, 1, "2/8r", **kw), _h(9, 8, "16/8", **kw), _h(40, 31, "32/8+30/8r", **kw),
+            _h(64, 32, "2x32/8", **kw),                                 # 2n = 64: the last Householder size
+            _h(66, 33, "cholqr", **kw), _h(130, 65, "cholqr", **kw),    # 2n = 66: the first CholeskyQR size
+            _h(100, 37, "cholqr", **kw), _h(100, 37, "cholqr", 32, **kw),
+            _h(2465, 16, "32/3r", **kw),                                # tall: 4930 embedded rows
+            _h(9856, 3, "6/1", **kw)]                                   # the complex row limit: 19712 embedded rows
+
+
+def house_cases():
+    return house_real_cases() + house_mode1_cases() + house_complex_cases()
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # checks (shared by the GPU tests, the child runner and -- with LAPACK in place of the library -- the CPU test)
 # ------------------------------------------------------------------------------------------------------------------
@@ -453,9 +621,80 @@ def run_svd_case(be, case: SvdCase, keep=None):
 
 def lapack_qrpos(A):
     Q, R = np.linalg.qr(A)
+    if np.iscomplexobj(A):               # divide by the phase of the diagonal; the diagonal itself becomes |diag| exactly
+        d = np.diag(R).copy()
+        ph = np.where(d == 0, 1.0, d / np.where(d == 0, 1.0, np.abs(d)))
+        Q, R = Q * ph, R / ph[:, None]
+        R[np.diag_indices_from(R)] = np.abs(d)
+        return Q, R
     sg = np.sign(np.diag(R))
     sg[sg == 0] = 1
     return Q * sg, sg[:, None] * R
+
+
+def house_ratios(case: HouseCase, Q, R):
+    """(factor, orthogonality, residual) errors of Q R = A of a tall-family case in the units of their bounds:
+    max(|R - Rx| / max|Rx|, |Q - Qx|) / (sqrt(m) u cond), |Q^H Q - I| / (sqrt(m) u), |Q R - A| / (sqrt(m) u max|Rx|);
+    the products are formed in longdouble, so the figures hold the factors' own error only"""
+    A, Qx, Rx, cond = case.matrix()
+    ldt = Qx.dtype
+    Ql, Rl = Q.astype(ldt), R.astype(ldt)
+    rmax, su = float(np.abs(Rx).max()), np.sqrt(case.m) * U
+    ef = max(float(np.abs(Rl - Rx).max()) / rmax, float(np.abs(Ql - Qx).max()))
+    eo = float(np.abs(Ql.conj().T @ Ql - np.eye(case.n)).max())
+    ea = float(np.abs(Ql @ Rl - A.astype(ldt)).max())
+    return ef / (su * cond), eo / su, ea / (su * rmax)
+
+
+def check_house_factors(case: HouseCase, Q, R, what="qrpos"):
+    """list of failed properties of Q R = A against the exact factors (LQpos: pass Q^H, L^H)"""
+    if case.family == "matrix":
+        return check_qr_factors(QrCase(case.m, case.n, case.log2grade), Q, R, what)
+    bad = []
+    if Q.shape != (case.m, case.n) or R.shape != (case.n, case.n) or np.iscomplexobj(Q) != case.cplx:
+        return [f"{case.name} {what}: shapes {Q.shape} {R.shape}"]
+    if not (np.all(np.isfinite(Q)) and np.all(np.isfinite(R))):
+        return [f"{case.name} {what}: not finite"]
+    if np.abs(np.tril(R, -1)).max(initial=0.0) != 0.0:
+        bad.append("tril(R, -1) != 0")
+    if np.abs(np.diag(R).imag).max() != 0.0:
+        bad.append("imag(diag(R)) != 0")
+    if not np.all(np.diag(R).real > 0):
+        bad.append("diag(R) not positive")
+    rf, ro, ra = house_ratios(case, Q, R)
+    if not rf <= C_QR_TALL:
+        bad.append(f"factor error / (sqrt(m) u cond) = {rf:.3f} > {C_QR_TALL}")
+    if not ro <= C_ORTH_TALL:
+        bad.append(f"|Q^H Q - I| / (sqrt(m) u) = {ro:.3f} > {C_ORTH_TALL}")
+    if not ra <= C_RES_TALL:
+        bad.append(f"|Q R - A| / (sqrt(m) u max|R|) = {ra:.3f} > {C_RES_TALL}")
+    return [f"{case.name} {what}: {b}" for b in bad]
+
+
+def inner_factorizations(s0, s1):
+    """real factorizations between two qr_stats() readings: every pass through the dispatcher ends in exactly one of these"""
+    return sum(s1[k] - s0[k] for k in ("cholqr3", "robust", "householder"))
+
+
+def run_house_case(be, case: HouseCase):
+    """QRpos of the case and LQpos of its (conjugate) transpose under the case's qr mode: (failures, stats before, between,
+    after).  The caller restores the qr mode."""
+    A = case.matrix()[0]
+    At = np.ascontiguousarray(A.conj().T)
+    be.set_qr_mode(case.mode)
+    s0 = be.qr_stats()
+    if case.cplx:
+        Q, R = (be.download_c(t) for t in be.qrpos_c(be.upload_c(A)))
+        s1 = be.qr_stats()
+        L, Ql = (be.download_c(t) for t in be.lqpos_c(be.upload_c(At)))
+    else:
+        Q, R = (be.download(t) for t in be.qrpos(be.upload(A)))
+        s1 = be.qr_stats()
+        L, Ql = (be.download(t) for t in be.lqpos(be.upload(At)))
+    s2 = be.qr_stats()
+    bad = check_house_factors(case, Q, R)
+    bad += check_house_factors(case, np.ascontiguousarray(Ql.conj().T), np.ascontiguousarray(L.conj().T), "lqpos")
+    return bad, s0, s1, s2
 
 
 def check_qr_factors(case: QrCase, Q, R, what="qrpos"):
