@@ -360,6 +360,22 @@ int mpsk_transfer_right(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, int
 int mpsk_site_gram(mpsk_ctx* ctx, int W, int d, int Dl, int Dr, const void* X, const void* Ab, void* dev_out);
 int mpsk_transfer_left_gram(mpsk_ctx* ctx, int W, int d, int Dl, int Dr, int Dlb, int Drb, const void* Vin, const void* A,
                             const void* Ab, void* Vout, void* dev_gram);
+/* mpsk_transfer_left_gram_env: one site of the matrix elements <bra| O_j |ket> between two DIFFERENT states that share their
+ * environments (WindowMPS, window.transition): everything to the right of the site does not close to an identity but to
+ * a matrix R[b,q] ([Dr, Drb], ket index first), carried from the right by pass-through transfers.
+ *   dev_gram[t,s] = sum conj(Ab[p,t,q]) Lin[p,a] A[a,s,b] R[b,q]          <bra| O_j |ket> = sum O[t,s] dev_gram[t,s]
+ *   Lin: [Dlb, Dl]; A: [Dl,d,Dr] (the ket's tensor at j); Ab: [Dlb,d,Drb] (the bra's); dev_gram: one column-major d x d
+ *   matrix in DEVICE memory, t fastest (interleaved under MPSK_C128).
+ *   Lout: [Drb, Dr], bit for bit what mpsk_transfer_left(ctx, NULL, 1, ...) writes on (Lin, A, Ab) (the same stage calls),
+ *   or NULL on the last site: stage 2 is then skipped; dev_gram does not depend on it.
+ * The stage-1 product T1 = Lin A is computed once and shared by the transfer and the Gram.  The closing product T1 R is a
+ * GEMM over the Dr index whose MFMA accumulator tiles are contracted in the epilogue with the matching tiles of conj(Ab)
+ * over (p, q): wavefront reduction, per-workgroup partials, one fixed-order final reduction, no atomics -- the product
+ * itself is never written to memory, and results are bit-identical from run to run.  Asynchronous; follows the ctx dtype
+ * (MPSK_F64, MPSK_C128).  d <= 64 (MPSK_ERR_INVALID above).  Workspace: that of mpsk_transfer_left plus d^2 1024 doubles
+ * (MPSK_C128: twice that, and 2 Dr Drb for the planes of R). */
+int mpsk_transfer_left_gram_env(mpsk_ctx* ctx, int d, int Dl, int Dr, int Dlb, int Drb, const void* Lin, const void* A,
+                                const void* Ab, const void* R, void* Lout, void* dev_gram);
 /* The transfers with flags.  MPSK_TRANSFER_CANONICAL: the caller guarantees that level 0 of GLin (mpsk_transfer_left_ex) /
  * level W-1 of GRin (mpsk_transfer_right_ex) is the identity and that A == Ab is an isometry on the contracted side
  * (sum_{p,t} A[p,t,q] A[p,t,b] = delta_qb, resp. sum_{t,b} A[a,t,b] A[p,t,b] = delta_ap) -- the environment update of a finite

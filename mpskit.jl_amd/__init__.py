@@ -24,4 +24,6 @@ from .statmech import DenseMPO, PerMPOInfEnv, leading_boundary, classical_ising,
 from .multiline import MPSMultiline, MPOMultiline, MultilineEnv  # noqa: F401,E402
 from . import native_cplx  # noqa: F401,E402   (complex128 states on interleaved storage: NativeFiniteMPS, dmrg, tdvp_step)
 from .measure import correlator, decompose_localmpo  # noqa: F401,E402   (local expectation values: expectation_value above)
+from . import window  # noqa: F401,E402
+from .window import WindowMPS, WindowEnv, transition  # noqa: F401,E402   (window.dot: overlaps of two windows)
 from .propagator import propagator, DynamicalDMRG, NaiveInvert, Jeckelmann, GMRES, LinearCombination  # noqa: F401,E402

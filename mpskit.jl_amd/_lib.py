@@ -145,6 +145,8 @@ SIGNATURES = {
     "mpsk_site_gram": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mpsk_transfer_left_gram": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p],
+    "mpsk_transfer_left_gram_env": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 # symbols without the (ctx, ...) -> int shape
 EXTRA_SYMBOLS = ["mpsk_version", "mpsk_last_error"]

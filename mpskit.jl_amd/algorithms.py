@@ -157,6 +157,9 @@ def calc_galerkin(psi, pos, envs=None, h=None, g=None):
     g: H_AC AC (any positive multiple) if the caller already has it.
     DenseMPO environments (statmech.PerMPOInfEnv): calc_galerkin(psi, envs) is the maximum over the unit cell."""
     from .statmech import PerMPOInfEnv, calc_galerkin as _galerkin_dense
+    from . import window
+    if isinstance(psi, window.WindowMPS):
+        return window.calc_galerkin(psi, pos, envs)
     if isinstance(pos, PerMPOInfEnv):
         return _galerkin_dense(psi, pos)
     if isinstance(envs, PerMPOInfEnv):
@@ -177,7 +180,9 @@ def expectation_value(psi, H, envs=None, *, device=None):
     Local operators (expval.jl:23-61, measure.py): expectation_value(psi, O) with O a [d,d] ndarray or a list of one per
     site, and expectation_value(psi, O, at) with an N-site ndarray or a list of MPO tensors and an int position; `device`
     selects their route (measure.expectation_value)."""
-    from . import measure
+    from . import measure, window
+    if isinstance(psi, window.WindowMPS):               # (vals, tot) for a Hamiltonian (expval.jl:76-87)
+        return window.expectation_value(psi, H, envs, device=device)
     if measure.is_local_operator(H, envs):
         return measure.expectation_value(psi, H, envs, device=device)
     from .statmech import DenseMPO, expectation_value as _expval_dense
@@ -265,8 +270,11 @@ def find_groundstate(psi, H, alg=None, envs=None, *, tol=None, maxiter=None, ver
     keywords: DMRG() / VUMPS().  Without alg and with any keyword: the reference's composite (_default_algorithm).
     A UnionAlg leaves the stages it ran in envs.stages = [(name, history), ...]."""
     from .operators import istimed
+    from . import window
     if istimed(H):
         raise ValueError("find_groundstate needs a time-independent operator: evaluate the time-dependent one first, H(t)")
+    if isinstance(psi, window.WindowMPS):
+        return window.find_groundstate(psi, H, alg, envs, tol=tol, maxiter=maxiter, verbosity=verbosity, trscheme=trscheme)
     if alg is None:
         if tol is None and maxiter is None and verbosity is None and trscheme is None:
             alg = DMRG() if isinstance(psi, FiniteMPS) else VUMPS()
@@ -656,6 +664,9 @@ def _timestep_inf(psi, H, t, dt, alg: TDVP, envs):  # tdvp.jl:21-59 (leftorthfla
 def timestep(psi, H, t, dt, alg=None, envs=None):
     """timestep(psi, H, t, dt, alg[, envs]) -> (psi', envs): the copying version (tdvp.jl:148-151)."""
     alg = TDVP() if alg is None else alg
+    from . import window
+    if isinstance(psi, window.WindowMPS):
+        return window.timestep(psi, H, t, dt, alg, envs)
     if isinstance(psi, InfiniteMPS):
         envs = environments(psi, H) if envs is None else envs
         return _timestep_inf(psi, H, t, dt, alg, envs)

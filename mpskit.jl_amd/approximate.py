@@ -117,7 +117,9 @@ def approximate(psi0, toapprox, alg, envs=None):
     Hamiltonian), alg = VOMPS() (approximate/vomps.jl; a VUMPS is converted, as the reference's deprecation does); eps is the
     Galerkin error.  psi0 an MPSMultiline: toapprox = (MPOMultiline, MPSMultiline), alg = VOMPS() (multiline.approximate).
     Not implemented for uniform states: IDMRG1 / IDMRG2 (approximate/idmrg.jl), complex tensors."""
-    from . import multiline
+    from . import multiline, window
+    if isinstance(psi0, window.WindowMPS):
+        return window.approximate(psi0, toapprox, alg, envs)
     if isinstance(psi0, multiline.MPSMultiline):
         return multiline.approximate(psi0, toapprox, alg, envs)
     if isinstance(psi0, InfiniteMPS):

@@ -452,6 +452,27 @@ class Backend:
             self._set_dtype(False)
         return y
 
+    def transfer_left_gram_env(self, Lin: DTensor, A: DTensor, Ab: DTensor, R: DTensor, gram_out: DTensor,
+                               out: DTensor = None, last=False, cplx=False):
+        """mpsk_transfer_left_gram_env: the pass-through transfer_left(None, Lin, A, Ab) of one slab plus gram_out[t,s] =
+        sum conj(Ab[p,t,q]) Lin[p,a] A[a,s,b] R[b,q], closed on the right with R [Dr, Drb].  gram_out: a view into a
+        caller-owned buffer.  last=True: nothing is transferred and None is returned."""
+        c = 2 if cplx else 1
+        Dl, d, Dr = A.shape[0] // c, A.shape[1], A.shape[2]
+        Dlb, Drb = Ab.shape[0] // c, Ab.shape[2]
+        if Lin.size != c * Dlb * Dl or R.size != c * Dr * Drb or Ab.shape[1] != d:
+            raise MpskError(f"transfer_left_gram_env: Lin {Lin.shape} / R {R.shape} do not fit A {A.shape}, Ab {Ab.shape}")
+        if gram_out.size != c * d * d:
+            raise MpskError(f"transfer_left_gram_env: gram_out {gram_out.shape} does not hold a matrix {c * d} x {d}")
+        y = None if last else (self.empty(1, c * Drb, Dr) if out is None else out)
+        self._set_dtype(cplx)
+        try:
+            check(self.lib.mpsk_transfer_left_gram_env(self.ctx, d, Dl, Dr, Dlb, Drb, Lin.ptr, A.ptr, Ab.ptr, R.ptr,
+                                                       None if last else y.ptr, gram_out.ptr), "mpsk_transfer_left_gram_env")
+        finally:
+            self._set_dtype(False)
+        return y
+
     def transfer_left_ex(self, H, GLin: DTensor, A: DTensor, Ab: DTensor, canonical: bool = False, out: DTensor = None):
         """mpsk_transfer_left_ex (real tensors); its presence tells FinEnv that the backend has the canonical route."""
         return self.transfer_left(H, GLin, A, Ab, out=out, canonical=canonical)

@@ -836,22 +836,28 @@ static int dAC2_c128(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* 
 // GLout[v][q,b] = sum GLin[w][p,a] A[a,s,b] O[w,t,s,v] conj(Ab[p,t,q])
 // gram (pass-through only, Dr == Drb): gram[w][t,s] = sum conj(Ab[p,t,b]) T1[w][p,s,b] of the stage-1 product, partials
 // after T1 in the workspace; GLout == nullptr then skips stage 2 (mpsk_transfer_left_gram)
+// envR (with gram, Wl == 1): the [Dr, Drb] matrix that closes the site on the right; gram[t,s] = sum conj(Ab[p,t,q])
+// T1[p,s,b] envR[b,q] then comes out of the fused closing product (gram_env), its planar copy of envR behind the partials
 static int transfer_left_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr, int d, int Dl, int Dr, int Dlb, int Drb,
                               const double* GLin, const double* A, const double* Ab, double* GLout,
-                              double* gram = nullptr) {
+                              double* gram = nullptr, const double* envR = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   const size_t nA = (size_t)Dl * d * Dr, slab = (size_t)2 * Dlb * d * Dr;
   Ws ws;
   const CxPlanes apl(ws, nA);
   const size_t o_t1 = ws.take(slab * Wl), o_t2 = ws.take(H ? slab * Wr : 0);
-  const size_t o_part = ws.take(gram ? site_gram_partial_doubles(Wl, d, true) : 0);     // H == NULL: straight after T1
+  const size_t o_part = ws.take(gram ? site_gram_partial_doubles(Wl, d, true) : 0, 2);  // H == NULL: straight after T1
+  const CxPlanes rpl(ws, envR ? (size_t)Dr * Drb : 0);
   if (int rc = ws.ensure(c)) return rc;
   double* T1 = Ws::at(c, o_t1);
   double* T2 = H ? Ws::at(c, o_t2) : T1;
   HIPCHK(apl.split(c, A));
   HIPCHK(stage1(c, Wl, 2 * Dlb, Dl, d * Dr, GLin, apl.at(c), T1, 0, 1, apl.stride()));      // T1[w] = GLin[w] A, rows interleaved
   if (H) HIPCHK(mix_levels(c, H->fwd, d, 2 * Dlb, Dr, T1, T2));
-  if (gram) HIPCHK(site_gram(Wl, d, Dlb, Dr, T1, Ab, true, gram, Ws::at(c, o_part), c->stream));
+  if (gram && envR) {
+    HIPCHK(rpl.split(c, envR));
+    HIPCHK(gram_env(d, Dlb, Dr, Drb, T1, rpl.at(c), rpl.stride(), Ab, true, gram, Ws::at(c, o_part), c->stream));
+  } else if (gram) HIPCHK(site_gram(Wl, d, Dlb, Dr, T1, Ab, true, gram, Ws::at(c, o_part), c->stream));
   if (!GLout) return MPSK_OK;
   // GLout[v] = Ab^H T2[v]:  K = (re / im, p, t) interleaved on both operands ->  real part = Ab_half^T T2_half,
   // imaginary part = (J Ab_half)^T T2_half ; plane alpha goes to the rows 2 q + alpha of the interleaved result
@@ -1876,8 +1882,10 @@ static int transfer_right_canonical(mpsk_ctx* c, const mpsk_mposlice* H, int Dl,
 
 // gram (pass-through only, Dr == Drb): gram[w][t,s] = sum Ab[p,t,b] T1[w][p,s,b] of the stage-1 product, partials after
 // T1 in the workspace; GLout == nullptr then skips stage 2 (mpsk_transfer_left_gram)
+// envR (with gram, Wl == 1): as in transfer_left_c128
 static int transfer_left_f64(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr, int d, int Dl, int Dr, int Dlb, int Drb,
-                             const void* GLin, const void* A, const void* Ab, void* GLout, double* gram) {
+                             const void* GLin, const void* A, const void* Ab, void* GLout, double* gram,
+                             const double* envR = nullptr) {
   const size_t slab = (size_t)Dlb * d * Dr;
   Ws ws;
   const size_t o_t = ws.take(slab * (Wl + (H ? Wr : 0)), gram ? 32 : 1);      // T1, then T2 when there is a mix
@@ -1887,7 +1895,9 @@ static int transfer_left_f64(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr
   double* T2 = H ? T1 + slab * Wl : T1;
   HIPCHK(stage1(c, Wl, Dlb, Dl, d * Dr, (const double*)GLin, (const double*)A, T1, 0));      // T1[w][p,s,b] = sum_a GLin[w][p,a] A[a,s,b]
   if (H) HIPCHK(mix_levels(c, H->fwd, d, Dlb, Dr, T1, T2));
-  if (gram) HIPCHK(site_gram(Wl, d, Dlb, Dr, T1, (const double*)Ab, false, gram, Ws::at(c, o_part), c->stream));
+  if (gram && envR)
+    HIPCHK(gram_env(d, Dlb, Dr, Drb, T1, envR, 0, (const double*)Ab, false, gram, Ws::at(c, o_part), c->stream));
+  else if (gram) HIPCHK(site_gram(Wl, d, Dlb, Dr, T1, (const double*)Ab, false, gram, Ws::at(c, o_part), c->stream));
   if (!GLout) return MPSK_OK;
   // GLout[v][q,b] = sum_{(p,t)} Ab[(p,t),q] T2[v][(p,t),b]
   GemmArgs g3 = mk((const double*)Ab, T2, (double*)GLout, Drb, Dr, Dlb * d, (int64_t)Dlb * d, (int64_t)Dlb * d, Drb, 1, 0);
@@ -1948,6 +1958,21 @@ int mpsk_transfer_left_gram(mpsk_ctx* c, int W, int d, int Dl, int Dr, int Dlb, 
     return transfer_left_c128(c, nullptr, W, W, d, Dl, Dr, Dlb, Drb, (const double*)Vin, (const double*)A, (const double*)Ab,
                               (double*)Vout, (double*)dev_gram);
   return transfer_left_f64(c, nullptr, W, W, d, Dl, Dr, Dlb, Drb, Vin, A, Ab, Vout, (double*)dev_gram);
+}
+
+// One site of the matrix elements <bra| O_j |ket> of two states on the same environments (window.transition): the
+// pass-through transfer of Lin over (A, Ab) plus dev_gram[t,s] = sum conj(Ab[p,t,q]) Lin[p,a] A[a,s,b] R[b,q], closed on
+// the right with R [Dr, Drb].  The stages of Lout are those of mpsk_transfer_left(NULL, W = 1).
+int mpsk_transfer_left_gram_env(mpsk_ctx* c, int d, int Dl, int Dr, int Dlb, int Drb, const void* Lin, const void* A,
+                                const void* Ab, const void* R, void* Lout, void* dev_gram) {
+  REQUIRE(c && Lin && A && Ab && R && dev_gram, "NULL argument");
+  REQUIRE(d > 0 && Dl > 0 && Dr > 0 && Dlb > 0 && Drb > 0, "dimensions must be positive");
+  REQUIRE(d <= gram_env_max_d(), "physical dimension above the limit of the fused closing product");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->dtype == MPSK_C128)
+    return transfer_left_c128(c, nullptr, 1, 1, d, Dl, Dr, Dlb, Drb, (const double*)Lin, (const double*)A, (const double*)Ab,
+                              (double*)Lout, (double*)dev_gram, (const double*)R);
+  return transfer_left_f64(c, nullptr, 1, 1, d, Dl, Dr, Dlb, Drb, Lin, A, Ab, Lout, (double*)dev_gram, (const double*)R);
 }
 
 // dev_out[w][t,s] = sum_{p,b} conj(Ab[p,t,b]) X[w][p,s,b]: the one-site reduced density matrix for X = Ab = AC

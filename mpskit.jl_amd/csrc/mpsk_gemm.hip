@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
@@ -1220,6 +1221,140 @@ hipError_t grassmann_coef(int K, const double* S, double scalar, int mode, doubl
   if (K <= 0 || !S || !coef || mode < 0 || mode > 2) return hipErrorInvalidValue;
   hipLaunchKernelGGL(grassmann_coef_kernel, dim3(1), dim3(256), 0, s, K, S, scalar, mode, coef);
   return hipGetLastError();
+}
+
+// ---- closing product of a bra-ket matrix element (mpsk_transfer_left_gram_env) -------------------
+//   gram[t,s] = sum_{p,q} conj(Ab[p,t,q]) X[p,s,q],   X[p,s,q] = sum_b T1[p,s,b] R[b,q]
+// X is one GEMM over the Dr index per physical index s (blockIdx.y): A operand T1[:,s,:] ([C Dlb] x Dr, lda = C Dlb d),
+// B operand R (complex: the plane pair through the J loader, as in stage 1).  The tile of X stays in the MFMA accumulators:
+// the epilogue multiplies it with the matching tile of conj(Ab[:,t,:]) for every t, reduces over the wavefront and then
+// over the four waves in a fixed order, and adds the d (complex: 2 d) sums to the workgroup's own partials -- X is never
+// written.  A lane holds X rows m = .. + fr (memory-contiguous in Ab) and columns n = .. + fq + 4 reg; for complex
+// operands row m = 2 p + alpha is the real (alpha = 0) or imaginary (alpha = 1) part, and conj(a) x splits into
+// Re += x[m] a[m], Im += (alpha ? + : -) x[m] a[m ^ 1], so no lane needs another lane's accumulator.
+// A workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... in ascending order (gridDim.x <= DOT_BLOCKS), so
+// every sum has a fixed order: partial[((t + d s) C + c) * DOT_BLOCKS + blockIdx.x], closed by dot_final.
+struct GramEnvArgs {
+  GemmArgs g;
+  const double* Ab;          // bra tensor [C Dlb, d, Drb]
+  int d;
+  int64_t ab_ldp, ab_ldq;    // doubles between two physical indices / two q of Ab
+  double* partial;
+};
+
+__device__ __forceinline__ double gram_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+template <bool ALIGNED, bool CJ>
+__global__ __launch_bounds__(NTHREADS, min_waves(64, 64)) void gram_env_kernel(GramEnvArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  constexpr int BM = 64, BN = 64, WTM = BM / 2, WTN = BN / 2, TM = WTM / 16, TN = WTN / 16;
+  constexpr int C = CJ ? 2 : 1;
+  const GemmArgs& g = a.g;
+  const int tilesM = (g.M + BM - 1) / BM, tilesN = (g.N + BN - 1) / BN;
+  const int ntiles = tilesM * tilesN;
+  const int z = blockIdx.y;
+  const double* Ab_ = g.A + (int64_t)z * g.bsA;
+  const int nt = ((g.K + BK - 1) / BK) * g.nseg;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wn = wave >> 1, fr = lane & 15, fq = lane >> 4;
+  const int d = a.d, nv = d * C;
+  bool first = true;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int bn = tile / tilesM, bm = tile - bn * tilesM;
+    const int m0 = bm * BM, n0 = bn * BN;
+    d4 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+    gemm_acc_dispatch<BM, BN, false, false, ALIGNED, false, CJ>(g, Ab_, g.B, z, m0, n0, 0, nt, acc, smem);
+    // (the accumulate ends with a barrier: the LDS images are free and serve as the reduction scratch)
+    for (int t = 0; t < d; ++t) {
+      const double* __restrict__ at = a.Ab + (int64_t)t * a.ab_ldp;
+      double vr = 0.0, vi = 0.0;
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int m = m0 + wm * WTM + i * 16 + fr;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) {
+            const int n = n0 + wn * WTN + j * 16 + fq + 4 * rg;
+            if (ALIGNED || (m < g.M && n < g.N)) {
+              const double* __restrict__ col = at + (int64_t)n * a.ab_ldq;
+              const double x = acc[i][j][rg];
+              vr += x * col[m];
+              if constexpr (CJ) {
+                const double o = x * col[m ^ 1];
+                vi += (m & 1) ? o : -o;
+              }
+            }
+          }
+        }
+      }
+      vr = gram_wave_sum(vr);
+      if constexpr (CJ) vi = gram_wave_sum(vi);
+      if (lane == 0) {
+        smem[wave * nv + t * C] = vr;
+        if constexpr (CJ) smem[wave * nv + t * C + 1] = vi;
+      }
+    }
+    __syncthreads();
+    if (tid < nv) {
+      const double v = ((smem[tid] + smem[nv + tid]) + smem[2 * nv + tid]) + smem[3 * nv + tid];
+      const int t = tid / C, c = tid - t * C;
+      double* q = a.partial + (((int64_t)t + (int64_t)d * z) * C + c) * DOT_BLOCKS + blockIdx.x;
+      *q = first ? v : *q + v;      // this thread is the only writer of the slot
+    }
+    __syncthreads();
+    first = false;
+  }
+}
+
+int gram_env_max_d() { return 64; }
+
+// T1: [C Dlb, d, Dr] (the stage-1 product of the transfer), R: [Dr, Drb] (complex: planar, r_plane doubles between the
+// re and im planes), Ab: [C Dlb, d, Drb]; d_out: the column-major d x d matrix (complex: interleaved), t fastest;
+// d_partial: site_gram_partial_doubles(1, d, cplx) doubles.  Asynchronous.
+hipError_t gram_env(int d, int Dlb, int Dr, int Drb, const double* T1, const double* R, int64_t r_plane, const double* Ab,
+                    bool cplx, double* d_out, double* d_partial, hipStream_t s) {
+  if (d <= 0 || d > gram_env_max_d() || Dlb <= 0 || Dr <= 0 || Drb <= 0) return hipErrorInvalidValue;
+  const int C = cplx ? 2 : 1;
+  GramEnvArgs a;
+  std::memset(&a, 0, sizeof(a));
+  GemmArgs& g = a.g;
+  g.A = T1; g.B = R; g.M = C * Dlb; g.N = Drb; g.K = Dr;
+  g.lda = (int64_t)C * Dlb * d; g.ldb = Dr;
+  g.batch = d; g.bsA = (int64_t)C * Dlb; g.nseg = 1; g.alpha = 1.0;
+  g.A2 = g.A; g.B2 = g.B; g.nseg1 = 1;
+  if (cplx) { g.nseg = 2; g.nseg1 = 2; g.segB[1] = r_plane; g.segJ[1] = 1; g.cplx = 1; }
+  a.Ab = Ab; a.d = d; a.ab_ldp = (int64_t)C * Dlb; a.ab_ldq = (int64_t)C * Dlb * d; a.partial = d_partial;
+  const bool aligned = (g.M % 64 == 0) && (g.N % 64 == 0) && (g.K % BK == 0) && (g.lda % 2 == 0) && (g.ldb % 2 == 0) &&
+                       (g.bsA % 2 == 0) && (r_plane % 2 == 0) && ((uintptr_t)T1 % 16 == 0) && ((uintptr_t)R % 16 == 0) &&
+                       g.lda < ((int64_t)1 << 21) && g.ldb < ((int64_t)1 << 21);
+  const int64_t ntiles = (int64_t)((g.M + 63) / 64) * ((g.N + 63) / 64);
+  const int nb = (int)(ntiles < DOT_BLOCKS ? ntiles : DOT_BLOCKS);
+  using IA = LdsImg<64, false>;
+  using IB = LdsImg<64, true>;
+  constexpr size_t smem = (2 * IA::SIZE + 2 * IB::SIZE) * sizeof(double);
+  static_assert(4 * 2 * 64 <= 2 * IA::SIZE + 2 * IB::SIZE, "reduction scratch of gram_env_kernel");
+  const dim3 grid((unsigned)nb, (unsigned)d);
+#define MPSK_GRAM_ENV(AL_, CJ_)                                                                                  \
+  do {                                                                                                           \
+    static std::atomic<uint64_t> done{0};                                                                        \
+    const auto kern = gram_env_kernel<AL_, CJ_>;                                                                 \
+    if (hipError_t e = ensure_dyn_smem(done, reinterpret_cast<const void*>(kern), smem); e != hipSuccess) return e; \
+    hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), smem, s, a);                                                  \
+  } while (0)
+  if (cplx) { if (aligned) MPSK_GRAM_ENV(true, true); else MPSK_GRAM_ENV(false, true); }
+  else { if (aligned) MPSK_GRAM_ENV(true, false); else MPSK_GRAM_ENV(false, false); }
+#undef MPSK_GRAM_ENV
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  return dot_final(d_partial, nb, d * d * C, d_out, s);
 }
 
 }  // namespace mpsk

@@ -193,6 +193,19 @@ hipError_t fold_lincomb(const FoldLincombArgs& a, hipStream_t s);
 size_t site_gram_partial_doubles(int W, int d, bool cplx);
 hipError_t site_gram(int W, int d, int Dl, int Dr, const double* X, const double* Ab, bool cplx, double* d_out,
                      double* d_partial, hipStream_t s);
+// per-block partial sums of the dot / Gram kernels: row j of a partial buffer is DOT_BLOCKS doubles, one per workgroup
+constexpr int DOT_BLOCKS = 1024;
+// d_out[j] = sum_{b < nblocks} d_partial[j * DOT_BLOCKS + b], j < nrows, in a fixed order (the closing launch of every dot
+// and Gram reduction)
+hipError_t dot_final(const double* d_partial, int nblocks, int nrows, double* d_out, hipStream_t s);
+// d_out[t,s] = sum_{p,q} conj(Ab[p,t,q]) sum_b T1[p,s,b] R[b,q]: the closing product of mpsk_transfer_left_gram_env on
+// the stage-1 product T1 [Dlb, d, Dr], fused with the Gram reduction (mpsk_gemm.hip: the product T1 R only exists as MFMA
+// accumulator tiles).  R: [Dr, Drb], for complex operands planar with r_plane doubles between the planes; T1 / Ab
+// interleaved.  d <= gram_env_max_d(); d_partial: site_gram_partial_doubles(1, d, cplx) doubles.  Asynchronous,
+// deterministic.
+int gram_env_max_d();
+hipError_t gram_env(int d, int Dlb, int Dr, int Drb, const double* T1, const double* R, int64_t r_plane, const double* Ab,
+                    bool cplx, double* d_out, double* d_partial, hipStream_t s);
 
 // ---- gauge kernels ----------------------------------------------------------------------------
 size_t regularize_workspace_doubles(int W, int D1, int D2);

@@ -199,7 +199,6 @@ template <int NV> __device__ inline void block_sum(double (&v)[NV], double* sh /
   __syncthreads();
 }
 
-constexpr int DOT_BLOCKS = 1024;
 constexpr int MD = 8;  // vectors per multidot pass
 
 struct PtrPack { const double* p[MD]; };
@@ -241,6 +240,12 @@ __global__ __launch_bounds__(256) void dot_final_kernel(const double* __restrict
   for (int i = threadIdx.x; i < nblocks; i += blockDim.x) acc[0] += p[i];
   block_sum<1>(acc, sh);
   if (threadIdx.x == 0) out[blockIdx.x] = acc[0];
+}
+
+hipError_t dot_final(const double* d_partial, int nblocks, int nrows, double* d_out, hipStream_t s) {
+  if (nblocks <= 0 || nblocks > DOT_BLOCKS || nrows <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dot_final_kernel, dim3((unsigned)nrows), dim3(256), 0, s, d_partial, nblocks, d_out);
+  return hipGetLastError();
 }
 
 static int dot_grid(int64_t n) {

@@ -288,7 +288,9 @@ def ddAC(pos, psi, H, envs, canonical=None):  # ∂∂AC  derivatives.jl:44-46
     GR = envs.rightenv(pos, psi)
     if canonical is None:
         from .environments import FinEnv
-        canonical = type(envs) is FinEnv and not getattr(psi, "cplx", False)
+        # (a window's environments, window.WindowEnv, keep the promise when their two start identities were verified)
+        canonical = ((type(envs) is FinEnv or (getattr(envs, "window_canonical", False) and getattr(envs, "canonical", False)))
+                     and not getattr(psi, "cplx", False))
     return _half_space(psi, MPO_ddAC(psi.be, opp, envs.leftenv(pos, psi), GR, canonical=canonical), "AC", GR)
 
 

@@ -28,17 +28,21 @@ class FinEnv:
     (FinEnv.jl:114-145): an AL/AR that was invalidated and recomputed is a new object, so the
     environments that depend on it are rebuilt exactly when the reference rebuilds them."""
 
-    def __init__(self, psi, H):
+    def __init__(self, psi, H, leftstart=None, rightstart=None):
+        """leftstart / rightstart: the environments left of site 0 / right of site L-1 when they are not the trivial ones
+        of a finite chain (window.WindowEnv, FinEnv.jl:84-89)"""
         be = self.be = psi.be
         L = len(psi)
         self.H = H
         self.opp = [H[i] for i in range(L)]
         odim = H.odim
-        D0 = psi.AL(0).shape[0]
-        t = psi.ARs[L - 1] if psi.ARs[L - 1] is not None else psi.AL(L - 1)
-        DL = t.shape[2]
-        self.leftenvs = [_start_env(be, self.opp[0].chil, D0, 0)] + [None] * L
-        self.rightenvs = [None] * L + [_start_env(be, self.opp[L - 1].chir, DL, odim - 1)]
+        if leftstart is None:
+            leftstart = _start_env(be, self.opp[0].chil, psi.AL(0).shape[0], 0)
+        if rightstart is None:
+            t = psi.ARs[L - 1] if psi.ARs[L - 1] is not None else psi.AL(L - 1)
+            rightstart = _start_env(be, self.opp[L - 1].chir, t.shape[2], odim - 1)
+        self.leftenvs = [leftstart] + [None] * L
+        self.rightenvs = [None] * L + [rightstart]
         self.ldeps = [None] * L
         self.rdeps = [None] * L
         self.n_transfers = 0
@@ -185,12 +189,17 @@ class MultipleEnvironments:
         return self
 
 
-def environments(psi, H, **kw):
-    """environments(psi, H)  (FinEnv.jl:41-70 / mpohaminfenv.jl:40-44 / multipleenv.jl:30-34; a DenseMPO:
+def environments(psi, H, *args, **kw):
+    """environments(window, H[, lenvs, renvs]): window.environments.  environments(psi, H)  (FinEnv.jl:41-70 / mpohaminfenv.jl:40-44 / multipleenv.jl:30-34; a DenseMPO:
     permpoinfenv.jl:20-29, an InfiniteMPS with H = (O, above): permpoinfenv.jl:29-42, both statmech.PerMPOInfEnv)."""
     from .states import FiniteMPS
     from .operators import LazySum, MultipliedOperator
     from .statmech import DenseMPO, PerMPOInfEnv
+    from . import window
+    if isinstance(psi, window.WindowMPS):                                       # FinEnv.jl:84-99
+        return window.environments(psi, H, *args, **kw)
+    if args:
+        raise TypeError("environments(psi, H): start environments are taken for a WindowMPS only")
     if isinstance(H, MultipliedOperator):                                       # multipliedoperator.jl:50-52
         return environments(psi, H.op, **kw)
     if isinstance(psi, FiniteMPS) and isinstance(H, (tuple, FiniteMPS)):       # FinEnv.jl:21-23, :91-99

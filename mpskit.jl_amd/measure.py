@@ -336,6 +336,9 @@ def correlator(psi, O1, O2, i=None, js=None, device=None):
     """correlator(psi, O1, O2, i, js) = [<O1_i O2_j> for j in js]  (correlators.jl:14-38); correlator(psi, O12, i, js) with a
     two-site operator O12[t1,t2,s1,s2] splits it first (:40-43).  O1 / O2 are [d,d] arrays or MPO tensors [1,d,d,W] /
     [W,d,d,1].  js: an int (a scalar comes back) or an increasing iterable with js[0] > i; an InfiniteMPS takes any j."""
+    from . import window
+    if isinstance(psi, window.WindowMPS):
+        return window.correlator(psi, O1, O2, i, js, device=device)
     if js is None:                                         # correlator(psi, O12, i, js)
         O12, i, js = np.asarray(O1), O2, i
         if O12.ndim != 4 or i is None or js is None:

@@ -131,6 +131,17 @@ class FiniteMPS:
                         for i in range(L)], normalize=normalize, be=be)
         return cls([rng.random((dims[i], d, dims[i + 1])) for i in range(L)], normalize=normalize, be=be)
 
+    @classmethod
+    def from_canonical(cls, ALs, ARs, ACs, CLs, be, cplx=False):
+        """a state from tensors that already are in canonical form: N entries of AL / AR / AC (device tensors or None) and
+        the N + 1 bond matrices CLs[i] = CR(i - 1).  No gauge step is run (window.WindowMPS(psi, L))."""
+        o = object.__new__(cls)
+        o.be, o.N, o.cplx = be, len(ALs), bool(cplx)
+        o.ALs, o.ARs, o.ACs, o.CLs = list(ALs), list(ARs), list(ACs), list(CLs)
+        if not (len(o.ARs) == len(o.ACs) == o.N and len(o.CLs) == o.N + 1):
+            raise ValueError("from_canonical: N tensors of each kind and N + 1 bond matrices")
+        return o
+
     def copy(self):
         o = object.__new__(FiniteMPS)
         o.be, o.N, o.cplx = self.be, self.N, self.cplx

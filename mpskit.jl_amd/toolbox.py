@@ -12,6 +12,9 @@ from .states import FiniteMPS
 
 def variance(state, H, envs=None):
     from .quasiparticle import LeftGaugedQP, QuasiparticleAnsatz, _QPContext
+    from . import window
+    if isinstance(state, window.WindowMPS):                                       # toolbox.jl:147-152
+        return window.variance(state, H, envs)
     if isinstance(state, LeftGaugedQP):
         if not state.finite or not state.trivial:
             raise NotImplementedError("variance of an infinite / domain-wall quasiparticle state")
@@ -49,6 +52,9 @@ def _xlogx_trace(be, c):
 
 def entanglement_spectrum(state, site=0):
     """entanglement_spectrum(psi; site)  (toolbox.jl:60-75): singular values of the bond matrix CR[site]."""
+    from . import window
+    if isinstance(state, window.WindowMPS):
+        state = state._real("entanglement_spectrum")
     c = state.CR(site) if isinstance(state, FiniteMPS) else state.CR[site % len(state)]
     _, S, _, kept, _ = state.be.tsvd(c)
     return np.asarray(state.be.download(S)).reshape(-1)[:kept]
@@ -57,6 +63,9 @@ def entanglement_spectrum(state, site=0):
 def entropy(state, loc=None):
     """entropy(state[, loc])  (toolbox.jl:1-5): -tr(rho log rho) of the bond right of site loc; all bonds of the unit cell for
     an InfiniteMPS without loc."""
+    from . import window
+    if isinstance(state, window.WindowMPS):
+        state = state._real("entropy")
     be = state.be
     if loc is None:
         if isinstance(state, FiniteMPS):
