@@ -393,6 +393,44 @@ int mpsk_transfer_left_ex(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, i
                           const void* GLin, const void* A, const void* Ab, int flags, void* GLout);
 int mpsk_transfer_right_ex(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
                            const void* A, const void* Ab, const void* GRin, int flags, void* GRout);
+/* ---- quasiparticle excitations of a transfer matrix: quasiparticleexcitation.jl:258-293 (the local term of the effective
+ * operator) and qpenv.jl:238-251 (the updates of lB / rB).  MPSK_F64 only: a MPSK_C128 slice or ctx gets
+ * MPSK_ERR_UNSUPPORTED.  Both slice kinds: sparse slices (slab mix) and dense slices on both sides of the crossover of
+ * mpsk_mposlice_create_dense (MPSK_DENSE_ROUTE honoured).  All entries are built from the stages of mpsk_dAC_proj and of
+ * the transfers; no new kernel.
+ * mpsk_qp_apply:   y[p,t,q] = sum GL[w][p,a] B[a,s,b]  O[w,t,s,v] GR[v][b,q]        B in the centre      :273-276
+ *                           + sum lB[w][p,c] AR[c,s,b] O[w,t,s,v] GR[v][b,q]        B further left       :278-281
+ *                           + sum GL[w][p,a] AL[a,s,e] O[w,t,s,v] rB[v][e,q]        B further right      :283-286
+ *   GL: Wl slabs [Dlo, Dl]; GR: Wr slabs [Dr, Dro]; B: [Dl, d, Dr]; lB: Wl slabs [Dlo, Dl2]; AR: [Dl2, d, Dr];
+ *   rB: Wr slabs [Dr2, Dro]; y: [Dlo, d, Dro].  The third term enters through `half`, stages 1 and 2 of (GL, AL [Dl, d, Dr2]):
+ *   it does not depend on B, so mpsk_qp_half computes it once per site into a caller-owned device buffer of
+ *   mpsk_qp_half_size doubles (= Wr d Dlo Dr2; its layout is that of the stage-2 result of the route the slice takes, so a
+ *   buffer is valid for the slice and the setting of MPSK_DENSE_ROUTE it was made with).  mpsk_qp_apply only reads it.
+ *   The pair (lB, AR) and the pair (half, rB) may each be NULL (both members).  With both NULL the call is mpsk_dAC_proj
+ *   bit for bit (same launches, same tiles).  Stage 1 of the second term is a GEMM that accumulates (beta = 1) into the
+ *   stage-1 buffer of the first; the third term is a second segmented-K GEMM that accumulates into y.
+ *   flops: 2 Wl d Dlo (Dl + Dl2) Dr + 2 Wr d Dlo (Dr + Dr2) Dro (+ the MPO stage, once) against three times
+ *   2 Wl d Dlo Dl Dr + 2 Wr d Dlo Dr Dro (+ three MPO stages) composed; mpsk_qp_half: 2 Wl d Dlo Dl Dr2 + the MPO stage.
+ *   Workspace: Dlo d Dr (Wl + Wr) doubles (mpsk_qp_half: Dlo d Dr2 Wl). */
+int mpsk_qp_half_size(const mpsk_mposlice* H, int Dlo, int Dr2, size_t* doubles);
+int mpsk_qp_half(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int Dr2, const void* GL, const void* A, void* half);
+int mpsk_qp_apply(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int Dl2, int Dr, int Dr2, int Dro, const void* GL,
+                  const void* GR, const void* B, const void* lB, const void* AR, const void* half, const void* rB, void* y);
+/* The pair transfers (qpenv.jl:238-251): out = T(V1; A1, O, Ab) + T(V2; A2, O, Ab), two transfers through the same O and the
+ * same bra Ab whose kets and environments differ.  Stage 1 runs twice, the second product accumulating into the first
+ * one's buffer; stages 2 and 3 run once.  Layouts as mpsk_transfer_left_ex / mpsk_transfer_right_ex without flags:
+ *   left:  V1: Wl slabs [Dlb, Dl1], A1: [Dl1, d, Dr]; V2: Wl slabs [Dlb, Dl2], A2: [Dl2, d, Dr]; Ab: [Dlb, d, Drb];
+ *          out: Wr slabs [Drb, Dr].   flops 2 Wl d Dlb (Dl1 + Dl2) Dr + 2 Wr d Dlb Dr Drb; workspace Dlb d Dr (Wl + Wr).
+ *   right: A1: [Dl, d, Dr1], V1: Wr slabs [Dr1, Drb]; A2: [Dl, d, Dr2], V2: Wr slabs [Dr2, Drb]; Ab: [Dlb, d, Drb];
+ *          out: Wl slabs [Dl, Dlb].   The ket is contracted first (the order of the right half of mpsk_dAC2_product), so
+ *          that both terms meet in one intermediate [Dl, d, Drb]: flops 2 Wr d Dl (Dr1 + Dr2) Drb + 2 Wl d Dl Drb Dlb;
+ *          workspace Dl d Drb (Wl + Wr).  (mpsk_transfer_right contracts the bra first: with V2 = 0 the results agree to
+ *          rounding, not bit for bit.)
+ * H is required. */
+int mpsk_transfer_left_pair(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dl1, int Dl2, int Dr, int Dlb, int Drb, const void* V1,
+                            const void* A1, const void* V2, const void* A2, const void* Ab, void* out);
+int mpsk_transfer_right_pair(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dl, int Dr1, int Dr2, int Dlb, int Drb, const void* A1,
+                             const void* V1, const void* A2, const void* V2, const void* Ab, void* out);
 /* regularize!(v, lvec, rvec)   src/transfermatrix/transfermatrix.jl:70-76
  *   v[w] -= <lvec^T, v[w]> * rvec  for each of the W slabs [D1, D2]; lvec: [D2, D1]; rvec: [D1, D2] */
 int mpsk_regularize(mpsk_ctx* ctx, int W, int D1, int D2, void* v, const void* lvec, const void* rvec);

@@ -195,6 +195,15 @@ function transfer_right(v::ROCTensor{3}, H::ROCSlice, A::ROCTensor{3}, Ab::ROCTe
         CTX[], H.handle, H.Wr, H.d, A.dims[1], A.dims[3], Ab.dims[1], Ab.dims[3], A.ptr, Ab.ptr, v.ptr, out.ptr))
     return out
 end
+# statistical-mechanics quasiparticles (quasiparticleexcitation.jl:273-286, qpenv.jl:238-251): T = GL B O GR + lB AR O GR + half rB
+# with half = mpsk_qp_half(GL, AL); mpsk_transfer_left_pair / mpsk_transfer_right_pair are the two updates of lB / rB
+function qp_apply(H::ROCSlice, GL, GR, B, lB, AR, half, rB)
+    y = ROCTensor((GL.dims[2], H.d, GR.dims[3]))
+    check(ccall((:mpsk_qp_apply, libmpsk[]), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        CTX[], H.handle, GL.dims[2], GL.dims[3], lB.dims[3], B.dims[3], rB.dims[2], GR.dims[3], GL.ptr, GR.ptr, B.ptr, lB.ptr, AR.ptr, half.ptr, rB.ptr, y.ptr))
+    return y
+end
 
 # ---- gauge steps (TensorKit leftorth!/rightorth!/tsvd! on the matricised tensor) ----
 # mpsk_qrpos / mpsk_lqpos / mpsk_tsplit follow the ctx dtype (include/mpsk.h): under MPSK_C128 their operands are the

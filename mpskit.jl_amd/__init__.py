@@ -17,7 +17,7 @@ from . import grassmann  # noqa: F401,E402
 from .changebonds import changebonds, OptimalExpand, RandExpand, SvdCut  # noqa: F401,E402
 from .approximate import approximate, ac_proj, c_proj, make_time_mpo, WI, WII, TaylorCluster  # noqa: F401,E402
 from .excitations import excitations, FiniteExcited, ProjectionOperator  # noqa: F401,E402
-from .quasiparticle import QuasiparticleAnsatz, LeftGaugedQP  # noqa: F401,E402
+from .quasiparticle import QuasiparticleAnsatz, LeftGaugedQP, MultilineQP  # noqa: F401,E402
 from .toolbox import (variance, entropy, entanglement_spectrum, transfer_spectrum, marek_gap, correlation_length,  # noqa: F401,E402
                       exact_diagonalization)
 from .statmech import DenseMPO, PerMPOInfEnv, leading_boundary, classical_ising, sixvertex, dot  # noqa: F401,E402

@@ -329,6 +329,73 @@ class Backend:
         check(self.lib.mpsk_dAC_proj(self.ctx, H.handle, Dlo // m, Dl, Dr, Dro, GL.ptr, GR.ptr, x.ptr, y.ptr), "mpsk_dAC_proj")
         return y
 
+    # ---- quasiparticle excitations of a transfer matrix (qp_statmech.py).  The presence of these methods tells the host code
+    # that the backend has the fused route; qp_calls counts the calls of each entry.
+    def _qp_count(self, name):
+        calls = self.__dict__.setdefault("qp_calls", {})
+        calls[name] = calls.get(name, 0) + 1
+
+    def qp_half(self, H, GL: DTensor, A: DTensor):
+        """mpsk_qp_half: stages 1 and 2 of (GL, A) as an opaque device buffer for qp_apply (the B-independent third term)."""
+        Wl, Dlo, Dl = GL.shape
+        Dla, d, Dr2 = A.shape
+        assert Dla == Dl and Wl == H.Wl and d == H.d, (GL.shape, A.shape)
+        n = C.c_size_t()
+        check(self.lib.mpsk_qp_half_size(H.handle, Dlo, Dr2, C.byref(n)), "mpsk_qp_half_size")
+        half = self.empty(n.value)
+        check(self.lib.mpsk_qp_half(self.ctx, H.handle, Dlo, Dl, Dr2, GL.ptr, A.ptr, half.ptr), "mpsk_qp_half")
+        self._qp_count("qp_half")
+        return half
+
+    def qp_apply(self, H, GL: DTensor, GR: DTensor, B: DTensor, lB: DTensor = None, AR: DTensor = None, half: DTensor = None,
+                 rB: DTensor = None, out: DTensor = None):
+        """mpsk_qp_apply: proj(GL, GR; B) + proj(lB, GR; AR) + half rB, with GL (Wl, Dlo, Dl), GR (Wr, Dr, Dro), B [Dl, d, Dr],
+        lB (Wl, Dlo, Dl2), AR [Dl2, d, Dr], half from qp_half(H, GL, AL [Dl, d, Dr2]), rB (Wr, Dr2, Dro).  Either pair may be
+        None."""
+        Wl, Dlo, Dl = GL.shape
+        Wr, Dr, Dro = GR.shape
+        assert B.shape == (Dl, H.d, Dr) and Wl == H.Wl and Wr == H.Wr, (GL.shape, GR.shape, B.shape)
+        assert (lB is None) == (AR is None) and (half is None) == (rB is None)
+        Dl2 = Dr2 = 0
+        if lB is not None:
+            Dl2 = lB.shape[2]
+            assert lB.shape == (Wl, Dlo, Dl2) and AR.shape == (Dl2, H.d, Dr), (lB.shape, AR.shape)
+        if rB is not None:
+            Dr2 = rB.shape[1]
+            assert rB.shape == (Wr, Dr2, Dro) and half.size == Wr * H.d * Dlo * Dr2, (rB.shape, half.shape)
+        y = self.empty(Dlo, H.d, Dro) if out is None else out
+        nul = lambda t: None if t is None else t.ptr
+        check(self.lib.mpsk_qp_apply(self.ctx, H.handle, Dlo, Dl, Dl2, Dr, Dr2, Dro, GL.ptr, GR.ptr, B.ptr, nul(lB), nul(AR),
+                                     nul(half), nul(rB), y.ptr), "mpsk_qp_apply")
+        self._qp_count("qp_apply")
+        return y
+
+    def transfer_left_pair(self, H, V1: DTensor, A1: DTensor, V2: DTensor, A2: DTensor, Ab: DTensor, out: DTensor = None):
+        """mpsk_transfer_left_pair: transfer_left(H, V1, A1, Ab) + transfer_left(H, V2, A2, Ab), stages 2 and 3 once."""
+        Dl1, d, Dr = A1.shape
+        Dl2 = A2.shape[0]
+        Dlb, _, Drb = Ab.shape
+        assert V1.shape == (H.Wl, Dlb, Dl1) and V2.shape == (H.Wl, Dlb, Dl2) and A2.shape == (Dl2, d, Dr) and d == H.d, \
+            (V1.shape, A1.shape, V2.shape, A2.shape, Ab.shape)
+        y = self.empty(H.Wr, Drb, Dr) if out is None else out
+        check(self.lib.mpsk_transfer_left_pair(self.ctx, H.handle, Dl1, Dl2, Dr, Dlb, Drb, V1.ptr, A1.ptr, V2.ptr, A2.ptr, Ab.ptr,
+                                               y.ptr), "mpsk_transfer_left_pair")
+        self._qp_count("transfer_left_pair")
+        return y
+
+    def transfer_right_pair(self, H, V1: DTensor, A1: DTensor, V2: DTensor, A2: DTensor, Ab: DTensor, out: DTensor = None):
+        """mpsk_transfer_right_pair: transfer_right(H, V1, A1, Ab) + transfer_right(H, V2, A2, Ab), stages 2 and 3 once."""
+        Dl, d, Dr1 = A1.shape
+        Dr2 = A2.shape[2]
+        Dlb, _, Drb = Ab.shape
+        assert V1.shape == (H.Wr, Dr1, Drb) and V2.shape == (H.Wr, Dr2, Drb) and A2.shape == (Dl, d, Dr2) and d == H.d, \
+            (V1.shape, A1.shape, V2.shape, A2.shape, Ab.shape)
+        y = self.empty(H.Wl, Dl, Dlb) if out is None else out
+        check(self.lib.mpsk_transfer_right_pair(self.ctx, H.handle, Dl, Dr1, Dr2, Dlb, Drb, A1.ptr, V1.ptr, A2.ptr, V2.ptr, Ab.ptr,
+                                                y.ptr), "mpsk_transfer_right_pair")
+        self._qp_count("transfer_right_pair")
+        return y
+
     def dC_proj(self, GL: DTensor, GR: DTensor, c: DTensor, out: DTensor = None):
         """mpsk_dC_proj (c_proj): the zero-site map with rectangular environments, GL (W, Dlo, Dl) and GR (W, Dr, Dro); c is
         [Dl, Dr], the result [Dlo, Dro].  Real fp64 only."""

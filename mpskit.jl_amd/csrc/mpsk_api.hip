@@ -633,6 +633,9 @@ struct Ws {
 };
 // K-segment lists: element offsets into A / B; j: plane of a complex B operand (the J-aware loader), empty for a real one
 struct Segs { std::vector<int64_t> a, b; std::vector<int> j; };
+// The two optional terms of mpsk_qp_apply on top of the plain projection: (lB, AR) joins stage 1 as a second product that
+// accumulates into T1, (half, rB) joins stage 3 as a second product that accumulates into y.  Either pair may be null.
+struct QpExtra { const double* lB; const double* AR; int Dl2; const double* half; const double* rB; int Dr2; };
 }  // namespace
 
 // over MPO levels: level v gives (v strideA, v strideB + pl planeB) for each of the `planes` (1: real, 2: re / im) planes
@@ -667,13 +670,13 @@ static void cx_operand(GemmArgs& g, int64_t stride, int j = 1) { g.nseg = 2; g.s
 // stage 1 of the left-to-right contractions: T1[w] = G[w] X for W slabs G[w] [M, K] and X [K, N] (complex: M = 2 x rows,
 // X the plane pair cx_stride apart).  X may come in nblk row blocks, which become K-segments (mpsk_dAC_blocked).
 static hipError_t stage1(mpsk_ctx* c, int W, int M, int K, int N, const double* G, const double* X, double* T1, int tag,
-                         int nblk = 1, int64_t cx_stride = 0) {
+                         int nblk = 1, int64_t cx_stride = 0, double beta = 0.0) {
   const int kb = K / nblk;
   GemmArgs g1 = mk(G, X, T1, M, N, kb, M, kb, M);
   g1.batch = W; g1.bsA = (int64_t)M * K; g1.bsB = 0; g1.bsC = (int64_t)M * N;
   g1.nseg = nblk;
   for (int q = 0; q < nblk; ++q) { g1.segA[q] = (int64_t)q * kb * M; g1.segB[q] = (int64_t)q * kb * N; }
-  g1.tag = tag;
+  g1.tag = tag; g1.beta = beta;
   if (cx_stride) cx_operand(g1, cx_stride);
   return gemm_f64(g1, c->stream);
 }
@@ -900,7 +903,7 @@ static int transfer_right_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int 
 // tensor): the blocks become K-segments of the stage-1 GEMM, nothing is re-interleaved (mpsk_dAC_blocked).
 // GR: Wr slabs [Dr, Dro], y: [Dlo, d, Dro]; the square matvec is Dro = Dr.
 static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR,
-                    const void* x, int nblk, void* y, double alpha = 1.0, double beta = 0.0) {
+                    const void* x, int nblk, void* y, double alpha = 1.0, double beta = 0.0, const QpExtra* q = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t slab = (size_t)Dlo * d * Dr;
@@ -910,6 +913,7 @@ static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
   // stage 1: T1[w] = GL[w] * x     (batched over w)
   HIPCHK(stage1(c, Wl, Dlo, Dl, d * Dr, (const double*)GL, (const double*)x, T1, 1, nblk));
+  if (q && q->lB) HIPCHK(stage1(c, Wl, Dlo, q->Dl2, d * Dr, q->lB, q->AR, T1, 1, 1, 0, 1.0));      // T1[w] += lB[w] AR
   // stage 2: T2[v][:,t,:] = sum_{w,s} O[w,t,s,v] T1[w][:,s,:]
   HIPCHK(mix_levels(c, H->fwd, d, Dlo, Dr, T1, T2));
   // stage 3: y = sum_v T2[v] * GR[v]   (K-segments over v)
@@ -919,6 +923,13 @@ static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   GemmArgs g3 = mk(T2, (const double*)GR, (double*)y, Dlo * d, Dro, Dr, (int64_t)Dlo * d, Dr, (int64_t)Dlo * d);
   g3.tag = 1; g3.alpha = alpha; g3.beta = beta;
   HIPCHK(gemm_segments(g3, sg, c->stream));
+  if (q && q->half) {                                                      // y += sum_v half[v] * rB[v]
+    Segs sh;
+    level_segs(sh, Wr, (int64_t)Dlo * d * q->Dr2, (int64_t)q->Dr2 * Dro, &H->col_used);
+    GemmArgs g4 = mk(q->half, q->rB, (double*)y, Dlo * d, Dro, q->Dr2, (int64_t)Dlo * d, q->Dr2, (int64_t)Dlo * d);
+    g4.tag = 1; g4.alpha = alpha; g4.beta = 1.0;
+    HIPCHK(gemm_segments(g4, sh, c->stream));
+  }
   return MPSK_OK;
 }
 
@@ -961,7 +972,8 @@ static int dense_tab(const mpsk_mposlice* H, bool right, int64_t P, int64_t Q, c
 }
 
 // stage 1 of the dense route: T[(r,b), (s,w)] = sum_a G[w][r,a] X[a,s,b]   (G: Wl slabs [R, Dk]; X: [Dk, d, Nb])
-static int dense_stage1(mpsk_ctx* c, const mpsk_mposlice* H, int R, int Dk, int Nb, const double* G, const double* X, double* T) {
+static int dense_stage1(mpsk_ctx* c, const mpsk_mposlice* H, int R, int Dk, int Nb, const double* G, const double* X, double* T,
+                        double beta = 0.0) {
   const int d = H->d;
   const int64_t* tab = nullptr;
   if (int rc = dense_tab(H, false, (int64_t)R * Dk, Dk, &tab)) return rc;
@@ -969,7 +981,7 @@ static int dense_stage1(mpsk_ctx* c, const mpsk_mposlice* H, int R, int Dk, int 
   g1.batch = H->Wl * d; g1.bsC = (int64_t)R * Nb;
   g1.tabA = tab; g1.tabB = tab + (size_t)H->Wl * d;
   g1.tabs_even = ((int64_t)R * Dk) % 2 == 0 && Dk % 2 == 0;
-  g1.tag = 1;
+  g1.tag = 1; g1.beta = beta;
   HIPCHK(gemm_f64(g1, c->stream));
   return MPSK_OK;
 }
@@ -984,7 +996,7 @@ static int dense_stage2(mpsk_ctx* c, const mpsk_mposlice* H, int64_t rows, const
 }
 
 static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const double* GL, const double* GR,
-                     const double* x, double* y, double alpha = 1.0, double beta = 0.0) {
+                     const double* x, double* y, double alpha = 1.0, double beta = 0.0, const QpExtra* q = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t slab = (size_t)Dlo * Dr;               // one (s,w) / (t,v) column of the intermediates
@@ -993,6 +1005,8 @@ static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int D
   if (int rc = ws.ensure(c)) return rc;
   double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
   if (int rc = dense_stage1(c, H, Dlo, Dl, Dr, GL, x, T1)) return rc;
+  if (q && q->lB)
+    if (int rc = dense_stage1(c, H, Dlo, q->Dl2, Dr, q->lB, q->AR, T1, 1.0)) return rc;      // T1 += lB AR
   if (int rc = dense_stage2(c, H, (int64_t)slab, T1, T2)) return rc;
   // stage 3: y[:, t, :] = sum_v T2[:, :, t, v] GR[v]    (batch over t; K-segments over v)
   Segs sg;
@@ -1002,12 +1016,23 @@ static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int D
   g3.batch = d; g3.bsA = (int64_t)slab; g3.bsB = 0; g3.bsC = Dlo;
   g3.tag = 1; g3.alpha = alpha; g3.beta = beta;
   HIPCHK(gemm_segments(g3, sg, c->stream));
+  if (q && q->half) {                                                      // y[:, t, :] += sum_v half[:, :, t, v] rB[v]
+    const size_t slab2 = (size_t)Dlo * q->Dr2;
+    Segs sh;
+    level_segs(sh, Wr, (int64_t)d * slab2, (int64_t)q->Dr2 * Dro, &H->col_used);
+    GemmArgs g4 = mk(q->half, q->rB, y, Dlo, Dro, q->Dr2, Dlo, q->Dr2, (int64_t)Dlo * d);
+    g4.batch = d; g4.bsA = (int64_t)slab2; g4.bsB = 0; g4.bsC = Dlo;
+    g4.tag = 1; g4.alpha = alpha; g4.beta = 1.0;
+    HIPCHK(gemm_segments(g4, sh, c->stream));
+  }
   return MPSK_OK;
 }
 
 // GLout[v][q,b] = sum GLin[w][p,a] A[a,s,b] O[w,t,s,v] Ab[p,t,q]
+// (V2, A2 [Dl2, d, Dr]): a second stage-1 product that accumulates into T1 (mpsk_transfer_left_pair)
 static int transfer_left_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dr, int Dlb, int Drb, const double* GLin,
-                               const double* A, const double* Ab, double* GLout) {
+                               const double* A, const double* Ab, double* GLout, const double* V2 = nullptr,
+                               const double* A2 = nullptr, int Dl2 = 0) {
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t slab = (size_t)Dlb * Dr;
   Ws ws;
@@ -1015,6 +1040,8 @@ static int transfer_left_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int 
   if (int rc = ws.ensure(c)) return rc;
   double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
   if (int rc = dense_stage1(c, H, Dlb, Dl, Dr, GLin, A, T1)) return rc;
+  if (V2)
+    if (int rc = dense_stage1(c, H, Dlb, Dl2, Dr, V2, A2, T1, 1.0)) return rc;
   if (int rc = dense_stage2(c, H, (int64_t)slab, T1, T2)) return rc;
   // GLout[v][q,b] = sum_t sum_p Ab[p,t,q] T2[(p,b), (t,v)]     (batch over v; K-segments over t)
   Segs sg;
@@ -1885,7 +1912,8 @@ static int transfer_right_canonical(mpsk_ctx* c, const mpsk_mposlice* H, int Dl,
 // envR (with gram, Wl == 1): as in transfer_left_c128
 static int transfer_left_f64(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr, int d, int Dl, int Dr, int Dlb, int Drb,
                              const void* GLin, const void* A, const void* Ab, void* GLout, double* gram,
-                             const double* envR = nullptr) {
+                             const double* envR = nullptr, const double* V2 = nullptr, const double* A2 = nullptr,
+                             int Dl2 = 0) {
   const size_t slab = (size_t)Dlb * d * Dr;
   Ws ws;
   const size_t o_t = ws.take(slab * (Wl + (H ? Wr : 0)), gram ? 32 : 1);      // T1, then T2 when there is a mix
@@ -1894,6 +1922,7 @@ static int transfer_left_f64(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int Wr
   double* T1 = Ws::at(c, o_t);
   double* T2 = H ? T1 + slab * Wl : T1;
   HIPCHK(stage1(c, Wl, Dlb, Dl, d * Dr, (const double*)GLin, (const double*)A, T1, 0));      // T1[w][p,s,b] = sum_a GLin[w][p,a] A[a,s,b]
+  if (V2) HIPCHK(stage1(c, Wl, Dlb, Dl2, d * Dr, V2, A2, T1, 0, 1, 0, 1.0));                 // T1[w] += V2[w] A2  (the pair transfer)
   if (H) HIPCHK(mix_levels(c, H->fwd, d, Dlb, Dr, T1, T2));
   if (gram && envR)
     HIPCHK(gram_env(d, Dlb, Dr, Drb, T1, envR, 0, (const double*)Ab, false, gram, Ws::at(c, o_part), c->stream));
@@ -3660,8 +3689,9 @@ static int half_left(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int D
 }
 
 // right half: T1 (scratch, Wr d Dm Dro) and R2 (result, Wm d Dm Dro).  GR: Wr slabs [Dr, Dro] (Dro = Dr: mpsk_dAC2_product)
+// (AR2 [Dm, d, Dr2], GR2: Wr slabs [Dr2, Dro]): a second stage-1 product that accumulates into T1 (mpsk_transfer_right_pair)
 static int half_right(mpsk_ctx* c, const mpsk_mposlice* H, int Dm, int Dr, int Dro, const double* AR, const double* GR,
-                      double* T1, double* R2, HalfView* v) {
+                      double* T1, double* R2, HalfView* v, const double* AR2 = nullptr, const double* GR2 = nullptr, int Dr2 = 0) {
   const int d = H->d;
   if (dense_route(H)) {
     const int64_t col = (int64_t)Dm * Dro;
@@ -3673,6 +3703,15 @@ static int half_right(mpsk_ctx* c, const mpsk_mposlice* H, int Dm, int Dr, int D
     g1.tabs_even = Dm % 2 == 0 && ((int64_t)Dr * Dro) % 2 == 0;
     g1.tag = 1;
     HIPCHK(gemm_f64(g1, c->stream));
+    if (AR2) {
+      if (int rc = dense_tab(H, true, Dm, (int64_t)Dr2 * Dro, &tab)) return rc;
+      GemmArgs h1 = mk(AR2, GR2, T1, Dm, Dro, Dr2, (int64_t)Dm * d, Dr2, Dm);
+      h1.batch = H->Wr * d; h1.bsC = col;
+      h1.tabA = tab; h1.tabB = tab + (size_t)H->Wr * d;
+      h1.tabs_even = Dm % 2 == 0 && ((int64_t)Dr2 * Dro) % 2 == 0;
+      h1.tag = 1; h1.beta = 1.0;
+      HIPCHK(gemm_f64(h1, c->stream));
+    }
     GemmArgs g2 = mk(T1, H->d_OdR, R2, (int)col, d * H->Wl, d * H->Wr, col, (int64_t)d * H->Wr, col);   // R2[(m,b), (t,u)]
     g2.tag = 1;
     HIPCHK(gemm_f64(g2, c->stream));
@@ -3684,6 +3723,12 @@ static int half_right(mpsk_ctx* c, const mpsk_mposlice* H, int Dm, int Dr, int D
   g1.batch = H->Wr; g1.bsA = 0; g1.bsB = (int64_t)Dr * Dro; g1.bsC = slab;
   g1.tag = 1;
   HIPCHK(gemm_f64(g1, c->stream));
+  if (AR2) {
+    GemmArgs h1 = mk(AR2, GR2, T1, Dm * d, Dro, Dr2, (int64_t)Dm * d, Dr2, (int64_t)Dm * d);
+    h1.batch = H->Wr; h1.bsA = 0; h1.bsB = (int64_t)Dr2 * Dro; h1.bsC = slab;
+    h1.tag = 1; h1.beta = 1.0;
+    HIPCHK(gemm_f64(h1, c->stream));
+  }
   HIPCHK(mix_levels(c, H->rgt, d, Dm, Dro, T1, R2));                             // R2[u][m,t,b]
   *v = HalfView{R2, Dm, slab, (int64_t)Dm * d};
   return MPSK_OK;
@@ -3727,6 +3772,99 @@ int mpsk_dAC2_product(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice*
   REQUIRE(Dl > 0 && Dm > 0 && Dr > 0, "dimensions must be positive");
   REQUIRE(H1->dtype == MPSK_F64 && H2->dtype == MPSK_F64, "MPSK_F64 slices only");
   return dAC2_factorised(c, H1, H2, Dl, Dl, Dm, Dr, Dr, GL, GR, AC, AR, Y);
+}
+
+}  // extern "C"
+
+// ---- quasiparticle excitations of a transfer matrix (quasiparticleexcitation.jl:258-293, qpenv.jl:238-251) -----------------
+// The three projections of one application share the slice: the (lB, AR) product joins stage 1 of the (GL, B) chain, the
+// (GL, AL) chain does not depend on B and is kept by the caller as `half` (stages 1 and 2, half_left), and joins stage 3.
+// The pair transfers add two stage-1 products and run stages 2 and 3 once; the right one contracts the ket first
+// (half_right, the order of the two-site product), so that both terms meet in one intermediate [Dl, d, Drb].
+static int qp_f64_only(const mpsk_ctx* c, const mpsk_mposlice* H, const char* who) {
+  if (H->dtype != MPSK_F64 || c->dtype != MPSK_F64) return fail(MPSK_ERR_UNSUPPORTED, std::string(who) + " is implemented for MPSK_F64 only");
+  return MPSK_OK;
+}
+
+extern "C" {
+int mpsk_qp_half_size(const mpsk_mposlice* H, int Dlo, int Dr2, size_t* doubles) {
+  REQUIRE(H && doubles, "NULL argument");
+  REQUIRE(Dlo > 0 && Dr2 > 0, "dimensions must be positive");
+  *doubles = (size_t)Dlo * H->d * Dr2 * H->Wr;
+  return MPSK_OK;
+}
+
+int mpsk_qp_half(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr2, const void* GL, const void* A, void* half) {
+  REQUIRE(c && H && GL && A && half, "NULL argument");
+  REQUIRE(Dlo > 0 && Dl > 0 && Dr2 > 0, "dimensions must be positive");
+  if (int rc = qp_f64_only(c, H, "mpsk_qp_half")) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  Ws ws;
+  const size_t o_t1 = ws.take((size_t)Dlo * H->d * Dr2 * H->Wl);
+  if (int rc = ws.ensure(c)) return rc;
+  HalfView v;
+  return half_left(c, H, Dlo, Dl, Dr2, (const double*)GL, (const double*)A, Ws::at(c, o_t1), (double*)half, &v);
+}
+
+int mpsk_qp_apply(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dl2, int Dr, int Dr2, int Dro, const void* GL,
+                  const void* GR, const void* B, const void* lB, const void* AR, const void* half, const void* rB, void* y) {
+  REQUIRE(c && H && GL && GR && B && y, "NULL argument");
+  REQUIRE((lB == nullptr) == (AR == nullptr), "lB and AR are given together or not at all");
+  REQUIRE((half == nullptr) == (rB == nullptr), "half and rB are given together or not at all");
+  REQUIRE(Dlo > 0 && Dl > 0 && Dr > 0 && Dro > 0, "dimensions must be positive");
+  REQUIRE((!lB || Dl2 > 0) && (!half || Dr2 > 0), "dimensions must be positive");
+  if (int rc = qp_f64_only(c, H, "mpsk_qp_apply")) return rc;
+  const QpExtra q{(const double*)lB, (const double*)AR, Dl2, (const double*)half, (const double*)rB, Dr2};
+  const QpExtra* qp = (lB || half) ? &q : nullptr;
+  if (dense_route(H))
+    return dAC_dense(c, H, Dlo, Dl, Dr, Dro, (const double*)GL, (const double*)GR, (const double*)B, (double*)y, 1.0, 0.0, qp);
+  return dAC_impl(c, H, Dlo, Dl, Dr, Dro, GL, GR, B, 1, y, 1.0, 0.0, qp);
+}
+
+int mpsk_transfer_left_pair(mpsk_ctx* c, const mpsk_mposlice* H, int Dl1, int Dl2, int Dr, int Dlb, int Drb, const void* V1,
+                            const void* A1, const void* V2, const void* A2, const void* Ab, void* out) {
+  REQUIRE(c && H && V1 && A1 && V2 && A2 && Ab && out, "NULL argument");
+  REQUIRE(Dl1 > 0 && Dl2 > 0 && Dr > 0 && Dlb > 0 && Drb > 0, "dimensions must be positive");
+  if (int rc = qp_f64_only(c, H, "mpsk_transfer_left_pair")) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if (dense_route(H))
+    return transfer_left_dense(c, H, Dl1, Dr, Dlb, Drb, (const double*)V1, (const double*)A1, (const double*)Ab, (double*)out,
+                               (const double*)V2, (const double*)A2, Dl2);
+  return transfer_left_f64(c, H, H->Wl, H->Wr, H->d, Dl1, Dr, Dlb, Drb, V1, A1, Ab, out, nullptr, nullptr, (const double*)V2,
+                           (const double*)A2, Dl2);
+}
+
+int mpsk_transfer_right_pair(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dr1, int Dr2, int Dlb, int Drb, const void* A1,
+                             const void* V1, const void* A2, const void* V2, const void* Ab, void* out) {
+  REQUIRE(c && H && V1 && A1 && V2 && A2 && Ab && out, "NULL argument");
+  REQUIRE(Dl > 0 && Dr1 > 0 && Dr2 > 0 && Dlb > 0 && Drb > 0, "dimensions must be positive");
+  if (int rc = qp_f64_only(c, H, "mpsk_transfer_right_pair")) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  const int d = H->d, Wl = H->Wl, Wr = H->Wr;
+  const size_t slab = (size_t)Dl * d * Drb;
+  Ws ws;
+  const size_t o_t1 = ws.take(slab * Wr), o_t2 = ws.take(slab * Wl);
+  if (int rc = ws.ensure(c)) return rc;
+  HalfView v;
+  if (int rc = half_right(c, H, Dl, Dr1, Drb, (const double*)A1, (const double*)V1, Ws::at(c, o_t1), Ws::at(c, o_t2), &v,
+                          (const double*)A2, (const double*)V2, Dr2))
+    return rc;
+  const double* T2 = Ws::at(c, o_t2);
+  if (dense_route(H)) {
+    // out[w][a,p] = sum_t sum_q T2[(a,q), (t,w)] Ab[p,t,q]     (batch over w; K-segments over t)
+    const int64_t col = (int64_t)Dl * Drb;
+    Segs sg;
+    phys_segs(sg, d, col, Dlb);
+    GemmArgs g3 = mk(T2, (const double*)Ab, (double*)out, Dl, Dlb, Drb, Dl, (int64_t)Dlb * d, Dl, 0, 1);
+    g3.batch = Wl; g3.bsA = col * d; g3.bsB = 0; g3.bsC = (int64_t)Dl * Dlb;
+    HIPCHK(gemm_segments(g3, sg, c->stream));
+    return MPSK_OK;
+  }
+  // out[w][a,p] = sum_{(t,q)} T2[w][a,(t,q)] Ab[p,(t,q)]
+  GemmArgs g3 = mk(T2, (const double*)Ab, (double*)out, Dl, Dlb, d * Drb, Dl, Dlb, Dl, 0, 1);
+  g3.batch = Wl; g3.bsA = (int64_t)slab; g3.bsB = 0; g3.bsC = (int64_t)Dl * Dlb;
+  HIPCHK(gemm_f64(g3, c->stream));
+  return MPSK_OK;
 }
 
 }  // extern "C"

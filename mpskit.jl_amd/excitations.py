@@ -119,12 +119,19 @@ def excitations(H, alg, *args, **kw):
       FiniteExcited:        excitations(H, alg, psi0::FiniteMPS; num, init)                     dmrgexcitation.jl:13-36
       QuasiparticleAnsatz:  excitations(H, alg, momentum | momenta, psi::InfiniteMPS[, envs]; num)   quasiparticleexcitation.jl:84-125
                             excitations(H, alg, psi::FiniteMPS[, envs]; num)                    :163-169
-                            excitations(H, alg, phi0::LeftGaugedQP[, envs]; num)                :39-53,127-143"""
+                            excitations(H, alg, phi0::LeftGaugedQP[, envs]; num)                :39-53,127-143
+                            excitations(H::DenseMPO | MPOMultiline, alg, momentum | momenta | [LeftGaugedQP per row],
+                                        psi::InfiniteMPS | MPSMultiline[, envs]; num, device)   :170-228"""
     from .quasiparticle import QuasiparticleAnsatz, LeftGaugedQP, excitations_qp, excitations_momenta
     if isinstance(alg, FiniteExcited):
         return _excitations_finite_excited(H, alg, *args, **kw)
     if not isinstance(alg, QuasiparticleAnsatz):
         raise TypeError(f"excitations: unknown algorithm {type(alg).__name__}")
+    from .statmech import DenseMPO
+    from .multiline import MPOMultiline
+    if isinstance(H, (DenseMPO, MPOMultiline)):                  # the row-to-row transfer matrix  :170-228
+        from .quasiparticle import excitations_statmech
+        return excitations_statmech(H, alg, *args, **kw)
     if isinstance(args[0], LeftGaugedQP):
         return excitations_qp(H, alg, *args, **kw)
     if isinstance(args[0], FiniteMPS):

@@ -576,3 +576,97 @@ def arnoldi_eigvals(be: Backend, matvec, x0: DTensor, num=1, tol=1e-10, krylovdi
             if conv >= min(num, k) or beta < 1e-300:
                 break
     return vals[:num], conv
+
+
+def _planar_times_i(be, x: DTensor, out: DTensor):
+    """out = i x on a planar vector [Re | Im]: [-Im | Re]."""
+    N = x.size // 2
+    be.lincomb([DTensor(x.buf[N:2 * N], (N,))], [-1.0], out=DTensor(out.buf[:N], (N,)))
+    be.lincomb([DTensor(x.buf[:N], (N,))], [1.0], out=DTensor(out.buf[N:2 * N], (N,)))
+    return out
+
+
+def eigsolve_lm_planar(be: Backend, matvec, x0: DTensor, num=1, tol=1e-10, krylovdim=30, maxiter=100):
+    """The `num` largest-magnitude (:LM) eigenpairs of a COMPLEX-linear, non-Hermitian operator acting on planar complex
+    vectors x = [Re | Im] (one real device vector of even length): KrylovKit's eigsolve(f, x0, num, :LM, Arnoldi(...))
+    as the statistical-mechanics quasiparticle solver calls it (quasiparticleexcitation.jl:182).
+
+    The arithmetic is complex throughout: the inner product is <x, y> + i <i x, y> from two real dots (i x = [-Im | Re]),
+    the Hessenberg matrix is complex and every linear combination a x is Re(a) x + Im(a) (i x), so the basis is kept as
+    the pairs (v, i v).  A real Arnoldi on the 2N-dimensional embedding would instead return every eigenvalue together
+    with its conjugate and mix their vectors.  Restart: the `keep` leading Ritz vectors are orthonormalised (QR of the
+    eigenvector block) and the factorisation A V = V H + v r^H continues from them (a thick restart; H stays a general
+    matrix, not Hessenberg, which the Ritz step does not need).
+
+    Returns (complex eigenvalues [num], vectors [num] (planar, unit norm), residuals [num], number converged); a residual
+    is |r^H s| for the Ritz pair (theta, V s).  Warns when fewer than `num` converged."""
+    n2 = x0.size
+    assert n2 % 2 == 0, "a planar complex vector has even length"
+    m = int(max(min(krylovdim, n2 // 2), 1))
+    num = int(min(num, n2 // 2))
+    V = [be.empty(n2) for _ in range(m + 1)]
+    IV = [be.empty(n2) for _ in range(m + 1)]
+    w, tmp = be.empty(n2), be.empty(n2)
+    be.axpby(1.0 / be.norm(x0), x0.reshape(n2), 0.0, V[0])
+    _planar_times_i(be, V[0], IV[0])
+    H = np.zeros((m + 1, m), dtype=complex)
+    k = 0
+    vals = S = res = None
+    conv = 0
+    for _restart in range(maxiter):
+        while k < m:
+            matvec(V[k], w)
+            basis = V[:k + 1] + IV[:k + 1]
+            h = np.zeros(k + 1, dtype=complex)
+            for _ in range(2):                                       # classical Gram-Schmidt, twice
+                dts = be.multidot(basis, w)
+                c = dts[:k + 1] + 1j * dts[k + 1:]                   # <v_j, w> = <v_j, w>_R + i <i v_j, w>_R
+                be.lincomb([w] + basis, [1.0] + list(-c.real) + list(-c.imag), out=tmp)
+                w, tmp = tmp, w
+                h += c
+            beta = be.norm(w)
+            H[:k + 1, k] = h
+            H[k + 1, k] = beta
+            k += 1
+            if beta < 1e-300:
+                break
+            be.axpby(1.0 / beta, w, 0.0, V[k])
+            _planar_times_i(be, V[k], IV[k])
+            if k >= num and (k % 3 == 0 or k == m):
+                ev, S = np.linalg.eig(H[:k, :k])
+                order = np.argsort(-np.abs(ev))
+                vals, S = ev[order], S[:, order]
+                res = np.abs(H[k, :k] @ S)
+                conv = int(np.sum(res[:num] < tol))
+                if conv >= num:
+                    break
+        ev, S = np.linalg.eig(H[:k, :k])
+        order = np.argsort(-np.abs(ev))
+        vals, S = ev[order], S[:, order]
+        res = np.abs(H[k, :k] @ S) if k < H.shape[0] else np.zeros(k)
+        conv = int(np.sum(res[:num] < tol))
+        if conv >= num or H[k, k - 1].real < 1e-300 or k < m:
+            break
+        keep = min(max(num + 2, m // 3), m - 1)
+        Q, _ = np.linalg.qr(S[:, :keep])
+        newV = [be.lincomb(V[:k] + IV[:k], list(Q[:, j].real) + list(Q[:, j].imag)) for j in range(keep)]
+        Hk = Q.conj().T @ H[:k, :k] @ Q
+        r = H[k, :k] @ Q
+        for j in range(keep):
+            be.axpby(1.0, newV[j], 0.0, V[j])
+            _planar_times_i(be, V[j], IV[j])
+        be.axpby(1.0, V[k], 0.0, V[keep])
+        _planar_times_i(be, V[keep], IV[keep])
+        H[:] = 0.0
+        H[:keep, :keep] = Hk
+        H[keep, :keep] = r
+        k = keep
+    vecs = []
+    for j in range(num):
+        s = S[:, j]
+        v = be.lincomb(V[:k] + IV[:k], list(s.real) + list(s.imag))
+        vecs.append(be.scal(1.0 / be.norm(v), v))
+    if conv < num:
+        import warnings
+        warnings.warn(f"eigsolve_lm_planar: {conv} of {num} eigenvalues converged, normres = {res[:num]}")
+    return vals[:num], vecs, res[:num], conv

@@ -11,8 +11,8 @@ A column update acts on the STACKED vector of all rows' AC (or CR): one contiguo
 Krylov kernels run on it unchanged.  The map is out[r + shift] = H_AC[r] x[r] (derivatives.jl:163-166, :195-197: shift = 1 is the
 reference's circshift, shift = 0 the plain batch of calc_galerkin).  One application is a loop of dAC_proj / dC_proj over the
 rows, each result copied into its slot; rows of different bond dimensions are allowed.  A launch chain that batches the rows
-of a column is not implemented.  Real fp64 only; GradientGrassmann, changebonds, excitations and the IDMRG forms of
-approximate are not implemented for more than one row."""
+of a column is not implemented.  Real fp64 only; GradientGrassmann, changebonds and the IDMRG forms of approximate are not
+implemented for more than one row (excitations: quasiparticle.excitations_statmech)."""
 from __future__ import annotations
 
 import time

@@ -20,8 +20,10 @@ R^{2N} = [Re | Im] with every eigenvalue doubled (v and i v); the Lanczos solver
 
 Built: LeftGaugedQP over an MPOHamiltonian -- FiniteQP, InfiniteQP at any momentum, topologically trivial
 (left_gs is right_gs, regularised environments) and domain-wall excitations between two different ground states (no
-regularisation, energies renormalised by the mean of the two); `variance` of a finite QP state (toolbox.py).  Not built:
-charged sectors, the statistical-mechanics (MPOMultiline) variant, RightGaugedQP conversion."""
+regularisation, energies renormalised by the mean of the two); `variance` of a finite QP state (toolbox.py); the
+statistical-mechanics method over a DenseMPO / MPOMultiline (excitations_statmech at the end of this file: topologically
+trivial, two real parts at every momentum).  Not built: charged sectors, RightGaugedQP conversion, domain walls and
+`variance` of a statistical-mechanics quasiparticle."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -402,6 +404,330 @@ def excitations_momenta(H, alg: QuasiparticleAnsatz, momenta, psi, lenvs=None, r
     Ep, Bp = [], []
     for p in momenta:
         e, b = excitations_qp(H, alg, LeftGaugedQP.random(psi, float(p), rng, rpsi), lenvs, renvs, num)
+        Ep.append(e)
+        Bp.append(b)
+    return np.array(Ep), Bp
+
+
+# ======================================================================================================================
+# Statistical-mechanics excitations: excitations(H::DenseMPO | MPOMultiline, QuasiparticleAnsatz(), momentum, psi, envs)
+# (quasiparticleexcitation.jl:170-228 dispatch, :258-293 effective operator, qpenv.jl:171-303 environments)
+# ======================================================================================================================
+# device=None picks the route per slice kind from the measured table (tools/bench_qp_statmech.py,
+# profiles/qp_statmech_timings.json, README): "mix" = slices whose MPO stage is the slab mix (chi d below the crossover of
+# mpsk_mposlice_create_dense), "gemm" = slices whose MPO stage is a GEMM of its own.
+FUSED_BY_DEFAULT = {"mix": True, "gemm": True}
+
+
+def _slice_kind(O):
+    import os
+    ev = os.environ.get("MPSK_DENSE_ROUTE", "")
+    if ev[:1] in ("0", "1"):
+        return "gemm" if ev[0] == "1" else "mix"
+    return "gemm" if min(O.Wl, O.Wr) * O.d >= 8 else "mix"
+
+
+def _use_fused(be, device, O):
+    has = all(hasattr(be, m) for m in ("qp_half", "qp_apply", "transfer_left_pair", "transfer_right_pair"))
+    if device and not has:
+        from ._lib import MpskError
+        raise MpskError("device=True: this backend has no mpsk_qp_apply / pair transfers")
+    if device is None:
+        return has and FUSED_BY_DEFAULT[_slice_kind(O)]
+    return bool(device)
+
+
+def _cscale(be, z, s):
+    """(re, im) * s for a complex scalar s."""
+    re, im = z
+    a, b = float(np.real(s)), float(np.imag(s))
+    return [be.lincomb([re, im], [a, -b]), be.lincomb([re, im], [b, a])]
+
+
+class _StatmechContext:
+    """Everything of the effective operator that depends neither on the momentum nor on X: per (row, column) the slice, the
+    tensors of the row above and the row below, the environments, the site eigenvalue lam = <AC_below, H_AC AC_above> (its
+    inverse is the reference's left_renorms = right_renorms of a topologically trivial excitation, qpenv.jl:205-226, and lam
+    itself the `en` every site of the result is divided by, quasiparticleexcitation.jl:267-271), the fixed points
+    that regularise the two mixed transfer matrices (qpenv.jl:259-271), and on the fused route the B-independent halves.
+
+    Rows of different bond dimensions: the reference writes `en` and the lvec of tm_LR with the legs of the two rows
+    exchanged, which is the same number only when the rows are equal; here both are contracted as the network
+    dictates (bra legs with the row below), and they agree with the reference whenever its expressions are defined."""
+
+    def __init__(self, psi, rows_env, alg, device):
+        self.be = be = psi.be
+        self.alg = alg
+        self.R, self.n = R, n = psi.shape
+        self.psi = psi
+        self.O = [[rows_env[r].O(c) for c in range(n)] for r in range(R)]
+        self.GL = [[rows_env[r].lw[c] for c in range(n)] for r in range(R)]
+        self.GR = [[rows_env[r].rw[c] for c in range(n)] for r in range(R)]
+        self.fused = _use_fused(be, device, self.O[0][0])
+        self.lam = [[be.dot(psi.AC[r + 1, c], self._proj(self.O[r][c], self.GL[r][c], self.GR[r][c], psi.AC[r, c]))
+                     for c in range(n)] for r in range(R)]
+        self.ws = krylov.KrylovWorkspace(be)
+        self.Ll, self.Rl, self.Rr, self.Lr = [], [], [], []
+        for r in range(R):
+            Ca, Cb = psi.CR[r, n - 1], psi.CR[r + 1, n - 1]
+            gl, gr = self.GL[r][0], self.GR[r][n - 1]
+            W = gl.shape[0]
+            sl = lambda t, w: _view(t, w * t.shape[1] * t.shape[2], t.shape[1:])
+            Ll, Rl, Rr, Lr = be.empty(gl.shape), be.empty(gl.shape), be.empty(gr.shape), be.empty(gr.shape)
+            for w in range(W):
+                be.gemm(sl(gl, w), Ca, out=sl(Ll, w))                       # left fixed point of T(AR above, AL below)
+                be.gemm(Cb, sl(gr, w), transB=True, out=sl(Rl, w))          # its right fixed point, slabs transposed
+                be.gemm(Ca, sl(gr, w), out=sl(Rr, w))                       # right fixed point of T(AL above, AR below)
+                be.gemm(sl(gl, w), Cb, transA=True, out=sl(Lr, w))          # its left fixed point, slabs transposed
+            self.Ll.append(Ll), self.Rl.append(Rl), self.Rr.append(Rr), self.Lr.append(Lr)
+        self.half = None
+        if self.fused:                                                       # once per site and ground state
+            self.half = [[be.qp_half(self.O[r][c], self.GL[r][c], psi.AL[r, c]) for c in range(n)] for r in range(R)]
+
+    # ---- the two routes ----
+    def _proj(self, O, GL, GR, x):
+        be = self.be
+        if hasattr(be, "dAC_proj"):
+            return be.dAC_proj(O, GL, GR, x)
+        return be.dAC(O, GL, GR, x, out=be.empty(GL.shape[1], x.shape[1], GR.shape[2]))
+
+    def _tl(self, O, V, A, Ab):
+        f = getattr(self.be, "transfer_left_ex", None)
+        return f(O, V, A, Ab) if f is not None else self.be.transfer_left(O, V, A, Ab)
+
+    def _tr(self, O, V, A, Ab):
+        f = getattr(self.be, "transfer_right_ex", None)
+        return f(O, V, A, Ab) if f is not None else self.be.transfer_right(O, V, A, Ab)
+
+    def _tl_pair(self, O, V1, A1, V2, A2, Ab):
+        be = self.be
+        if self.fused:
+            return be.transfer_left_pair(O, V1, A1, V2, A2, Ab)
+        return be.axpby(1.0, self._tl(O, V2, A2, Ab), 1.0, self._tl(O, V1, A1, Ab))
+
+    def _tr_pair(self, O, V1, A1, V2, A2, Ab):
+        be = self.be
+        if self.fused:
+            return be.transfer_right_pair(O, V1, A1, V2, A2, Ab)
+        return be.axpby(1.0, self._tr(O, V2, A2, Ab), 1.0, self._tr(O, V1, A1, Ab))
+
+    def _local(self, r, c, B, lB, rB):
+        """T = GL B O GR + lB AR O GR + GL AL O rB   (quasiparticleexcitation.jl:273-286), one real part."""
+        be, psi = self.be, self.psi
+        O, GL, GR = self.O[r][c], self.GL[r][c], self.GR[r][c]
+        if self.fused:
+            return be.qp_apply(O, GL, GR, B, lB, psi.AR[r, c], self.half[r][c], rB)
+        T = self._proj(O, GL, GR, B)
+        be.axpby(1.0, self._proj(O, lB, GR, psi.AR[r, c]), 1.0, T)
+        be.axpby(1.0, self._proj(O, GL, rB, psi.AL[r, c]), 1.0, T)
+        return T
+
+    # ---- qpenv.jl:171-303 for one row ----
+    def _geometric_sum(self, left, r, b, coef):
+        """x = b + coef x T_reg (left) / b + coef T_reg x (right): one GMRES solve on the planar pair (qpenv.jl:273-283)."""
+        be, psi, n = self.be, self.psi, self.n
+        shape, sz = b[0].shape, b[0].size
+        flat = be.empty(2 * sz)
+        for k in range(2):
+            flat.buf[k * sz:(k + 1) * sz].copy_(b[k].buf[:sz])
+        lv, rv = (self.Rl[r], self.Ll[r]) if left else (self.Lr[r], self.Rr[r])
+        a, bb = float(np.real(coef)), float(np.imag(coef))
+
+        def op(x, out):
+            ys = []
+            for k in range(2):
+                v = _view(x, k * sz, shape)
+                if left:
+                    for c in range(n):
+                        v = self._tl(self.O[r][c], v, psi.AR[r, c], psi.AL[r + 1, c])
+                else:
+                    for c in range(n - 1, -1, -1):
+                        v = self._tr(self.O[r][c], v, psi.AL[r, c], psi.AR[r + 1, c])
+                be.axpby(-be.dot(v, lv), rv, 1.0, v)                        # regularize!(v, lvec, rvec), transfermatrix.jl:83-85
+                ys.append(v)
+            xs = [_view(x, k * sz, shape) for k in range(2)]
+            be.lincomb([xs[0], ys[0], ys[1]], [1.0, -a, bb], out=_view(out, 0, shape))
+            be.lincomb([xs[1], ys[0], ys[1]], [1.0, -bb, -a], out=_view(out, sz, shape))
+            return out
+
+        sol = krylov.gmres(be, op, flat, flat, tol=self.alg.solver_tol, maxiter=self.alg.solver_maxiter, ws=self.ws)
+        return [be.copy(_view(sol, k * sz, shape)) for k in range(2)]
+
+    def qp_envs(self, r, Bs, p):
+        be, psi, n = self.be, self.psi, self.n
+        O, GL, GR = self.O[r], self.GL[r], self.GR[r]
+        ARa, ALa = [psi.AR[r, c] for c in range(n)], [psi.AL[r, c] for c in range(n)]
+        ALb, ARb = [psi.AL[r + 1, c] for c in range(n)], [psi.AR[r + 1, c] for c in range(n)]
+        ren = [1.0 / self.lam[r][c] for c in range(n)]
+        el, er = np.exp(-1j * p), np.exp(1j * p)
+        lBs, rBs = [None] * n, [None] * n
+        cur = None
+        for c in range(n):                                                   # :238-244
+            if cur is None:
+                nxt = [self._tl(O[c], GL[c], Bs[c][k], ALb[c]) for k in range(2)]
+            else:
+                nxt = [self._tl_pair(O[c], cur[k], ARa[c], GL[c], Bs[c][k], ALb[c]) for k in range(2)]
+            cur = lBs[c] = _cscale(be, nxt, ren[c] * el)
+        cur = None
+        for c in range(n - 1, -1, -1):                                       # :246-252
+            if cur is None:
+                nxt = [self._tr(O[c], GR[c], Bs[c][k], ARb[c]) for k in range(2)]
+            else:
+                nxt = [self._tr_pair(O[c], cur[k], ALa[c], GR[c], Bs[c][k], ARb[c]) for k in range(2)]
+            cur = rBs[c] = _cscale(be, nxt, ren[c] * er)
+        prod = float(np.prod(ren))
+        lBs[n - 1] = self._geometric_sum(True, r, lBs[n - 1], el ** n * prod)      # :273-277
+        rBs[0] = self._geometric_sum(False, r, rBs[0], er ** n * prod)             # :279-283
+        cur = lBs[n - 1]
+        for c in range(n - 1):                                               # :285-291
+            cur = _cscale(be, [self._tl(O[c], cur[k], ARa[c], ALb[c]) for k in range(2)], ren[c] * el)
+            _acc(be, lBs[c], cur)
+        cur = rBs[0]
+        for c in range(n - 1, 0, -1):                                        # :293-299
+            cur = _cscale(be, [self._tr(O[c], cur[k], ALa[c], ARb[c]) for k in range(2)], ren[c] * er)
+            _acc(be, rBs[c], cur)
+        return lBs, rBs
+
+
+class MultilineQP:
+    """Multiline{<:InfiniteQP}: one LeftGaugedQP per row on one flat device vector [Re rows | Im rows].  qp[r] is the row
+    as a LeftGaugedQP of its own (two parts)."""
+
+    def __init__(self, rows, momentum, vec=None):
+        self.be = rows[0].be
+        self.rows, self.momentum = rows, float(momentum)
+        self.Ns = [q.N for q in rows]
+        self.roff = np.concatenate([[0], np.cumsum(self.Ns)]).astype(int)
+        self.N = int(self.roff[-1])
+        if vec is None:
+            vec = self.be.empty(2 * self.N)
+            for r, q in enumerate(rows):
+                for k in range(2):
+                    dst = _view(vec, k * self.N + int(self.roff[r]), (q.N,))
+                    if k < q.nparts:
+                        self.be.axpby(1.0, _view(q.vec, k * q.N, (q.N,)), 0.0, dst)
+                    else:
+                        self.be.scal(0.0, dst)
+        self.vec = vec
+
+    def __len__(self):
+        return len(self.rows)
+
+    def X(self, part, r, c, vec=None):
+        q = self.rows[r % len(self.rows)]
+        vec = self.vec if vec is None else vec
+        return _view(vec, part * self.N + int(self.roff[r % len(self.rows)]) + int(q.offs[c]), q.xshapes[c])
+
+    def B(self, part, r, c, vec=None):
+        q = self.rows[r % len(self.rows)]
+        Dl, d, _ = q.left_gs.AL[c].shape
+        return self.be.gemm(q.VLs[c], self.X(part, r, c, vec)).reshape(Dl, d, q.xshapes[c][1])
+
+    def __getitem__(self, r):
+        q = self.rows[r % len(self.rows)]
+        be = self.be
+        v = be.empty(2 * q.N)
+        for k in range(2):
+            be.axpby(1.0, _view(self.vec, k * self.N + int(self.roff[r % len(self.rows)]), (q.N,)), 0.0, _view(v, k * q.N, (q.N,)))
+        return LeftGaugedQP(q.left_gs, q.VLs, q.xshapes, self.momentum, v, 2)
+
+    def with_vec(self, vec):
+        return MultilineQP(self.rows, self.momentum, vec)
+
+
+def _statmech_heff(ctx: _StatmechContext, phi: MultilineQP, x: DTensor, out: DTensor):
+    """effective_excitation_hamiltonian(H::MPOMultiline, phi)  :258-293: row r + 1 of the result from row r of the input,
+    every site divided by its own en."""
+    be, R, n = ctx.be, ctx.R, ctx.n
+    for r in range(R):
+        Bs = [[phi.B(k, r, c, x) for k in range(2)] for c in range(n)]
+        lBs, rBs = ctx.qp_envs(r, Bs, phi.momentum)
+        q = phi.rows[(r + 1) % R]
+        for c in range(n):
+            for k in range(2):
+                T = ctx._local(r, c, Bs[c][k], lBs[(c - 1) % n][k], rBs[(c + 1) % n][k])
+                Dl, d, Dr = T.shape
+                be.gemm(q.VLs[c], T.reshape(Dl * d, Dr), transA=True, alpha=1.0 / ctx.lam[r][c], out=phi.X(k, r + 1, c, out))
+    return out
+
+
+def excitations_statmech(H, alg: QuasiparticleAnsatz, momenta, psi, envs=None, rpsi=None, renvs=None, num=1, rng=None,
+                         device=None):
+    """excitations(H::DenseMPO | MPOMultiline, QuasiparticleAnsatz(), momentum | momenta | [LeftGaugedQP per row], psi[, envs];
+    num)  (quasiparticleexcitation.jl:170-228): the `num` largest-magnitude (:LM) eigenvalues of the effective operator of
+    the row-to-row transfer matrix on the quasiparticle tangent space, normalised by the leading eigenvalue per site, so that
+    |E| = exp(-eps(p)) with eps the excitation's inverse correlation length at momentum p.
+
+    A DenseMPO with an InfiniteMPS of any unit cell is converted to one row (:202-216) and its states come back as
+    LeftGaugedQP; an MPOMultiline with an MPSMultiline gives MultilineQP states (one LeftGaugedQP per row, qp[r]).  A scalar
+    momentum returns (E[num] complex, states[num]); a list returns (E[len(momenta), num], states[len(momenta)][num]).
+
+    The operator is not Hermitian and an eigenvector can be complex at any momentum, p = 0 included, so a
+    statistical-mechanics quasiparticle always carries two real parts [Re | Im] and every kernel runs once per part: at
+    p = 0 and p = pi this costs a factor of two over what a real vector would need (the Hamiltonian method carries one part
+    there).  The eigensolver is the complex Arnoldi of krylov.eigsolve_lm_planar.
+
+    device: None = the route FUSED_BY_DEFAULT gives for the slice kind, True = insist on mpsk_qp_apply and the pair
+    transfers (mpsk_qp_half once per site per call), False = the composed route (mpsk_dAC_proj, the _ex transfers, axpby),
+    which is also what a backend without the new entries runs."""
+    from . import multiline, statmech
+    if rpsi is not None and rpsi is not psi:
+        raise NotImplementedError("excitations of a transfer matrix between two different ground states are not built: "
+                                  "\"there is a phase ambiguity in topologically nontrivial statmech excitations\" "
+                                  "(qpenv.jl:176-177)")
+    one_row = isinstance(H, statmech.DenseMPO) and not isinstance(psi, multiline.MPSMultiline)
+    if one_row:                                                              # :202-216
+        envs = statmech.environments(psi, H) if envs is None else envs
+        envs.leftenv(0, psi)
+        rows_env = [envs]
+        psi = multiline.MPSMultiline(psi)
+    else:
+        H = multiline.MPOMultiline(H) if isinstance(H, statmech.DenseMPO) else H
+        if not isinstance(H, multiline.MPOMultiline) or not isinstance(psi, multiline.MPSMultiline):
+            raise TypeError("excitations of a transfer matrix take (DenseMPO, InfiniteMPS) or (MPOMultiline, MPSMultiline)")
+        envs = multiline.environments(psi, H) if envs is None else envs
+        envs._fresh(psi)
+        rows_env = envs.sub
+    be = psi.be
+    rng = np.random.default_rng(0) if rng is None else rng
+    R = psi.shape[0]
+    ctx = _StatmechContext(psi, rows_env, alg, device)
+
+    def solve(phi0: MultilineQP):
+        def op(x, out):
+            return _statmech_heff(ctx, phi0, x, out)
+        vals, vecs, _, conv = krylov.eigsolve_lm_planar(be, op, phi0.vec, num=num, tol=alg.tol, krylovdim=alg.krylovdim,
+                                                        maxiter=alg.maxiter)
+        if conv < num:
+            import warnings
+            warnings.warn("excitation failed to converge")                  # :184-185
+        states = [phi0.with_vec(v) for v in vecs]
+        return vals, [s[0] for s in states] if one_row else states
+
+    def start(p):
+        rows = []
+        for r in range(R):
+            q = LeftGaugedQP.random(psi[r], p, rng)
+            rows.append(LeftGaugedQP(psi[r], q.VLs, q.xshapes, float(p), be.upload(rng.random(2 * q.N)), 2))
+        return MultilineQP(rows, p)
+
+    if isinstance(momenta, LeftGaugedQP):
+        momenta = [momenta]
+    if isinstance(momenta, (list, tuple)) and momenta and isinstance(momenta[0], LeftGaugedQP):
+        if len(momenta) != R:
+            raise ValueError(f"{len(momenta)} quasiparticle rows for a state of {R} rows")
+        for r, q in enumerate(momenta):
+            if not q.trivial:
+                raise NotImplementedError("\"there is a phase ambiguity in topologically nontrivial statmech excitations\" "
+                                          "(qpenv.jl:176-177): domain-wall excitations of a transfer matrix are not built")
+            if q.left_gs is not psi[r]:
+                raise ValueError(f"quasiparticle row {r} was built on another ground state")
+        return solve(MultilineQP(list(momenta), momenta[0].momentum))
+    if np.isscalar(momenta):
+        return solve(start(float(momenta)))
+    Ep, Bp = [], []
+    for p in momenta:
+        e, b = solve(start(float(p)))
         Ep.append(e)
         Bp.append(b)
     return np.array(Ep), Bp
