@@ -393,6 +393,23 @@ int mpsk_transfer_left_ex(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, i
                           const void* GLin, const void* A, const void* Ab, int flags, void* GLout);
 int mpsk_transfer_right_ex(mpsk_ctx* ctx, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,
                            const void* A, const void* Ab, const void* GRin, int flags, void* GRout);
+/* Pair-Gram route of the canonical transfers.  The levels that receive from the identity level alone are combinations of
+ * a few products of the site tensor with itself, GLout[v] = sum_{t,s} O[0,t,s,v] P_ts with P_ts = A[:,t,:]^T A[:,s,:] and
+ * P_st = P_ts^T (right: GRout[w] = sum O[w,t,s,W-1] Q_st, Q_st = A[:,s,:] A[:,t,:]^T).  Where a flop-and-launch model says
+ * it pays (Heisenberg S = 1/2: from D ~ 350), a canonical-route call computes the unordered pairs {t,s} that carry a
+ * coefficient in ONE batched launch (symmetric products P_tt: upper block triangle only), one elementwise kernel writes the
+ * interior levels (and the D-block term of the finished level) from them, and the finished level is a single GEMM of the
+ * fold application: Heisenberg 24 -> ~16 D^3.  Workspace d^2 D^2 + d Dl Dr + pairs n^2 doubles (n = Dr left, Dl right).
+ * Environment MPSK_TRANSFER_MODE, read per call: 0 dense route, 1 the level-by-level canonical route, 2 the pair-Gram
+ * route wherever the slice has pairs, unset: the model.
+ * mpsk_ctx_transfer_stats: canonical transfers of this ctx that took the pair-Gram route.
+ * mpsk_transfer_pair_model: host only (no ctx, no device) -- what mpsk_mposlice_create records for a Jordan-form slice
+ * given as the dense tensor O[Wl, d, d, Wr] (column-major, index (w,t,s,v)) and what the model chooses at (Dl, Dr); every
+ * output is an int[2] = {transfer_left, transfer_right} or NULL: pairs, the symmetric ones among them, output levels of the
+ * combination kernel, route (1 pair-Gram, 0 level by level). */
+int mpsk_ctx_transfer_stats(mpsk_ctx* ctx, long* n_pair);
+int mpsk_transfer_pair_model(int Wl, int Wr, int d, const double* O, int Dl, int Dr, int* pairs, int* diagonal, int* levels,
+                             int* route);
 /* ---- quasiparticle excitations of a transfer matrix: quasiparticleexcitation.jl:258-293 (the local term of the effective
  * operator) and qpenv.jl:238-251 (the updates of lB / rB).  MPSK_F64 only: a MPSK_C128 slice or ctx gets
  * MPSK_ERR_UNSUPPORTED.  Both slice kinds: sparse slices (slab mix) and dense slices on both sides of the crossover of

@@ -80,6 +80,9 @@ SIGNATURES = {
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
     "mpsk_transfer_right_ex": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "mpsk_ctx_transfer_stats": [C.c_void_p, C.POINTER(C.c_long)],
+    "mpsk_transfer_pair_model": [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "mpsk_regularize": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "mpsk_qrpos": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int],
     "mpsk_qrpos2": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,

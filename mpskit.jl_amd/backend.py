@@ -447,6 +447,12 @@ class Backend:
         check(self.lib.mpsk_ctx_complement_stats(self.ctx, C.byref(a), C.byref(b), C.byref(c)), "mpsk_ctx_complement_stats")
         return {"calls": a.value, "subspace": b.value, "full": c.value}
 
+    def transfer_stats(self):
+        """{"pair": canonical transfers of this ctx that took the pair-Gram route} (mpsk_ctx_transfer_stats)"""
+        a = C.c_long()
+        check(self.lib.mpsk_ctx_transfer_stats(self.ctx, C.byref(a)), "mpsk_ctx_transfer_stats")
+        return {"pair": a.value}
+
     def transfer_left(self, H, GLin: DTensor, A: DTensor, Ab: DTensor, out: DTensor = None, cplx=False, canonical=False):
         """mpsk_transfer_left; canonical=True promises that level 0 of GLin is the identity and that A (== Ab) is a left
         isometry (MPSK_TRANSFER_CANONICAL): a real Jordan-form slice then takes the 24 D^3 route of mpsk_transfer_left_ex."""

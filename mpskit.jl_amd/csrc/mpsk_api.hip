@@ -30,6 +30,65 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 // dense slices (mpsk_mposlice_create_dense) with min(Wl, Wr) d below this keep the slab-mix route (see dense_route)
 static constexpr int MPSK_DENSE_MIN_CHID = 8;
 
+// Pair-Gram form of the interior levels of a canonical transfer (Jordan-form slice, dense O[Wl, d, d, Wr]).  The levels
+// that receive from the identity level alone are combinations of a few D x D products of the site tensor with itself:
+//   left   GLout[v] = sum_{t,s} O[0,t,s,v] P_ts,      P_ts = A[:,t,:]^T A[:,s,:],   P_st = P_ts^T,   v = 1 .. Wr-2, and the
+//          D-block term of level Wr-1
+//   right  GRout[w] = sum_{t,s} O[w,t,s,Wr-1] Q_st,   Q_st = A[:,s,:] A[:,t,:]^T,   Q_ts = Q_st^T,   w = 1 .. Wl-2
+// Pair p = {i, j}, i <= j, stands for M_p = op(A_i) op(A_j) (left: P_ij, right: Q_ij); only pairs with a non-zero
+// coefficient on some level are listed, the diagonal ones (symmetric M_p) first.  coef[l][p] = (direct, transposed):
+//   left   level v = 1 + l:  (O[0,i,j,v], O[0,j,i,v])          right  level w = 1 + l:  (O[w,j,i,Wr-1], O[w,i,j,Wr-1])
+// with the transposed coefficient of a diagonal pair zero.  Host data only; d_coef is the slice's device copy.
+struct PairPlan {
+  int np = 0, ndiag = 0, nl = 0;
+  std::vector<int> i, j;
+  std::vector<double> coef;        // [nl][np][2]
+  double* d_coef = nullptr;
+};
+
+static void pair_plan_build(int Wl, int Wr, int d, const double* O, bool left, PairPlan* pp) {
+  auto at = [&](int w, int t, int s, int v) { return O[w + (size_t)Wl * (t + d * (s + (size_t)d * v))]; };
+  *pp = PairPlan();
+  if (Wl < 2 || Wr < 2) return;
+  int nl = left ? Wr - 2 : Wl - 2;
+  if (left)
+    for (int t = 0; t < d && nl == Wr - 2; ++t)
+      for (int s = 0; s < d; ++s) if (at(0, t, s, Wr - 1) != 0.0) { nl = Wr - 1; break; }
+  if (nl <= 0) return;
+  auto direct = [&](int l, int i, int j) { return left ? at(0, i, j, 1 + l) : at(1 + l, j, i, Wr - 1); };
+  for (int pass = 0; pass < 2; ++pass)          // diagonal pairs, then the others
+    for (int i = 0; i < d; ++i)
+      for (int j = i; j < d; ++j) {
+        if ((pass == 0) != (i == j)) continue;
+        bool used = false;
+        for (int l = 0; l < nl && !used; ++l) used = direct(l, i, j) != 0.0 || direct(l, j, i) != 0.0;
+        if (!used) continue;
+        pp->i.push_back(i); pp->j.push_back(j);
+        if (i == j) pp->ndiag++;
+      }
+  pp->np = (int)pp->i.size();
+  pp->nl = pp->np ? nl : 0;
+  pp->coef.assign((size_t)pp->nl * pp->np * 2, 0.0);
+  for (int l = 0; l < pp->nl; ++l)
+    for (int p = 0; p < pp->np; ++p) {
+      const int i = pp->i[p], j = pp->j[p];
+      pp->coef[((size_t)l * pp->np + p) * 2] = direct(l, i, j);
+      pp->coef[((size_t)l * pp->np + p) * 2 + 1] = i == j ? 0.0 : direct(l, j, i);
+    }
+}
+
+// Route choice of a canonical transfer, in seconds at the rate the batched transfer GEMMs reach (~50 TFLOP/s): the pair
+// products -- 2 K n^2 flops each, a symmetric one ~0.55 of that with its lower tiles skipped -- plus the one launch the
+// route adds (~6 us with its gap, the price mpsk_hac_create_ex uses) against `interior` levels of 2 d K n^2.  The
+// elementwise passes of the two routes (slab mix / combination) move about the same bytes and are left out.  With a
+// single interior level the batch of two levels would fall apart into two launches of n^2 / 64^2 tiles each for less than
+// 2 K n^2 saved: not taken.  K, n: contracted and result bond (left: Dl, Dr; right: Dr, Dl).
+static bool pair_route_pays(const PairPlan& pp, int interior, int d, int K, int n) {
+  if (pp.np == 0 || interior < 2) return false;
+  const double unit = 2.0 * K * (double)n * n / 50e12;
+  return (0.55 * pp.ndiag + (pp.np - pp.ndiag)) * unit + 6e-6 < (double)interior * d * unit;
+}
+
 struct mpsk_mposlice {
   mpsk_ctx* ctx;
   int Wl, Wr, d;
@@ -70,6 +129,10 @@ struct mpsk_mposlice {
   bool tl_dblock = false;
   mutable std::map<int64_t, int64_t*> jtabL;                          // key Dl
   mutable std::map<std::pair<int64_t, int64_t>, int64_t*> jtabR;      // key (Dl, Dr)
+  // pair-Gram route of the canonical transfers (PairPlan below): pl for transfer_left, pr for transfer_right; ptabL /
+  // ptabR: device offset tables [2][np] of the pair batch (first operand i Dl, second operand j Dl), key Dl
+  PairPlan pl, pr;
+  mutable std::map<int64_t, int64_t*> ptabL, ptabR;
   double O(int w, int t, int s, int v) const { return Ofull[w + (size_t)Wl * (t + d * (s + (size_t)d * v))]; }
   // dense slice (mpsk_mposlice_create_dense): stage 2 of dAC / the transfers is the fp64 GEMM
   //   T2[:, (t,v)] = T1[:, (s,w)] Od[(s,w), (t,v)]  on intermediates whose K index (s,w) has ONE stride;
@@ -145,6 +208,7 @@ struct mpsk_ctx {
   void* exws = nullptr;
   size_t exws_bytes = 0;
   long n_compl = 0, n_compl_sub = 0, n_compl_full = 0;
+  long n_transfer_pair = 0;     // canonical transfers that took the pair-Gram route (mpsk_ctx_transfer_stats)
 };
 
 // prepared effective Hamiltonian of one site (MPO_ddAC of derivatives.jl:11-15: built once, applied by every Krylov step)
@@ -498,6 +562,15 @@ static int mposlice_build(mpsk_ctx* c, int dtype, int odim, const int32_t* chi_l
           }
         HIPCHK(mix_plan_create(tl, d * (Wr - (s->tl_dblock ? 1 : 2)), d, &s->tl));
         HIPCHK(mix_plan_create(tr, d * (Wl - 2), d, &s->tr));
+        for (PairPlan* pp : {&s->pl, &s->pr}) {
+          pair_plan_build(Wl, Wr, d, s->Ofull.data(), pp == &s->pl, pp);
+          if (pp->np == 0) continue;
+          if (hipMalloc(&pp->d_coef, sizeof(double) * pp->coef.size()) != hipSuccess) {
+            mpsk_mposlice_destroy(s);
+            return fail(MPSK_ERR_NOMEM, "pair coefficient table hipMalloc failed");
+          }
+          HIPCHK(hipMemcpy(pp->d_coef, pp->coef.data(), sizeof(double) * pp->coef.size(), hipMemcpyHostToDevice));
+        }
       }
     }
   }
@@ -559,6 +632,10 @@ int mpsk_mposlice_destroy(mpsk_mposlice* s) {
   mix_plan_destroy(&s->tr);
   for (auto& kv : s->jtabL) (void)hipFree(kv.second);
   for (auto& kv : s->jtabR) (void)hipFree(kv.second);
+  for (auto& kv : s->ptabL) (void)hipFree(kv.second);
+  for (auto& kv : s->ptabR) (void)hipFree(kv.second);
+  if (s->pl.d_coef) (void)hipFree(s->pl.d_coef);
+  if (s->pr.d_coef) (void)hipFree(s->pr.d_coef);
   if (s->d_Od) (void)hipFree(s->d_Od);
   if (s->d_OdR) (void)hipFree(s->d_OdR);
   for (auto& kv : s->dtab) (void)hipFree(kv.second);
@@ -1779,6 +1856,51 @@ static bool transfer_canonical_ok(const mpsk_mposlice* H, int flags, const void*
   return !(ev && ev[0] == '0');
 }
 
+// Which canonical route: the pair-Gram form of the interior levels (PairPlan) or the level-by-level one.
+// MPSK_TRANSFER_MODE (read per call): 1 = level by level, 2 = pair-Gram wherever the slice has a pair plan (A/B runs and
+// tests at shapes the model would not send there), unset = pair_route_pays.
+static bool transfer_pair_route(const mpsk_mposlice* H, bool left, int Dl, int Dr) {
+  const PairPlan& pp = left ? H->pl : H->pr;
+  if (pp.np == 0) return false;
+  if (const char* ev = getenv("MPSK_TRANSFER_MODE")) {
+    if (ev[0] == '1') return false;
+    if (ev[0] == '2') return true;
+  }
+  return left ? pair_route_pays(pp, H->Wr - 2, H->d, Dl, Dr) : pair_route_pays(pp, H->Wl - 2, H->d, Dr, Dl);
+}
+
+// device offset tables [2][np] of the pair batch, cached on the slice per Dl: operand offsets i Dl and j Dl into A
+static int pair_tab(const mpsk_mposlice* H, bool left, int Dl, const int64_t** out) {
+  auto& cache = left ? H->ptabL : H->ptabR;
+  auto it = cache.find(Dl);
+  if (it != cache.end()) { *out = it->second; return MPSK_OK; }
+  const PairPlan& pp = left ? H->pl : H->pr;
+  std::vector<int64_t> h((size_t)2 * pp.np);
+  for (int p = 0; p < pp.np; ++p) { h[p] = (int64_t)pp.i[p] * Dl; h[(size_t)pp.np + p] = (int64_t)pp.j[p] * Dl; }
+  int64_t* d = nullptr;
+  if (int rc = upload_table(h, "pair offset table", &d)) return rc;
+  cache.emplace(Dl, d);
+  *out = d;
+  return MPSK_OK;
+}
+
+// M_p = op(A_i) op(A_j) for every pair of the plan, ONE launch: left P_ij = A_i^T A_j (TN, K = Dl, Dr x Dr), right
+// Q_ij = A_i A_j^T (NT, K = Dr, Dl x Dl), A_s = A[:, s, :] (leading dimension Dl d).  The symmetric products come first
+// in the batch and skip their lower tiles (GemmArgs::upper_nb); pair_combine reads them through the upper triangle.
+static int pair_products(mpsk_ctx* c, const mpsk_mposlice* H, bool left, int Dl, int Dr, const double* A, double* P) {
+  const PairPlan& pp = left ? H->pl : H->pr;
+  const int64_t* tab = nullptr;
+  if (int rc = pair_tab(H, left, Dl, &tab)) return rc;
+  const int n = left ? Dr : Dl, K = left ? Dl : Dr;
+  const int64_t ld = (int64_t)Dl * H->d;
+  GemmArgs g = mk(A, A, P, n, n, K, ld, ld, n, left ? 1 : 0, left ? 0 : 1);
+  g.batch = pp.np; g.tabA = tab; g.tabB = tab + pp.np; g.bsC = (int64_t)n * n;
+  g.tabs_even = Dl % 2 == 0;
+  if (pp.ndiag > 0) { g.upper_only = 1; g.upper_nb = pp.ndiag; }
+  HIPCHK(gemm_f64(g, c->stream));
+  return MPSK_OK;
+}
+
 // MPSK_HAC_CHECK=1 (debug, synchronises): the promises behind MPSK_TRANSFER_CANONICAL -- the identity level of the input
 // environment (n x n at G) and the isometry of A on the contracted side (Gram matrix through c->ws) -- hold to 1e-10
 static int transfer_canonical_check(mpsk_ctx* c, const char* who, const double* G, int n, const double* A, int d, int Dl,
@@ -1830,11 +1952,50 @@ static int jordan_tab(const mpsk_mposlice* H, bool left, int Dl, int Dr, const i
   return MPSK_OK;
 }
 
+// Pair-Gram route of transfer_left_canonical.  The interior levels and the D-block term of the finished level are
+// combinations of the pair products (pair_combine writes levels 1 .. W-1, or 1 .. W-2 for a slice without a D block); the
+// finished level then is a single TN GEMM A^T T of the fold application T = GLc A alone, with beta = 1 on top of the
+// D-block term the combination has written (combine first, accumulate second: the GEMM epilogue reads C anyway, the
+// elementwise kernel stays write-only).  No mix pass over A and no T2 slabs: the workspace is the fold, one slab for T
+// and np Dr^2 doubles of products.
+static int transfer_left_pairs(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dr, const double* GLin, const double* A,
+                               double* GLout) {
+  const int d = H->d, Wr = H->Wr, n2 = H->jl_nseg;
+  const PairPlan& pp = H->pl;
+  const size_t slab = (size_t)Dl * d * Dr, nD = (size_t)Dr * Dr;
+  const int64_t tL = (int64_t)Dl * d * Dl;
+  Ws ws;
+  const size_t o_glc = ws.take((size_t)d * tL, 32), o_t = ws.take(slab, 32), o_p = ws.take(nD * pp.np);
+  if (int rc = ws.ensure(c)) return rc;
+  const int64_t* tab = nullptr;
+  if (int rc = jordan_tab(H, true, Dl, Dr, &tab)) return rc;
+  double *GLc = Ws::at(c, o_glc), *T = Ws::at(c, o_t), *P = Ws::at(c, o_p);
+  if (int rc = pair_products(c, H, true, Dl, Dr, A, P)) return rc;
+  HIPCHK(identity_slab(GLout, Dr, c->stream));
+  HIPCHK(pair_combine(P, pp.np, pp.ndiag, Dr, pp.d_coef, pp.nl, GLout + nD, (int64_t)nD, c->stream));
+  // GLc[(s,t)] = sum_{w>0} O[w,t,s,W-1] GLin[w];  T[:,t,:] = sum_k GLc[(s_k,t)] A[:,s_k,:]     (batch over t)
+  SlabIndex il{1 << 30, 1, (int64_t)Dl * Dl, 0, 0, (int64_t)Dl}, ol{d, 1 << 30, (int64_t)Dl, tL, 0, (int64_t)d * Dl};
+  HIPCHK(mix_apply(H->jl, GLin, il, GLc, ol, Dl, Dl, c->stream));
+  GemmArgs g = mk(GLc, A, T, Dl, Dr, Dl, (int64_t)Dl * d, (int64_t)Dl * d, (int64_t)Dl * d);
+  g.batch = d; g.bsA = 0; g.bsB = 0; g.bsC = (int64_t)Dl;
+  g.nseg = n2; g.zsegA = tab; g.zsegB = tab + (size_t)d * n2;
+  g.tabs_even = Dl % 2 == 0;
+  g.tag = 1;
+  HIPCHK(gemm_f64(g, c->stream));
+  // GLout[W-1][q,b] (+)= sum_{(p,t)} A[(p,t),q] T[(p,t),b]
+  GemmArgs g3 = mk(A, T, GLout + nD * (Wr - 1), Dr, Dr, Dl * d, (int64_t)Dl * d, (int64_t)Dl * d, Dr, 1, 0);
+  g3.beta = pp.nl == Wr - 1 ? 1.0 : 0.0;
+  HIPCHK(gemm_f64(g3, c->stream));
+  c->n_transfer_pair++;
+  return MPSK_OK;
+}
+
 static int transfer_left_canonical(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dr, const double* GLin, const double* A,
                                    double* GLout) {
   const int d = H->d, Wr = H->Wr, n2 = H->jl_nseg;
   if (hac_check_on())
     if (int rc = transfer_canonical_check(c, "mpsk_transfer_left_ex", GLin, Dl, A, d, Dl, Dr, true)) return rc;
+  if (transfer_pair_route(H, true, Dl, Dr)) return transfer_left_pairs(c, H, Dl, Dr, GLin, A, GLout);
   const size_t slab = (size_t)Dl * d * Dr;                  // one level of T2
   const int64_t tL = (int64_t)Dl * d * Dl;                  // one t-group of GLc
   const size_t nL = (size_t)d * tL;
@@ -1868,12 +2029,48 @@ static int transfer_left_canonical(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, 
   return MPSK_OK;
 }
 
+// Pair-Gram route of transfer_right_canonical: the interior levels from the pair products Q_ij = A_i A_j^T, level 0 from
+// the right fold (which already holds the D block) as a single NT GEMM over the physical index, beta = 0.
+static int transfer_right_pairs(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dr, const double* A, const double* GRin,
+                                double* GRout) {
+  const int d = H->d, Wl = H->Wl, n1 = H->jr_nseg;
+  const PairPlan& pp = H->pr;
+  const size_t slab = (size_t)Dl * d * Dr, nD = (size_t)Dl * Dl;
+  const int64_t tR = (int64_t)Dr * d * Dr;
+  Ws ws;
+  const size_t o_grc = ws.take((size_t)d * tR, 32), o_x = ws.take(slab, 32), o_p = ws.take(nD * pp.np);
+  if (int rc = ws.ensure(c)) return rc;
+  const int64_t* tab = nullptr;
+  if (int rc = jordan_tab(H, false, Dl, Dr, &tab)) return rc;
+  double *GRc = Ws::at(c, o_grc), *X = Ws::at(c, o_x), *P = Ws::at(c, o_p);
+  if (int rc = pair_products(c, H, false, Dl, Dr, A, P)) return rc;
+  HIPCHK(identity_slab(GRout + nD * (Wl - 1), Dl, c->stream));
+  HIPCHK(pair_combine(P, pp.np, pp.ndiag, Dl, pp.d_coef, pp.nl, GRout + nD, (int64_t)nD, c->stream));
+  // GRc0[(s,t)] = sum_v O[0,t,s,v] GRin[v];  X[:,t,:] = sum_k A[:,s_k,:] GRc0[(s_k,t)]     (batch over t)
+  SlabIndex ir{1 << 30, 1, (int64_t)Dr * Dr, 0, 0, (int64_t)Dr}, orr{d, 1 << 30, (int64_t)Dr, tR, 0, (int64_t)d * Dr};
+  HIPCHK(mix_apply(H->jr, GRin, ir, GRc, orr, Dr, Dr, c->stream));
+  GemmArgs g = mk(A, GRc, X, Dl, Dr, Dr, (int64_t)Dl * d, (int64_t)Dr * d, (int64_t)Dl * d);
+  g.batch = d; g.bsA = 0; g.bsB = 0; g.bsC = (int64_t)Dl;
+  g.nseg = n1; g.zsegA = tab; g.zsegB = tab + (size_t)d * n1;
+  g.tabs_even = Dl % 2 == 0 && Dr % 2 == 0;
+  g.tag = 1;
+  HIPCHK(gemm_f64(g, c->stream));
+  // GRout[0][a,p] = sum_t sum_b X[a,t,b] A[p,t,b]
+  Segs sg;
+  phys_segs(sg, d, Dl, Dl);
+  GemmArgs g3 = mk(X, A, GRout, Dl, Dl, Dr, (int64_t)Dl * d, (int64_t)Dl * d, Dl, 0, 1);
+  HIPCHK(gemm_segments(g3, sg, c->stream));
+  c->n_transfer_pair++;
+  return MPSK_OK;
+}
+
 static int transfer_right_canonical(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int Dr, const double* A, const double* GRin,
                                     double* GRout) {
   const int d = H->d, Wl = H->Wl, Wr = H->Wr, n1 = H->jr_nseg;
   if (hac_check_on())
     if (int rc = transfer_canonical_check(c, "mpsk_transfer_right_ex", GRin + (size_t)(Wr - 1) * Dr * Dr, Dr, A, d, Dl, Dr, false))
       return rc;
+  if (transfer_pair_route(H, false, Dl, Dr)) return transfer_right_pairs(c, H, Dl, Dr, A, GRin, GRout);
   const size_t slab = (size_t)Dl * d * Dr;                  // one level of X
   const int64_t tR = (int64_t)Dr * d * Dr;                  // one t-group of GRc0
   const size_t nR = (size_t)d * tR;
@@ -1958,6 +2155,26 @@ int mpsk_transfer_right_ex(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, in
     return transfer_right_canonical(c, H, Dl, Dr, (const double*)A, (const double*)GRin, (double*)GRout);
   }
   return mpsk_transfer_right(c, H, W, d, Dl, Dr, Dlb, Drb, A, Ab, GRin, GRout);
+}
+
+int mpsk_ctx_transfer_stats(mpsk_ctx* c, long* n_pair) {
+  REQUIRE(c, "ctx is NULL");
+  if (n_pair) *n_pair = c->n_transfer_pair;
+  return MPSK_OK;
+}
+
+int mpsk_transfer_pair_model(int Wl, int Wr, int d, const double* O, int Dl, int Dr, int* pairs, int* diagonal, int* levels,
+                             int* route) {
+  REQUIRE(O && Wl >= 2 && Wr >= 2 && d > 0 && Dl > 0 && Dr > 0, "O is NULL or a dimension is out of range");
+  for (int side = 0; side < 2; ++side) {
+    PairPlan pp;
+    pair_plan_build(Wl, Wr, d, O, side == 0, &pp);
+    if (pairs) pairs[side] = pp.np;
+    if (diagonal) diagonal[side] = pp.ndiag;
+    if (levels) levels[side] = pp.nl;
+    if (route) route[side] = (side == 0 ? pair_route_pays(pp, Wr - 2, d, Dl, Dr) : pair_route_pays(pp, Wl - 2, d, Dr, Dl)) ? 1 : 0;
+  }
+  return MPSK_OK;
 }
 
 int mpsk_transfer_left(mpsk_ctx* c, const mpsk_mposlice* H, int W, int d, int Dl, int Dr, int Dlb, int Drb,

@@ -481,8 +481,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
   }
   int bm, bn;
   tile_coords(g, bid, tilesM, tilesN, &bm, &bn);
-  if (g.upper_only && bm > bn) return;      // symmetric result, lower tiles never read (uniform per workgroup)
   const int z = blockIdx.y;
+  if (g.upper_only && bm > bn && (g.upper_nb == 0 || z < g.upper_nb)) return;      // symmetric result, lower tiles never read (uniform per workgroup)
   const int m0 = bm * BM, n0 = bn * BN;
   const double* Ab = g.A + (g.tabA ? g.tabA[z] : (int64_t)z * g.bsA);
   const double* Bb = g.B + (g.tabB ? g.tabB[z] : (int64_t)z * g.bsB);
@@ -542,7 +542,7 @@ __device__ __forceinline__ void gemm_sk_body(const GemmArgs& g) {
     const int z = tz / ntiles, tile = tz - z * ntiles;
     int bm, bn;
     tile_coords(g, tile, tilesM, tilesN, &bm, &bn);
-    if (g.upper_only && bm > bn) { u += kt1 - kt0; continue; }     // uniform: the whole workgroup skips the share
+    if (g.upper_only && bm > bn && (g.upper_nb == 0 || z < g.upper_nb)) { u += kt1 - kt0; continue; }     // uniform: the whole workgroup skips the share
     const int m0 = bm * BM, n0 = bn * BN;
     const double* Ab = g.A + (g.tabA ? g.tabA[z] : (int64_t)z * g.bsA);
     const double* Bb = g.B + (g.tabB ? g.tabB[z] : (int64_t)z * g.bsB);
@@ -619,7 +619,7 @@ __global__ __launch_bounds__(256) void gemm_sk_fixup_kernel(GemmArgs g) {
   if (i * g.sk_units >= u1) return;            // tile not split
   int bm, bn;
   tile_coords(g, tile, tilesM, tilesN, &bm, &bn);
-  if (g.upper_only && bm > bn) return;
+  if (g.upper_only && bm > bn && (g.upper_nb == 0 || z < g.upper_nb)) return;
   const int m0 = bm * BM, n0 = bn * BN;
   double* Cb = g.C + (g.tabC ? g.tabC[z] : (int64_t)z * g.bsC);
   // 8 elements per thread and pass, every load of a pass issued before the first use: the earlier one-element loop

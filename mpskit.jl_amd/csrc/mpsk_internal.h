@@ -74,6 +74,8 @@ struct GemmArgs {
                              // only meet structural zeros are skipped -- B upper: k < n0 + BN ; A upper: k >= m0
   int upper_only;            // C is symmetric (Gram matrix) and only its upper triangle is consumed: tiles strictly below the
                              // block diagonal are skipped (M == N, square tiles)
+  int upper_nb;              // upper_only on a batch whose first upper_nb results are symmetric and the others are not: only
+                             // batches z < upper_nb skip their lower tiles (0: every batch)
   int cplx;
   int c_rs;
   int tag;                   // 1: matvec-stage launch (own kernel symbol + event profile)
@@ -143,6 +145,13 @@ hipError_t deinterleave(const double* z, int64_t n, double* re, double* im, hipS
 hipError_t copy_strided(const double* src, int64_t srs, int64_t scs, double* dst, int64_t drs, int64_t dcs, int64_t R,
                         int64_t C, hipStream_t s);
 hipError_t identity_slab(double* G, int n, hipStream_t s);   // G[n, n] (contiguous) = identity
+// out[l] = sum_p cd[l,p] P[p] + ct[l,p] P[p]^T for l < nl: P np contiguous n x n matrices, out[l] at out + l * out_stride
+// (n x n, contiguous), d_coef device [nl][np][2] = (cd, ct).  The first ndiag matrices are symmetric with only their upper
+// triangle valid (the Gram products P_tt of the pair-Gram transfers): element (r, c) with r > c is read at (c, r), and their
+// ct is not used.  Terms with both coefficients zero are skipped; the others are added in the order p = 0 .. np-1, direct
+// before transposed: bit-reproducible.
+hipError_t pair_combine(const double* P, int np, int ndiag, int n, const double* d_coef, int nl, double* out,
+                        int64_t out_stride, hipStream_t s);
 
 // ---- vector kernels ---------------------------------------------------------------------------
 // xs: HOST array of k device pointers; d_out / d_coefs: device [k]; d_partial: device scratch

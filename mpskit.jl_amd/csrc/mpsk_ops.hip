@@ -174,6 +174,93 @@ hipError_t identity_slab(double* G, int n, hipStream_t s) {
   return hipGetLastError();
 }
 
+// Interior levels of the pair-Gram transfers: out[l] = sum_p cd[l,p] P[p] + ct[l,p] P[p]^T.  One workgroup per 32 x 32
+// tile of one output level; a thread owns the row pair (2 rp, 2 rp + 1) in the columns cq and cq + 16.  Direct terms are
+// read as 16-byte vectors; a transposed term reads the mirror tile of P[p] the same (coalesced) way and turns it over in
+// the LDS.  Of a symmetric P[p] (p < ndiag) only the upper triangle is valid: element (r, c) takes (r, c) when r <= c and
+// (c, r) otherwise -- by selection, the lower triangle may hold anything.  Every branch around a barrier is uniform.
+constexpr int PC_T = 32, PC_LD = 34;
+template <bool VEC2>
+__global__ __launch_bounds__(256) void pair_combine_kernel(const double* __restrict__ P, int np, int ndiag, int n,
+                                                           const double* __restrict__ coef, double* __restrict__ out,
+                                                           int64_t out_stride) {
+  __shared__ __attribute__((aligned(16))) double sm[PC_T * PC_LD];
+  const int tid = threadIdx.x, rp = tid & 15, cq = tid >> 4;
+  const int R0 = blockIdx.x * PC_T, C0 = blockIdx.y * PC_T, l = blockIdx.z;
+  const int rl = 2 * rp, r = R0 + rl;
+  const int64_t nn = (int64_t)n * n;
+  double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};      // [column j][row i]
+  for (int p = 0; p < np; ++p) {
+    const double cd = coef[((size_t)l * np + p) * 2], ct = coef[((size_t)l * np + p) * 2 + 1];
+    const bool diag = p < ndiag;
+    if (cd == 0.0 && (diag || ct == 0.0)) continue;
+    const bool need_d = diag ? (R0 <= C0) : (cd != 0.0);
+    const bool need_t = diag ? (R0 >= C0) : (ct != 0.0);
+    const double* Pp = P + (size_t)p * nn;
+    double vd[2][2] = {{0.0, 0.0}, {0.0, 0.0}}, vt[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+    if (need_d) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int c = C0 + cq + 16 * j;
+        if (c < n && r < n) {
+          const double* q = Pp + r + (int64_t)c * n;
+          if (VEC2) { const d2 v = *reinterpret_cast<const d2*>(q); vd[j][0] = v.x; vd[j][1] = v.y; }
+          else { vd[j][0] = q[0]; if (r + 1 < n) vd[j][1] = q[1]; }
+        }
+      }
+    }
+    if (need_t) {
+      __syncthreads();                      // the previous term's readers are done with sm
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {         // mirror tile: rows C0 + ., columns R0 + .; sm[column][row]
+        const int mr = C0 + rl, mc = R0 + cq + 16 * j;
+        double a = 0.0, b = 0.0;
+        if (mc < n && mr < n) {
+          const double* q = Pp + mr + (int64_t)mc * n;
+          if (VEC2) { const d2 v = *reinterpret_cast<const d2*>(q); a = v.x; b = v.y; }
+          else { a = q[0]; if (mr + 1 < n) b = q[1]; }
+        }
+        *reinterpret_cast<d2*>(&sm[(cq + 16 * j) * PC_LD + rl]) = d2{a, b};
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {         // out (rl + i, cl) <- P (C0 + cl, R0 + rl + i) = sm[rl + i][cl]
+        const int cl = cq + 16 * j;
+        vt[j][0] = sm[rl * PC_LD + cl];
+        vt[j][1] = sm[(rl + 1) * PC_LD + cl];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        if (diag) acc[j][i] += cd * ((r + i <= C0 + cq + 16 * j) ? vd[j][i] : vt[j][i]);
+        else { acc[j][i] += cd * vd[j][i]; acc[j][i] += ct * vt[j][i]; }
+      }
+  }
+  double* o = out + (size_t)l * out_stride;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int c = C0 + cq + 16 * j;
+    if (c < n && r < n) {
+      double* q = o + r + (int64_t)c * n;
+      if (VEC2) *reinterpret_cast<d2*>(q) = d2{acc[j][0], acc[j][1]};
+      else { q[0] = acc[j][0]; if (r + 1 < n) q[1] = acc[j][1]; }
+    }
+  }
+}
+hipError_t pair_combine(const double* P, int np, int ndiag, int n, const double* d_coef, int nl, double* out,
+                        int64_t out_stride, hipStream_t s) {
+  if (n <= 0 || nl <= 0) return hipSuccess;
+  if (np <= 0 || !d_coef) return hipErrorInvalidValue;
+  const int tiles = (n + PC_T - 1) / PC_T;
+  const bool vec2 = n % 2 == 0 && out_stride % 2 == 0 && (uintptr_t)P % 16 == 0 && (uintptr_t)out % 16 == 0;
+  dim3 grid(tiles, tiles, nl);
+  if (vec2) hipLaunchKernelGGL(pair_combine_kernel<true>, grid, dim3(256), 0, s, P, np, ndiag, n, d_coef, out, out_stride);
+  else hipLaunchKernelGGL(pair_combine_kernel<false>, grid, dim3(256), 0, s, P, np, ndiag, n, d_coef, out, out_stride);
+  return hipGetLastError();
+}
+
 // -------------------------------------------------------------------------------------------
 // vector kernels
 // -------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Environment transfers alone: the dense three-stage route against the canonical route (mpsk_transfer_left_ex /
-mpsk_transfer_right_ex with MPSK_TRANSFER_CANONICAL) of the same library in one process, on canonical operands (identity
-level, isometric A).  Prints ms per call and TFLOP/s of the flops each route executes, and the largest difference.
+mpsk_transfer_right_ex with MPSK_TRANSFER_CANONICAL; level by level and pair-Gram) of the same library in one process, on
+canonical operands (identity level, isometric A).  Prints ms per call and TFLOP/s of the flops each route executes, and the largest difference.
 usage: transfer_only.py [D ...] [--model heis|heis1] [--reps N]   (default: D = 256 512 1024, Heisenberg S=1/2)
 Under rocprofv3 --kernel-trace --stats use --reps 5 --only dense|canonical."""
 import argparse
@@ -15,7 +15,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("D", nargs="*", type=int, default=[256, 512, 1024])
 ap.add_argument("--model", default="heis")
 ap.add_argument("--reps", type=int, default=50)
-ap.add_argument("--only", choices=["dense", "canonical"])
+ap.add_argument("--only", choices=["dense", "canonical", "pair"])
 args = ap.parse_args()
 
 be = mk.Backend(0)
@@ -56,18 +56,24 @@ for D in args.D:
     dense_fl = 4.0 * d * W * D ** 3
     for side, f, G, A, out in (("left", be.transfer_left, GL, AL, outl), ("right", be.transfer_right, GR, AR, outr)):
         res = {}
-        for route in ("dense", "canonical"):
+        for route in ("dense", "canonical", "pair"):
             if args.only and route != args.only:
                 continue
-            ms = timed(lambda: f(H, G, A, A, out=out, canonical=(route == "canonical")), args.reps)
+            # canonical: the level-by-level route (MPSK_TRANSFER_MODE=1); pair: the pair-Gram route forced (=2)
+            os.environ["MPSK_TRANSFER_MODE"] = {"dense": "0", "canonical": "1", "pair": "2"}[route]
+            ms = timed(lambda: f(H, G, A, A, out=out, canonical=(route != "dense")), args.reps)
             res[route] = (ms, out.buf[: out.size].clone())
         line = f"transfer_{side} {args.model} D={D} d={d} W={W}:"
         for route, (ms, _) in res.items():
             # canonical: fold application 2 d n D^3 (n = d slabs per t for these models) + stage 3 on W-1 levels
             fl = dense_fl if route == "dense" else 2.0 * d * d * D ** 3 + 2.0 * d * (W - 1) * D ** 3
+            if route == "pair":         # fold application + finished level + the pair products at their nominal 2 D^3 each
+                fl = 2.0 * d * d * D ** 3 + 2.0 * d * D ** 3 + 2.0 * (3 if d == 2 else 4) * D ** 3
             line += f"  {route} {ms:.4f} ms ({fl / ms / 1e9:.1f} TF/s of {fl / D ** 3:.0f} D^3)"
-        if len(res) == 2:
-            a, b = res["dense"][1], res["canonical"][1]
-            line += f"  speed-up {res['dense'][0] / res['canonical'][0]:.3f}x  max|diff|/max = {float((a - b).abs().max() / b.abs().max()):.2e}"
+        if "dense" in res:
+            for route in ("canonical", "pair"):
+                if route in res:
+                    a, b = res["dense"][1], res[route][1]
+                    line += f"  {route}: {res['dense'][0] / res[route][0]:.3f}x of dense, max|diff|/max = {float((a - b).abs().max() / b.abs().max()):.2e}"
         print(line, flush=True)
 be.close()
