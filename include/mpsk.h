@@ -448,6 +448,21 @@ int mpsk_transfer_left_pair(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dl1, int 
                             const void* A1, const void* V2, const void* A2, const void* Ab, void* out);
 int mpsk_transfer_right_pair(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dl, int Dr1, int Dr2, int Dlb, int Drb, const void* A1,
                              const void* V1, const void* A2, const void* V2, const void* Ab, void* out);
+/* ---- quasiparticle excitations of a Hamiltonian: one site and one real part of effective_excitation_hamiltonian in the left
+ * gauge (quasiparticleexcitation.jl:254-328, quasiparticle_state.jl:95-104).  MPSK_F64 only (MPSK_ERR_UNSUPPORTED otherwise).
+ * mpsk_qp_heff_site:   Xout[n,q] = sum_{p,t} VL[(p,t),n] y[p,t,q] - E X[n,q],
+ *                      y = mpsk_qp_apply(GL, GR, B = VL X, lB, AR, half, rB)  with Dlo = Dl and Dro = Dr.
+ *   VL: [Dl d, Dl d - DrL], orthonormal columns (the complement of AL [Dl, d, DrL]); X, Xout: [Dl d - DrL, Dr]; GL: Wl slabs
+ *   [Dl, Dl]; GR: Wr slabs [Dr, Dr]; lB: Wl slabs [Dl, Dl2]; AR: [Dl2, d, Dr]; half: mpsk_qp_half(H, Dl, Dl, Dr2, GL, AL);
+ *   rB: Wr slabs [Dr2, Dr].  The pairs (lB, AR) and (half, rB) may each be NULL (both members).  -E X stands for -E B pulled
+ *   back (VL^T B = X), so B is never scaled: B = VL X is one GEMM into the workspace, the three terms run through the stages
+ *   of mpsk_qp_apply into the workspace, and the pull-back is one GEMM C = A^T Y + gamma Z whose store path reads X and
+ *   writes Xout -- no pass over the result, no copy of X.  Xout must not alias X; X and half are only read.  An empty
+ *   complement (Dl d == DrL) returns MPSK_OK and writes nothing.  Fixed summation order: bit-reproducible.
+ *   flops: those of mpsk_qp_apply + 4 (Dl d)(Dl d - DrL) Dr.  Workspace: Dl d Dr (Wl + Wr + 2) doubles. */
+int mpsk_qp_heff_site(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dl, int DrL, int Dr, int Dl2, int Dr2, const void* GL,
+                      const void* GR, const void* VL, const void* X, double E, const void* lB, const void* AR, const void* half,
+                      const void* rB, void* Xout);
 /* regularize!(v, lvec, rvec)   src/transfermatrix/transfermatrix.jl:70-76
  *   v[w] -= <lvec^T, v[w]> * rvec  for each of the W slabs [D1, D2]; lvec: [D2, D1]; rvec: [D1, D2] */
 int mpsk_regularize(mpsk_ctx* ctx, int W, int D1, int D2, void* v, const void* lvec, const void* rvec);

@@ -27,3 +27,4 @@ from .measure import correlator, decompose_localmpo  # noqa: F401,E402   (local 
 from . import window  # noqa: F401,E402
 from .window import WindowMPS, WindowEnv, transition  # noqa: F401,E402   (window.dot: overlaps of two windows)
 from .propagator import propagator, DynamicalDMRG, NaiveInvert, Jeckelmann, GMRES, LinearCombination  # noqa: F401,E402
+from .susceptibility import fidelity_susceptibility, effective_excitation_hamiltonian, qp_dot  # noqa: F401,E402

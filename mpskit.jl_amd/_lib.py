@@ -158,7 +158,11 @@ SIGNATURES = {
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mpsk_transfer_right_pair": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mpsk_qp_heff_site": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                          C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
+# entries a library built before them may lack: load() leaves them unbound and Backend.has_* answers False
+OPTIONAL_SYMBOLS = ["mpsk_qp_heff_site"]
 # symbols without the (ctx, ...) -> int shape
 EXTRA_SYMBOLS = ["mpsk_version", "mpsk_last_error"]
 
@@ -182,6 +186,8 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in SIGNATURES.items():
+        if name in OPTIONAL_SYMBOLS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -396,6 +396,42 @@ class Backend:
         self._qp_count("transfer_right_pair")
         return y
 
+    # ---- quasiparticle excitations of a Hamiltonian (quasiparticle.py, susceptibility.py)
+    @property
+    def has_qp_heff(self):
+        """True when the loaded library exports mpsk_qp_heff_site; the host code takes the composed route otherwise."""
+        return hasattr(self.lib, "mpsk_qp_heff_site")
+
+    def qp_heff_site(self, H, GL: DTensor, GR: DTensor, VL: DTensor, X: DTensor, E, lB: DTensor = None, AR: DTensor = None,
+                     half: DTensor = None, rB: DTensor = None, out: DTensor = None):
+        """mpsk_qp_heff_site: VL^T qp_apply(GL, GR, VL X, lB, AR, half, rB) - E X for one site and one real part, with GL
+        (Wl, Dl, Dl), GR (Wr, Dr, Dr), VL [Dl d, n], X [n, Dr]; lB (Wl, Dl, Dl2), AR [Dl2, d, Dr], half from
+        qp_half(H, GL, AL), rB (Wr, Dr2, Dr).  Either pair may be None.  out must not alias X; an empty complement (n = 0)
+        returns out untouched."""
+        if not self.has_qp_heff:
+            raise MpskError("this libmpsk has no mpsk_qp_heff_site: rebuild it")
+        Wl, Dl, Dl_ = GL.shape
+        Wr, Dr, Dr_ = GR.shape
+        rows, n = VL.shape
+        d = H.d
+        assert Dl_ == Dl and Dr_ == Dr and rows == Dl * d and X.shape == (n, Dr) and Wl == H.Wl and Wr == H.Wr, \
+            (GL.shape, GR.shape, VL.shape, X.shape)
+        assert (lB is None) == (AR is None) and (half is None) == (rB is None)
+        Dl2 = Dr2 = 0
+        if lB is not None:
+            Dl2 = lB.shape[2]
+            assert lB.shape == (Wl, Dl, Dl2) and AR.shape == (Dl2, d, Dr), (lB.shape, AR.shape)
+        if rB is not None:
+            Dr2 = rB.shape[1]
+            assert rB.shape == (Wr, Dr2, Dr) and half.size == Wr * d * Dl * Dr2, (rB.shape, half.shape)
+        y = self.empty(n, Dr) if out is None else out
+        assert y.shape == (n, Dr) and (n == 0 or y.ptr != X.ptr), "out must be [n, Dr] and must not alias X"
+        nul = lambda t: None if t is None else t.ptr
+        check(self.lib.mpsk_qp_heff_site(self.ctx, H.handle, Dl, rows - n, Dr, Dl2, Dr2, GL.ptr, GR.ptr, VL.ptr, X.ptr, float(E),
+                                         nul(lB), nul(AR), nul(half), nul(rB), y.ptr), "mpsk_qp_heff_site")
+        self._qp_count("qp_heff_site")
+        return y
+
     def dC_proj(self, GL: DTensor, GR: DTensor, c: DTensor, out: DTensor = None):
         """mpsk_dC_proj (c_proj): the zero-site map with rectangular environments, GL (W, Dlo, Dl) and GR (W, Dr, Dro); c is
         [Dl, Dr], the result [Dlo, Dro].  Real fp64 only."""

@@ -980,11 +980,13 @@ static int transfer_right_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Wl, int 
 // tensor): the blocks become K-segments of the stage-1 GEMM, nothing is re-interleaved (mpsk_dAC_blocked).
 // GR: Wr slabs [Dr, Dro], y: [Dlo, d, Dro]; the square matvec is Dro = Dr.
 static int dAC_impl(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR,
-                    const void* x, int nblk, void* y, double alpha = 1.0, double beta = 0.0, const QpExtra* q = nullptr) {
+                    const void* x, int nblk, void* y, double alpha = 1.0, double beta = 0.0, const QpExtra* q = nullptr,
+                    size_t ws_base = 0) {
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t slab = (size_t)Dlo * d * Dr;
   Ws ws;
+  ws.n = ws_base;                 // the doubles in front belong to the caller (mpsk_qp_heff_site: B and the projected result)
   const size_t o_t1 = ws.take(slab * Wl), o_t2 = ws.take(slab * Wr);
   if (int rc = ws.ensure(c)) return rc;
   double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
@@ -1073,11 +1075,13 @@ static int dense_stage2(mpsk_ctx* c, const mpsk_mposlice* H, int64_t rows, const
 }
 
 static int dAC_dense(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, int Dro, const double* GL, const double* GR,
-                     const double* x, double* y, double alpha = 1.0, double beta = 0.0, const QpExtra* q = nullptr) {
+                     const double* x, double* y, double alpha = 1.0, double beta = 0.0, const QpExtra* q = nullptr,
+                     size_t ws_base = 0) {
   HIPCHK(hipSetDevice(c->device));
   const int d = H->d, Wl = H->Wl, Wr = H->Wr;
   const size_t slab = (size_t)Dlo * Dr;               // one (s,w) / (t,v) column of the intermediates
   Ws ws;
+  ws.n = ws_base;
   const size_t o_t1 = ws.take(slab * d * Wl), o_t2 = ws.take(slab * d * Wr);
   if (int rc = ws.ensure(c)) return rc;
   double *T1 = Ws::at(c, o_t1), *T2 = Ws::at(c, o_t2);
@@ -4036,6 +4040,47 @@ int mpsk_qp_apply(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dl2,
   if (dense_route(H))
     return dAC_dense(c, H, Dlo, Dl, Dr, Dro, (const double*)GL, (const double*)GR, (const double*)B, (double*)y, 1.0, 0.0, qp);
   return dAC_impl(c, H, Dlo, Dl, Dr, Dro, GL, GR, B, 1, y, 1.0, 0.0, qp);
+}
+
+// One site and one real part of the Hamiltonian quasiparticle operator in the left gauge: B = VL X into the workspace, the
+// three terms through the stages of mpsk_qp_apply into the workspace, and the pull-back VL^T (.) - E X as one GEMM whose
+// store path adds gamma Z (GemmArgs::Z), so that -E X costs neither a pass over the result nor a copy of X.
+int mpsk_qp_heff_site(mpsk_ctx* c, const mpsk_mposlice* H, int Dl, int DrL, int Dr, int Dl2, int Dr2, const void* GL,
+                      const void* GR, const void* VL, const void* X, double E, const void* lB, const void* AR, const void* half,
+                      const void* rB, void* Xout) {
+  REQUIRE(c && H && GL && GR && VL && X && Xout, "NULL argument");
+  REQUIRE((lB == nullptr) == (AR == nullptr), "lB and AR are given together or not at all");
+  REQUIRE((half == nullptr) == (rB == nullptr), "half and rB are given together or not at all");
+  REQUIRE(Dl > 0 && Dr > 0 && DrL > 0, "dimensions must be positive");
+  REQUIRE((!lB || Dl2 > 0) && (!half || Dr2 > 0), "dimensions must be positive");
+  REQUIRE(X != Xout, "Xout must not alias X");
+  if (int rc = qp_f64_only(c, H, "mpsk_qp_heff_site")) return rc;
+  const int d = H->d;
+  REQUIRE((int64_t)Dl * d >= DrL, "the complement of AL has Dl d - DrL columns: DrL must not exceed Dl d");
+  const int64_t rows = (int64_t)Dl * d;
+  const int n = (int)(rows - DrL);
+  if (n == 0) return MPSK_OK;                       // empty complement: nothing to write
+  HIPCHK(hipSetDevice(c->device));
+  // workspace: B | Y | the intermediates of the three terms (what mpsk_qp_apply takes), reserved in one piece so that the
+  // inner ensure() never moves B and Y
+  const size_t site = (size_t)rows * Dr;
+  Ws ws;
+  const size_t o_b = ws.take(site, 2), o_y = ws.take(site, 2);
+  const size_t base = ws.n;
+  ws.take(site * (size_t)(H->Wl + H->Wr));
+  if (int rc = ws.ensure(c)) return rc;
+  double *B = Ws::at(c, o_b), *Y = Ws::at(c, o_y);
+  GemmArgs gb = mk((const double*)VL, (const double*)X, B, (int)rows, Dr, n, rows, n, rows);          // B = VL X
+  HIPCHK(gemm_f64(gb, c->stream));
+  const QpExtra q{(const double*)lB, (const double*)AR, Dl2, (const double*)half, (const double*)rB, Dr2};
+  const QpExtra* qp = (lB || half) ? &q : nullptr;
+  if (int rc = dense_route(H) ? dAC_dense(c, H, Dl, Dl, Dr, Dr, (const double*)GL, (const double*)GR, B, Y, 1.0, 0.0, qp, base)
+                              : dAC_impl(c, H, Dl, Dl, Dr, Dr, GL, GR, B, 1, Y, 1.0, 0.0, qp, base))
+    return rc;
+  GemmArgs gp = mk((const double*)VL, Y, (double*)Xout, n, Dr, (int)rows, rows, rows, n, 1, 0);       // Xout = VL^T Y - E X
+  gp.Z = (const double*)X; gp.ldz = n; gp.gamma = -E;
+  HIPCHK(gemm_f64(gp, c->stream));
+  return MPSK_OK;
 }
 
 int mpsk_transfer_left_pair(mpsk_ctx* c, const mpsk_mposlice* H, int Dl1, int Dl2, int Dr, int Dlb, int Drb, const void* V1,

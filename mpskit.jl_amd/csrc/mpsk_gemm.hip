@@ -423,7 +423,8 @@ __device__ __forceinline__ void tile_coords(const GemmArgs& g, int t, int tilesM
 }
 
 // epilogue: lane holds C[m = .. + fr][n = .. + fq + 4*reg]
-template <int BM, int BN, bool ALIGNED, bool CJ = false>
+// ZADD: C = alpha acc + gamma Z with Z [M, N] (ldz) another matrix than C, which is only written (GemmArgs::Z)
+template <int BM, int BN, bool ALIGNED, bool CJ = false, bool ZADD = false>
 __device__ __forceinline__ void gemm_store_c(const GemmArgs& g, double* __restrict__ Cb, int z, int m0, int n0,
                                              const d4 (&acc)[BM / 32][BN / 32]) {
   constexpr int WTM = BM / 2, WTN = BN / 2, TM = WTM / 16, TN = WTN / 16;
@@ -444,7 +445,8 @@ __device__ __forceinline__ void gemm_store_c(const GemmArgs& g, double* __restri
                           ? g.C + g.tabC2[z] + mo + (int64_t)(n - g.splitN) * g.ldc
                           : Cb + mo + (int64_t)n * g.ldc;
           double v = alpha * acc[i][j][rg];
-          if (beta != 0.0) v += beta * (*p);
+          if constexpr (ZADD) v += g.gamma * g.Z[(int64_t)m + (int64_t)n * g.ldz];
+          else if (beta != 0.0) v += beta * (*p);
           *p = v;
         }
       }
@@ -467,7 +469,7 @@ __device__ __forceinline__ void gemm_store_ws(double alpha, double* __restrict__
         slot[(wm * WTM + i * 16 + fr) + (wn * WTN + j * 16 + fq + 4 * rg) * BM] = alpha * acc[i][j][rg];
 }
 
-template <int BM, int BN, bool TA, bool TB, bool ALIGNED, bool ZS = false, bool CJ = false>
+template <int BM, int BN, bool TA, bool TB, bool ALIGNED, bool ZS = false, bool CJ = false, bool ZADD = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   // XCD-aware tile mapping: blocks b, b+8, ... share an XCD (L2); give each XCD a contiguous
@@ -497,7 +499,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
   if (g.b_upper) { const int lim = (n0 + BN + BK - 1) / BK; if (lim < kthi) kthi = lim; }
   if (g.a_upper) ktlo = m0 / BK;
   if (ktlo < kthi) gemm_acc_dispatch<BM, BN, TA, TB, ALIGNED, ZS, CJ>(g, Ab, Bb, z, m0, n0, ktlo, kthi, acc, smem);
-  gemm_store_c<BM, BN, ALIGNED, CJ>(g, Cb, z, m0, n0, acc);
+  gemm_store_c<BM, BN, ALIGNED, CJ, ZADD>(g, Cb, z, m0, n0, acc);
 }
 
 // ---- stream-K: equal shares of the flattened (tile, k-tile) work list ---------------------------
@@ -506,7 +508,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
 // middle of a tile writes its partial tile to workspace slot i, and gemm_sk_fixup_kernel adds the
 // slots to C in a fixed order (deterministic, no atomics).  This removes the wave-quantisation loss
 // of big tiles (640 tiles of 128x128 on 512 resident workgroups at the north-star point).
-template <int BM, int BN, bool TA, bool TB, bool ALIGNED, bool ZS = false>
+template <int BM, int BN, bool TA, bool TB, bool ALIGNED, bool ZS = false, bool ZADD = false>
 __device__ __forceinline__ void gemm_sk_body(const GemmArgs& g) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int WTM = BM / 2, WTN = BN / 2, TM = WTM / 16, TN = WTN / 16;
@@ -578,7 +580,8 @@ __device__ __forceinline__ void gemm_sk_body(const GemmArgs& g) {
             double* p = base + m + (int64_t)n * ld;
             if (split && n0 + n >= g.splitN) p = g.C + g.tabC2[z] + (m0 + m) + (int64_t)(n0 + n - g.splitN) * g.ldc;
             double v = alpha * acc[i][j][rg];
-            if (beta != 0.0) v += beta * (*p);
+            if constexpr (ZADD) { if (toC) v += g.gamma * g.Z[(int64_t)(m0 + m) + (int64_t)(n0 + n) * g.ldz]; }
+            else if (beta != 0.0) v += beta * (*p);
             *p = v;
           }
         }
@@ -672,6 +675,17 @@ __global__ __launch_bounds__(NTHREADS, min_waves(BM, BN)) void dac_gemm_f64_kern
 template <int BM, int BN, bool ALIGNED>
 __global__ __launch_bounds__(NTHREADS, min_waves(BM, BN)) void dac_gemm_zs_f64_kernel(GemmArgs g) {
   gemm_body<BM, BN, false, false, ALIGNED, true>(g);
+}
+
+// C = alpha A^T B + gamma Z (GemmArgs::Z, the ZADD store path): the pull-back of mpsk_qp_heff_site.  The split-K form adds
+// Z in the share that writes C; the fixup then adds the partial tiles to C as for every other split launch.
+template <int BM, int BN, bool ALIGNED>
+__global__ __launch_bounds__(NTHREADS, min_waves(BM, BN)) void gemm_tn_zadd_f64_kernel(GemmArgs g) {
+  gemm_body<BM, BN, true, false, ALIGNED, false, false, true>(g);
+}
+template <int BM, int BN, bool ALIGNED>
+__global__ __launch_bounds__(NTHREADS, min_waves(BM, BN)) void gemm_tn_zadd_sk_f64_kernel(GemmArgs g) {
+  gemm_sk_body<BM, BN, true, false, ALIGNED, false, true>(g);
 }
 
 // complex128 family (A / C rows interleaved re-im, B planar; GemmArgs::segJ / c_rs): same body with the J-aware loader
@@ -774,14 +788,21 @@ static hipError_t launch_cfg(const GemmArgs& g, hipStream_t s) {
     static std::atomic<uint64_t> c0{0};
     return launch_one(cgemm_f64_kernel<BM, BN, TA, TB, ALIGNED>, c0, grid, smem, g, s, false, &r);
   }
+  // C = alpha A^T B + gamma Z (GemmArgs::Z): kernels of its own, instantiated for A^T B only (gemm_f64 checked the rest);
+  // they take the launch geometry, and the split launches the fixup, of the blocks below
+  constexpr bool ZADD_OK = TA && !TB;
+  if (g.Z && !ZADD_OK) return hipErrorInvalidValue;
   if constexpr ((BM == 128 && BN == 128) || (BM == 64 && BN == 64)) {
     if (g.sk_units > 0) {   // stream-K launch: equal k-tile shares + fixed-order fixup of split tiles
       const int KT = ((g.K + BK - 1) / BK) * g.nseg;
       const int64_t U = (int64_t)tilesM * tilesN * g.batch * KT;
       const dim3 sgrid((unsigned)((U + g.sk_units - 1) / g.sk_units));
       r.sk = 1;
-      static std::atomic<uint64_t> a0{0}, a1{0}, a2{0};
-      if constexpr (!TA && !TB) {
+      static std::atomic<uint64_t> a0{0}, a1{0}, a2{0}, a3{0};
+      if constexpr (ZADD_OK) {
+        if (g.Z) e = launch_one(gemm_tn_zadd_sk_f64_kernel<BM, BN, ALIGNED>, a3, sgrid, smem, g, s, false, &r);
+        else e = launch_one(gemm_sk_f64_kernel<BM, BN, TA, TB, ALIGNED>, a0, sgrid, smem, g, s, false, &r);
+      } else if constexpr (!TA && !TB) {
         if (tagged && zs) e = launch_one(dac_gemm_sk_zs_f64_kernel<BM, BN, ALIGNED>, a2, sgrid, smem, g, s, prof, &r);
         else if (tagged) e = launch_one(dac_gemm_sk_f64_kernel<BM, BN, ALIGNED>, a1, sgrid, smem, g, s, prof, &r);
         else e = launch_one(gemm_sk_f64_kernel<BM, BN, TA, TB, ALIGNED>, a0, sgrid, smem, g, s, false, &r);
@@ -795,8 +816,11 @@ static hipError_t launch_cfg(const GemmArgs& g, hipStream_t s) {
       return hipGetLastError();
     }
   }
-  static std::atomic<uint64_t> b0{0}, b1{0}, b2{0};
-  if constexpr (!TA && !TB) {
+  static std::atomic<uint64_t> b0{0}, b1{0}, b2{0}, b3{0};
+  if constexpr (ZADD_OK) {
+    if (g.Z) e = launch_one(gemm_tn_zadd_f64_kernel<BM, BN, ALIGNED>, b3, grid, smem, g, s, false, &r);
+    else e = launch_one(gemm_f64_kernel<BM, BN, TA, TB, ALIGNED>, b0, grid, smem, g, s, false, &r);
+  } else if constexpr (!TA && !TB) {
     if (tagged && zs) e = launch_one(dac_gemm_zs_f64_kernel<BM, BN, ALIGNED>, b2, grid, smem, g, s, prof, &r);
     else if (tagged) e = launch_one(dac_gemm_f64_kernel<BM, BN, ALIGNED>, b1, grid, smem, g, s, prof, &r);
     else e = launch_one(gemm_f64_kernel<BM, BN, TA, TB, ALIGNED>, b0, grid, smem, g, s, false, &r);
@@ -894,6 +918,8 @@ hipError_t gemm_f64(const GemmArgs& g_in, hipStream_t s) {
   if (g.K <= 0 || g.nseg <= 0) {  // pure scaling C = beta*C is not needed by any caller
     return hipErrorInvalidValue;
   }
+  if (g.Z && (!g.transA || g.transB || g.cplx || g.tabC2 || g.batch != 1 || g.beta != 0.0 || g.Z == g.C || g.zsegA))
+    return hipErrorInvalidValue;            // the ZADD store path: one real A^T B product, Z another matrix than C
   if (!g.A2 && !g.B2) { g.A2 = g.A; g.B2 = g.B; g.nseg1 = g.nseg; }
   else if (!g.A2 || !g.B2 || !g.zsegA || !g.zsegB || g.nseg1 < 0 || g.nseg1 > g.nseg) return hipErrorInvalidValue;
   int bm = 128, bn = 128;

@@ -80,6 +80,11 @@ struct GemmArgs {
   int c_rs;
   int tag;                   // 1: matvec-stage launch (own kernel symbol + event profile)
   int tabs_even;             // caller guarantees every tabA/tabB entry is even (16-B aligned operands)
+  // optional second epilogue: C = alpha A^T B + gamma Z with Z [M, N] (column stride ldz) another matrix than C, which is
+  // then only written (beta must be 0).  transA, !transB, batch 1, real operands; null: the alpha / beta epilogue.
+  const double* Z;
+  int64_t ldz;
+  double gamma;
 };
 
 hipError_t gemm_f64(const GemmArgs& g, hipStream_t s);

@@ -120,6 +120,8 @@ def excitations(H, alg, *args, **kw):
       QuasiparticleAnsatz:  excitations(H, alg, momentum | momenta, psi::InfiniteMPS[, envs]; num)   quasiparticleexcitation.jl:84-125
                             excitations(H, alg, psi::FiniteMPS[, envs]; num)                    :163-169
                             excitations(H, alg, phi0::LeftGaugedQP[, envs]; num)                :39-53,127-143
+                            (all three: device=True takes the fused route, mpsk_qp_heff_site and the pair transfers;
+                             the default is the composed route)
                             excitations(H::DenseMPO | MPOMultiline, alg, momentum | momenta | [LeftGaugedQP per row],
                                         psi::InfiniteMPS | MPSMultiline[, envs]; num, device)   :170-228"""
     from .quasiparticle import QuasiparticleAnsatz, LeftGaugedQP, excitations_qp, excitations_momenta

@@ -341,9 +341,10 @@ def exponentiate_general(be: Backend, gen, x0: DTensor, tol=1e-12, krylovdim=30,
 
 
 def gmres(be: Backend, matvec, b: DTensor, x0: DTensor, tol=1e-12, krylovdim=30, maxiter=100,
-          ws: KrylovWorkspace | None = None):
+          ws: KrylovWorkspace | None = None, info: dict | None = None):
     """Restarted GMRES for matvec(x) = b on device vectors (KrylovKit.linsolve stand-in,
-    mpohaminfenv.jl:95,113,146,164).  Returns x (new DTensor)."""
+    mpohaminfenv.jl:95,113,146,164).  Returns x (new DTensor).  info: a dict that receives the convergence history's
+    {"converged", "normres"} (the residual norm the solver stopped on)."""
     ws = KrylovWorkspace(be) if ws is None else ws
     shape = b.shape
     vecs = ws.get(shape, krylovdim + 3)
@@ -351,6 +352,8 @@ def gmres(be: Backend, matvec, b: DTensor, x0: DTensor, tol=1e-12, krylovdim=30,
     x = be.copy(x0)
     bnorm = be.norm(b)
     if bnorm == 0:
+        if info is not None:
+            info.update(converged=True, normres=0.0)
         return be.zeros(*shape)
     res = np.inf
     for _ in range(maxiter):
@@ -359,6 +362,7 @@ def gmres(be: Backend, matvec, b: DTensor, x0: DTensor, tol=1e-12, krylovdim=30,
         be.axpby(-1.0, tmp, 1.0, r)
         beta = be.norm(r)
         if beta <= tol:
+            res = beta
             break
         be.axpby(1.0 / beta, r, 0.0, V[0])
         Hm = np.zeros((krylovdim + 1, krylovdim))
@@ -398,6 +402,8 @@ def gmres(be: Backend, matvec, b: DTensor, x0: DTensor, tol=1e-12, krylovdim=30,
         be.axpby(1.0, tmp, 1.0, x)
         if res <= tol:
             break
+    if info is not None:
+        info.update(converged=bool(res <= tol), normres=float(res))
     return x
 
 

@@ -141,12 +141,27 @@ def _phase(be, z, ang):
     return [be.lincomb([re, im], [c, -s]), be.lincomb([re, im], [s, c])]
 
 
-class _QPContext:
-    """Everything that does not depend on X: ground-state tensors, environments, regularisation bonds, energies."""
+def _has_heff_entries(be):
+    return bool(getattr(be, "has_qp_heff", False)) and all(
+        hasattr(be, m) for m in ("qp_half", "qp_heff_site", "transfer_left_pair", "transfer_right_pair"))
 
-    def __init__(self, H, phi: LeftGaugedQP, lenvs, alg: QuasiparticleAnsatz, renvs=None):
+
+class _QPContext:
+    """Everything that does not depend on X: ground-state tensors, environments, regularisation bonds, energies.
+
+    device=True: the fused route -- mpsk_qp_heff_site per site and part (B = VL X, the three terms, the pull-back and
+    -E X in one entry), the B-independent half of the third term once per site and context (mpsk_qp_half), and the pair
+    transfers wherever qp_envs adds a transfer of B to a transfer of lB / rB.  device=False: the composed route (three
+    mpsk_dAC, three axpby, two GEMMs), which is also what a backend without the entries runs."""
+
+    def __init__(self, H, phi: LeftGaugedQP, lenvs, alg: QuasiparticleAnsatz, renvs=None, device=False):
         self.H, self.alg, self.be = H, alg, phi.be
         be = self.be
+        if device and not _has_heff_entries(be):
+            from ._lib import MpskError
+            raise MpskError("device=True: this backend has no mpsk_qp_heff_site / pair transfers")
+        self.device = bool(device)
+        self.half = {}                  # site -> mpsk_qp_half(H[site], GL[site], AL[site]), made on first use
         gs, rgs = phi.left_gs, phi.right_gs
         self.trivial = phi.trivial
         renvs = lenvs if (renvs is None and self.trivial) else (_environments(rgs, H) if renvs is None else renvs)
@@ -292,28 +307,34 @@ class _QPContext:
         nparts = phi.nparts
         Bs = [[phi.B(k, s, vec) for k in range(nparts)] for s in range(n)]
         lBs, rBs = [None] * n, [None] * n
+
+        def left(pos, lB):              # T(GL; B, AL) + T(lB; AR, AL): the B of this site joins what came from further left
+            if lB is None:
+                return _lin(lambda b: be.transfer_left(H[pos], self.GL[pos], b, AL[pos]), Bs[pos])
+            if self.device:
+                return [be.transfer_left_pair(H[pos], self.GL[pos], b, v, AR[pos], AL[pos]) for b, v in zip(Bs[pos], lB)]
+            nxt = _lin(lambda b: be.transfer_left(H[pos], self.GL[pos], b, AL[pos]), Bs[pos])
+            return _acc(be, nxt, _lin(lambda v: be.transfer_left(H[pos], v, AR[pos], AL[pos]), lB))
+
+        def right(pos, rB):
+            if rB is None:
+                return _lin(lambda b: be.transfer_right(H[pos], self.GR[pos], b, AR[pos]), Bs[pos])
+            if self.device:
+                return [be.transfer_right_pair(H[pos], self.GR[pos], b, v, AL[pos], AR[pos]) for b, v in zip(Bs[pos], rB)]
+            nxt = _lin(lambda b: be.transfer_right(H[pos], self.GR[pos], b, AR[pos]), Bs[pos])
+            return _acc(be, nxt, _lin(lambda v: be.transfer_right(H[pos], v, AL[pos], AR[pos]), rB))
+
         if self.finite:                                                              # :146-170
             for pos in range(n - 1):
-                nxt = _lin(lambda b: be.transfer_left(H[pos], self.GL[pos], b, AL[pos]), Bs[pos])
-                if lBs[pos] is not None:
-                    nxt = _acc(be, nxt, _lin(lambda v: be.transfer_left(H[pos], v, AR[pos], AL[pos]), lBs[pos]))
-                lBs[pos + 1] = nxt
+                lBs[pos + 1] = left(pos, lBs[pos])
             for pos in range(n - 1, 0, -1):
-                nxt = _lin(lambda b: be.transfer_right(H[pos], self.GR[pos], b, AR[pos]), Bs[pos])
-                if rBs[pos] is not None:
-                    nxt = _acc(be, nxt, _lin(lambda v: be.transfer_right(H[pos], v, AL[pos], AR[pos]), rBs[pos]))
-                rBs[pos - 1] = nxt
+                rBs[pos - 1] = right(pos, rBs[pos])
             return Bs, lBs, rBs
         p = self.p
         for pos in range(n):                                                         # :66-79
-            nxt = _lin(lambda b: be.transfer_left(H[pos], self.GL[pos], b, AL[pos]), Bs[pos])
-            if lBs[pos] is not None:
-                nxt = _acc(be, nxt, _lin(lambda v: be.transfer_left(H[pos], v, AR[pos], AL[pos]), lBs[pos]))
-            lBs[(pos + 1) % n] = self._reg_ids(_phase(be, nxt, -p), H[pos].chir, pos)
+            lBs[(pos + 1) % n] = self._reg_ids(_phase(be, left(pos, lBs[pos]), -p), H[pos].chir, pos)
         for pos in range(n - 1, -1, -1):                                             # :81-97
-            nxt = _lin(lambda b: be.transfer_right(H[pos], self.GR[pos], b, AR[pos]), Bs[pos])
-            if rBs[pos] is not None and pos != n - 1:
-                nxt = _acc(be, nxt, _lin(lambda v: be.transfer_right(H[pos], v, AL[pos], AR[pos]), rBs[pos]))
+            nxt = right(pos, rBs[pos] if pos != n - 1 else None)
             rBs[(pos - 1) % n] = self._reg_ids(_phase(be, nxt, p), H[pos].chil, pos - 1)
         # :99-105  geometric sums over all unit cells further away
         lv = [self._levels(part, H[0].chil) for part in lBs[0]]
@@ -342,6 +363,17 @@ class _QPContext:
             if phi.xshapes[loc][0] == 0:
                 continue
             Dl, d, _ = self.AL[loc].shape
+            if self.device:
+                half = None
+                if rBs[loc] is not None:
+                    if loc not in self.half:
+                        self.half[loc] = be.qp_half(H[loc], self.GL[loc], self.AL[loc])
+                    half = self.half[loc]
+                for k in range(phi.nparts):
+                    lB, rB = (None if z is None else z[k] for z in (lBs[loc], rBs[loc]))
+                    be.qp_heff_site(H[loc], self.GL[loc], self.GR[loc], phi.VLs[loc], phi.X(k, loc, x), self.E[loc], lB,
+                                    None if lB is None else self.AR[loc], half, rB, out=phi.X(k, loc, out))
+                continue
             for k in range(phi.nparts):
                 B = Bs[loc][k]
                 Bn = be.dAC(H[loc], self.GL[loc], self.GR[loc], B)                     # B in the centre
@@ -363,11 +395,12 @@ def _times_i_vec(be, phi, v):
     return out
 
 
-def excitations_qp(H, alg: QuasiparticleAnsatz, phi0: LeftGaugedQP, lenvs=None, renvs=None, num=1):
-    """excitations(H, alg, phi0::QP, lenvs, renvs; num)  :39-64,127-143 -> (energies, [LeftGaugedQP])."""
+def excitations_qp(H, alg: QuasiparticleAnsatz, phi0: LeftGaugedQP, lenvs=None, renvs=None, num=1, device=False):
+    """excitations(H, alg, phi0::QP, lenvs, renvs; num)  :39-64,127-143 -> (energies, [LeftGaugedQP]).  device=True: the
+    fused route of _QPContext (mpsk_qp_heff_site, pair transfers); the default is the composed one."""
     be = phi0.be
     lenvs = _environments(phi0.left_gs, H) if lenvs is None else lenvs
-    ctx = _QPContext(H, phi0, lenvs, alg, renvs)
+    ctx = _QPContext(H, phi0, lenvs, alg, renvs, device)
     eig_ws = krylov.KrylovWorkspace(be)      # NOT ctx.ws: the GMRES solves run inside this solver's matvec
     found, Es = [], []
     for _ in range(num):
@@ -391,7 +424,8 @@ def excitations_qp(H, alg: QuasiparticleAnsatz, phi0: LeftGaugedQP, lenvs=None, 
     return [Es[k] for k in keep], [phi0.with_vec(found[k]) for k in keep]
 
 
-def excitations_momenta(H, alg: QuasiparticleAnsatz, momenta, psi, lenvs=None, rpsi=None, renvs=None, num=1, rng=None):
+def excitations_momenta(H, alg: QuasiparticleAnsatz, momenta, psi, lenvs=None, rpsi=None, renvs=None, num=1, rng=None,
+                        device=False):
     """excitations(H, alg, momentum | momenta, lmps::InfiniteMPS, lenvs, rmps, renvs; num)  :84-125.  A scalar momentum
     returns (energies[num], states[num]); a list returns (E[len(momenta), num], states[len(momenta)][num]).  rmps different
     from lmps: domain-wall (topologically non-trivial) excitations between two ground states."""
@@ -400,10 +434,10 @@ def excitations_momenta(H, alg: QuasiparticleAnsatz, momenta, psi, lenvs=None, r
     renvs = (lenvs if rpsi is psi else _environments(rpsi, H)) if renvs is None else renvs
     rng = np.random.default_rng(0) if rng is None else rng
     if np.isscalar(momenta):
-        return excitations_qp(H, alg, LeftGaugedQP.random(psi, momenta, rng, rpsi), lenvs, renvs, num)
+        return excitations_qp(H, alg, LeftGaugedQP.random(psi, momenta, rng, rpsi), lenvs, renvs, num, device)
     Ep, Bp = [], []
     for p in momenta:
-        e, b = excitations_qp(H, alg, LeftGaugedQP.random(psi, float(p), rng, rpsi), lenvs, renvs, num)
+        e, b = excitations_qp(H, alg, LeftGaugedQP.random(psi, float(p), rng, rpsi), lenvs, renvs, num, device)
         Ep.append(e)
         Bp.append(b)
     return np.array(Ep), Bp
