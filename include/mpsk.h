@@ -563,6 +563,26 @@ int mpsk_gemm(mpsk_ctx* ctx, int transA, int transB, int M, int N, int K, double
 int mpsk_gemm_pair(mpsk_ctx* ctx, int M, int N, int K, const void* P, int64_t ldp, const void* Q, int64_t ldq,
                    const void* B, int64_t ldb, const void* coef, int64_t ldcoef, double beta1, void* out1, int64_t ld1,
                    double beta2, void* out2, int64_t ld2);
+/* Site step of the sum of two finite MPS (src/states/finitemps.jl:397-408 the left half, :423-435 the right half): the
+ * carried gauge factor times the direct sum of the two states' site tensors, written as the direct-sum tensor itself.  The
+ * isometries F1 / F2 of the reference are never formed: they are the block offsets below.  A1: [D1, d, E1], A2: [D2, d, E2],
+ * column-major with the first index fastest, contiguous.
+ *   MPSK_DSUM_LEFT   G: [Dn, D1 + D2] (ldg), out: [Dn, d, E1 + E2]
+ *                    out[:, :, :E1] = G[:, :D1] A1,  out[:, :, E1:] = G[:, D1:] A2     (two contiguous halves of out)
+ *   MPSK_DSUM_RIGHT  G: [E1 + E2, Dn] (ldg), out: [D1 + D2, d, Dn]
+ *                    out[:D1, s, :] = A1[:, s, :] G[:E1, :],  out[D1:, s, :] = A2[:, s, :] G[E1:, :]
+ *                    (the two blocks interleave along the fastest index of out: no mpsk_gemm call writes that layout)
+ * The boundary sites are D1 = D2 = Dn = 1 with G = [1 1] on the left, and E1 = E2 = Dn = 1 with G = [1; 1] on the right.
+ * One launch: the tile list holds both block products (a grouped GEMM on v_mfma_f64_16x16x4_f64, operands staged through
+ * LDS as in mpsk_gemm), one workgroup per output tile, ascending k, no atomics and no workspace: results are bit-identical
+ * from run to run.  Partial tiles are guarded on every edge; nothing outside out is written.  2 d Dn (D1 E1 + D2 E2) flops.
+ * out must not overlap an operand.  mpsk_ctx_force_tile applies.  All of d, Dn, D1, D2, E1, E2 >= 1 and ldg >= the rows of
+ * G, else MPSK_ERR_INVALID.  MPSK_F64 only: a ctx set to MPSK_C128 gets MPSK_ERR_UNSUPPORTED (bond-embedded complex
+ * tensors run on it unchanged: concatenating embedded bond indices keeps their (re, im) pairing). */
+enum { MPSK_DSUM_LEFT = 0, MPSK_DSUM_RIGHT = 1 };
+int mpsk_dsum_site(mpsk_ctx* ctx, int side, int d, int Dn, int D1, int D2, int E1, int E2, const void* G, int64_t ldg,
+                   const void* A1, const void* A2, void* out);
+
 /* The four coefficient rows of mpsk_gemm_pair from the K singular values S (device) and one host scalar, on the device:
  * a line-search trial step at a new alpha costs no device-to-host copy.  coef: 4 K doubles, row r at coef + r K; rows a
  * mode does not use are zeroed.

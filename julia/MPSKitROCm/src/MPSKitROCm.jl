@@ -264,6 +264,9 @@ function transfer_right(v::ROCTensor{3}, ::Nothing, A::ROCTensor{3}, Ab::ROCTens
         CTX[], C_NULL, W, A.dims[2], A.dims[1], A.dims[3], Ab.dims[1], Ab.dims[3], A.ptr, Ab.ptr, v.ptr, out.ptr))
     return out
 end
+# ---- FiniteMPS + FiniteMPS: finitemps.jl:397-408 (side = 0, left half), :423-435 (side = 1, right half) ----
+"site step of the sum: G times the direct sum of A1 and A2, written as the direct-sum tensor (one launch); Dn = free leg of G"
+dsum_site!(out::ROCTensor{3}, side::Integer, G::ROCTensor{2}, A1::ROCTensor{3}, A2::ROCTensor{3}) = (check(ccall((:mpsk_dsum_site, libmpsk[]), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), CTX[], side, A1.dims[2], G.dims[side == 0 ? 1 : 2], A1.dims[1], A2.dims[1], A1.dims[3], A2.dims[3], G.ptr, G.dims[1], A1.ptr, A2.ptr, out.ptr)); out)
 # ---- local measurements: expval.jl:23-37, correlators.jl:25-38 ----
 "gram[w][t,s] = sum_{p,b} conj(Ab[p,t,b]) X[w][p,s,b] into device memory (W matrices d x d); X = Ab = AC: one-site rho"
 function site_gram!(gram::Ptr{Cvoid}, W::Integer, X::ROCTensor, Ab::ROCTensor{3})

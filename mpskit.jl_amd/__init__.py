@@ -28,3 +28,5 @@ from . import window  # noqa: F401,E402
 from .window import WindowMPS, WindowEnv, transition  # noqa: F401,E402   (window.dot: overlaps of two windows)
 from .propagator import propagator, DynamicalDMRG, NaiveInvert, Jeckelmann, GMRES, LinearCombination  # noqa: F401,E402
 from .susceptibility import fidelity_susceptibility, effective_excitation_hamiltonian, qp_dot  # noqa: F401,E402
+from . import linalg  # noqa: F401,E402
+from .linalg import normalize  # noqa: F401,E402   (psi1 + psi2, a * psi, dot(psi1, psi2) of finite states: linalg.py)

@@ -160,6 +160,8 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mpsk_qp_heff_site": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                           C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mpsk_dsum_site": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                       C.c_void_p, C.c_void_p, C.c_void_p],
 }
 # entries a library built before them may lack: load() leaves them unbound and Backend.has_* answers False
 OPTIONAL_SYMBOLS = ["mpsk_qp_heff_site"]

@@ -661,6 +661,28 @@ class Backend:
         check(self.lib.mpsk_gemm_pair(self.ctx, M, N, K, p_ptr, ldp, q_ptr, ldq, b_ptr, ldb, coef_ptr, ldcoef, float(beta1),
                                       o1_ptr, ld1, float(beta2), o2_ptr, ld2), "mpsk_gemm_pair")
 
+    DSUM_SIDES = {"left": 0, "right": 1}
+
+    def dsum_site(self, side, G: DTensor, A1: DTensor, A2: DTensor, out: DTensor = None, ldg=None):
+        """mpsk_dsum_site: the site step of FiniteMPS + FiniteMPS in one launch.  A1: (D1, d, E1), A2: (D2, d, E2).
+        side "left":  G (Dn, D1 + D2) -> out (Dn, d, E1 + E2), out[:, :, :E1] = G[:, :D1] A1, out[:, :, E1:] = G[:, D1:] A2;
+        side "right": G (E1 + E2, Dn) -> out (D1 + D2, d, Dn), out[:D1, s, :] = A1[:, s, :] G[:E1, :] and
+        out[D1:, s, :] = A2[:, s, :] G[E1:, :].  ldg: leading dimension of G when it is a view of a taller matrix."""
+        D1, d, E1 = A1.shape
+        D2, d2, E2 = A2.shape
+        gr, gc = G.shape
+        left = self.DSUM_SIDES[side] == 0
+        Dn = gr if left else gc
+        if d2 != d or (gc if left else gr) != (D1 + D2 if left else E1 + E2):
+            raise MpskError(f"dsum_site ({side}): G {G.shape} does not match the site tensors {A1.shape}, {A2.shape}")
+        shape = (Dn, d, E1 + E2) if left else (D1 + D2, d, Dn)
+        o = self.empty(*shape) if out is None else out
+        if o.shape != shape:
+            raise MpskError(f"dsum_site ({side}): out {o.shape} is not {shape}")
+        check(self.lib.mpsk_dsum_site(self.ctx, self.DSUM_SIDES[side], d, Dn, D1, D2, E1, E2, G.ptr, gr if ldg is None else ldg,
+                                      A1.ptr, A2.ptr, o.ptr), "mpsk_dsum_site")
+        return o
+
     GRASSMANN_MODES = {"retract": 0, "transport": 1, "precondition": 2}
 
     def grassmann_coef(self, S: DTensor, scalar, mode, out: DTensor = None):

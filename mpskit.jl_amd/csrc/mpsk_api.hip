@@ -3591,6 +3591,50 @@ int mpsk_gemm_pair(mpsk_ctx* c, int M, int N, int K, const void* P, int64_t ldp,
   return MPSK_OK;
 }
 
+// fp64 only; one launch, no workspace: the two block products are the two tile families of dsum_f64
+int mpsk_dsum_site(mpsk_ctx* c, int side, int d, int Dn, int D1, int D2, int E1, int E2, const void* G, int64_t ldg,
+                   const void* A1, const void* A2, void* out) {
+  REQUIRE(c && G && A1 && A2 && out, "NULL argument");
+  if (c->dtype == MPSK_C128) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_dsum_site: fp64 only");
+  REQUIRE(side == MPSK_DSUM_LEFT || side == MPSK_DSUM_RIGHT, "side must be MPSK_DSUM_LEFT or MPSK_DSUM_RIGHT");
+  REQUIRE(d > 0 && Dn > 0 && D1 > 0 && D2 > 0 && E1 > 0 && E2 > 0, "dimensions must be positive");
+  const bool left = side == MPSK_DSUM_LEFT;
+  const int64_t Dt = (int64_t)D1 + D2, Et = (int64_t)E1 + E2;
+  const int64_t g_rows = left ? Dn : Et, g_cols = left ? Dt : Dn;
+  REQUIRE(ldg >= g_rows, "ldg below the row count of G");
+  REQUIRE((int64_t)D1 * d <= 0x7fffffff && (int64_t)D2 * d <= 0x7fffffff && (int64_t)E1 * d <= 0x7fffffff &&
+              (int64_t)E2 * d <= 0x7fffffff && Dt <= 0x7fffffff && Et <= 0x7fffffff,
+          "a matrix extent exceeds 2^31 - 1");
+  const double* Gp = (const double*)G;
+  const double* a1 = (const double*)A1;
+  const double* a2 = (const double*)A2;
+  double* o = (double*)out;
+  const int64_t n_out = (left ? (int64_t)Dn * Et : Dt * Dn) * d;
+  auto overlaps = [&](const double* p, int64_t n) { return p < o + n_out && o < p + n; };
+  REQUIRE(!overlaps(a1, (int64_t)D1 * d * E1) && !overlaps(a2, (int64_t)D2 * d * E2) &&
+              !overlaps(Gp, ldg * (g_cols - 1) + g_rows),
+          "out must not alias an operand");
+  HIPCHK(hipSetDevice(c->device));
+  DsumArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (left) {
+    // out[:, :, :E1] = G[:, :D1] A1 and out[:, :, E1:] = G[:, D1:] A2: two contiguous matrices Dn x (d E)
+    a.f[0] = mk(Gp, a1, o, Dn, d * E1, D1, ldg, D1, Dn);
+    a.f[1] = mk(Gp + (int64_t)D1 * ldg, a2, o + (int64_t)Dn * d * E1, Dn, d * E2, D2, ldg, D2, Dn);
+    a.rmod[0] = a.rmod[1] = Dn;
+    a.rstride = 0;
+  } else {
+    // out[:D1, s, :] = A1[:, s, :] G[:E1, :] and out[D1:, s, :] = A2[:, s, :] G[E1:, :]: the products (D d) x Dn with
+    // row (a, s) of block f written at a + s (D1 + D2)
+    a.f[0] = mk(a1, Gp, o, D1 * d, Dn, E1, (int64_t)D1 * d, ldg, Dt * d);
+    a.f[1] = mk(a2, Gp + E1, o + D1, D2 * d, Dn, E2, (int64_t)D2 * d, ldg, Dt * d);
+    a.rmod[0] = D1; a.rmod[1] = D2;
+    a.rstride = Dt;
+  }
+  HIPCHK(dsum_f64(a, c->stream));
+  return MPSK_OK;
+}
+
 int mpsk_grassmann_coef(mpsk_ctx* c, int K, const void* S, double scalar, int mode, void* coef) {
   REQUIRE(c && S && coef, "NULL argument");
   if (c->dtype == MPSK_C128) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_grassmann_coef: fp64 only");

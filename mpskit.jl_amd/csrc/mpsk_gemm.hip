@@ -1203,6 +1203,100 @@ hipError_t gemm_pair_f64(const GemmPairArgs& g, hipStream_t s) {
   return aligned ? launch_pair_tile<true, false>(g, bm, bn, s) : launch_pair_tile<false, false>(g, bm, bn, s);
 }
 
+// ---- direct-sum site step (mpsk_dsum_site) ------------------------------------------------------
+// Two independent products C_f = A_f B_f (f = 0, 1; neither operand transposed, own M / N / K extents) in ONE launch: the
+// tile list is the tiles of family 0 followed by those of family 1, one workgroup per output tile, k ascending, no split
+// and no workspace -- bit-identical from run to run.  The k loop is gemm_acc_dispatch of the plain core (same loaders, LDS
+// images and MFMA operand order); only the epilogue differs: row m of a family lands at
+//   C_f + (m % rmod_f) + (m / rmod_f) * rstride + n * ldc
+// which is how the right-hand step interleaves its two blocks along the fastest index of the result (rows (a, s) of
+// A_f[:, s, :] G_f go to a + s (D1 + D2)); the left-hand step has rmod_f = M_f and writes two plain matrices.
+template <int BM, int BN, bool ALIGNED>
+__device__ __forceinline__ void dsum_tile(const GemmArgs& g, int rmod, int64_t rstride, int t, double* smem) {
+  constexpr int WTM = BM / 2, WTN = BN / 2, TM = WTM / 16, TN = WTN / 16;
+  const int tilesM = (g.M + BM - 1) / BM;
+  const int bn = t / tilesM, bm = t - bn * tilesM;
+  const int m0 = bm * BM, n0 = bn * BN;
+  d4 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+  gemm_acc_dispatch<BM, BN, false, false, ALIGNED, false, false>(g, g.A, g.B, 0, m0, n0, 0, (g.K + BK - 1) / BK, acc, smem);
+  // epilogue: lane holds C[m = .. + fr][n = .. + fq + 4*reg]; every edge is guarded, nothing outside the block is written
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wm = wave & 1, wn = wave >> 1, fr = lane & 15, fq = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int m = m0 + wm * WTM + i * 16 + fr;
+    const int sl = m / rmod;
+    double* const row = g.C + (m - sl * rmod) + (int64_t)sl * rstride;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const int n = n0 + wn * WTN + j * 16 + fq + 4 * rg;
+        if (m < g.M && n < g.N) row[(int64_t)n * g.ldc] = acc[i][j][rg];
+      }
+    }
+  }
+}
+
+template <int BM, int BN, bool ALIGNED>
+__global__ __launch_bounds__(NTHREADS, min_waves(BM, BN)) void dsum_f64_kernel(DsumArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int t = blockIdx.x;      // uniform per workgroup: the two families are two straight-line copies of the tile body
+  if (t < a.ntiles0) dsum_tile<BM, BN, ALIGNED>(a.f[0], a.rmod[0], a.rstride, t, smem);
+  else dsum_tile<BM, BN, ALIGNED>(a.f[1], a.rmod[1], a.rstride, t - a.ntiles0, smem);
+}
+
+template <int BM, int BN, bool ALIGNED>
+static hipError_t launch_dsum(DsumArgs& a, hipStream_t s) {
+  using IA = LdsImg<BM, false>;
+  using IB = LdsImg<BN, true>;
+  constexpr size_t smem = (2 * IA::SIZE + 2 * IB::SIZE) * sizeof(double);
+  static std::atomic<uint64_t> done{0};
+  const auto kern = dsum_f64_kernel<BM, BN, ALIGNED>;
+  if (hipError_t e = ensure_dyn_smem(done, reinterpret_cast<const void*>(kern), smem); e != hipSuccess) return e;
+  int64_t nt[2];
+  for (int f = 0; f < 2; ++f) nt[f] = (int64_t)((a.f[f].M + BM - 1) / BM) * ((a.f[f].N + BN - 1) / BN);
+  if (nt[0] + nt[1] > 0x7fffffff) return hipErrorInvalidValue;
+  a.ntiles0 = (int)nt[0];
+  hipLaunchKernelGGL(kern, dim3((unsigned)(nt[0] + nt[1])), dim3(NTHREADS), smem, s, a);
+  return hipGetLastError();
+}
+
+template <bool ALIGNED>
+static hipError_t launch_dsum_tile(DsumArgs& a, int bm, int bn, hipStream_t s) {
+  if (bm == 128 && bn == 128) return launch_dsum<128, 128, ALIGNED>(a, s);
+  if (bm == 64 && bn == 128) return launch_dsum<64, 128, ALIGNED>(a, s);
+  if (bm == 128 && bn == 64) return launch_dsum<128, 64, ALIGNED>(a, s);
+  return launch_dsum<64, 64, ALIGNED>(a, s);
+}
+
+hipError_t dsum_f64(const DsumArgs& in, hipStream_t s) {
+  DsumArgs a = in;
+  for (int f = 0; f < 2; ++f) {
+    const GemmArgs& g = a.f[f];
+    if (g.M <= 0 || g.N <= 0 || g.K <= 0 || !g.A || !g.B || !g.C || a.rmod[f] <= 0) return hipErrorInvalidValue;
+  }
+  // the products of a site step are bond-sized (M, N, K <= D1 + D2 or d times that): the 64x64 tile of the plain core's
+  // short-to-medium products; 128 rows once the tile list is several waves of workgroups long (as gemm_pair_f64)
+  int bm = 64, bn = 64;
+  int64_t t64 = 0;
+  for (int f = 0; f < 2; ++f) t64 += (int64_t)((a.f[f].M + 63) / 64) * ((a.f[f].N + 63) / 64);
+  if (t64 > 4096) bm = 128;
+  if (g_force_bm.load()) { bm = g_force_bm.load(); bn = g_force_bn.load(); }
+  bool aligned = true;
+  for (int f = 0; f < 2; ++f) {
+    const GemmArgs& g = a.f[f];
+    aligned = aligned && (g.M % bm == 0) && (g.N % bn == 0) && (g.K % BK == 0) && (g.lda % 2 == 0) && (g.ldb % 2 == 0) &&
+              ((uintptr_t)g.A % 16 == 0) && ((uintptr_t)g.B % 16 == 0) && g.lda < ((int64_t)1 << 21) &&
+              g.ldb < ((int64_t)1 << 21);
+  }
+  return aligned ? launch_dsum_tile<true>(a, bm, bn, s) : launch_dsum_tile<false>(a, bm, bn, s);
+}
+
 // Coefficient rows of mpsk_gemm_pair for the Grassmann geometry, filled from the singular values on the device (a trial
 // step at a new alpha costs this launch, not a copy): coef[r * K + k], r = a1, b1, a2, b2; rows a mode does not use are
 // zeroed.  One workgroup: K is a bond dimension.

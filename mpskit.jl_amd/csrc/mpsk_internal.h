@@ -117,6 +117,19 @@ struct GemmPairArgs {
   double beta1, beta2;
 };
 hipError_t gemm_pair_f64(const GemmPairArgs& g, hipStream_t s);
+// ---- direct-sum site step (mpsk_dsum_site; mpsk_gemm.hip) -------------------------------------
+// Two products C_f = A_f B_f in one launch (a grouped GEMM: the tile list of family 0, then that of family 1).  Of each
+// GemmArgs only A, B, C, M, N, K, lda, ldb, ldc and K-segment 0 (nseg = 1, segA[0] = segB[0] = 0) are read; neither
+// operand is transposed.  Row m of family f is written at C_f + (m % rmod[f]) + (m / rmod[f]) * rstride + n * ldc.
+// One workgroup per output tile, k ascending, no workspace; ntiles0 is filled by dsum_f64.
+struct DsumArgs {
+  GemmArgs f[2];
+  int rmod[2];
+  int64_t rstride;
+  int ntiles0;
+};
+static_assert(sizeof(DsumArgs) <= 4096, "DsumArgs is passed by value as a kernel argument");
+hipError_t dsum_f64(const DsumArgs& a, hipStream_t s);
 // coefficient rows of the Grassmann retraction / transport / preconditioner (mpsk_grassmann_coef): coef[r * K + k],
 // r = a1, b1, a2, b2; mode 0 retract, 1 transport, 2 precondition
 hipError_t grassmann_coef(int K, const double* S, double scalar, int mode, double* coef, hipStream_t s);

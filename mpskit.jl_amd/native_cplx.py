@@ -98,6 +98,34 @@ class NativeFiniteMPS:
         out.A = [self.be.copy(t) for t in self.A]
         return out
 
+    # ---- linear algebra (finitemps.jl:365-469; linalg.py: the composed route on gemm_c / qrpos_c / lqpos_c) ----
+    __array_ufunc__ = None
+
+    def __add__(self, other):
+        from . import linalg
+        return linalg.add(self, other) if isinstance(other, NativeFiniteMPS) else NotImplemented
+
+    def __sub__(self, other):
+        from . import linalg
+        return linalg.sub(self, other) if isinstance(other, NativeFiniteMPS) else NotImplemented
+
+    def __mul__(self, a):
+        from . import linalg
+        return linalg.scale(self, a) if isinstance(a, (int, float, complex, np.number)) else NotImplemented
+
+    __rmul__ = __mul__
+
+    def __neg__(self):
+        return self * -1.0
+
+    def normalize(self):
+        from . import linalg
+        return linalg.normalize_(self)
+
+    def dot(self, other):
+        from . import linalg
+        return linalg.dot(self, other)
+
 
 class ComplexMPOHamiltonian:
     """MPOHamiltonian with ComplexF64 entries (mpohamiltonian.jl:8-31): a periodic list of MPSK_C128 slices.  `data[site]` =

@@ -244,6 +244,35 @@ class FiniteMPS:
         n = self.be.norm(self.AC(0))
         return n / np.sqrt(2.0) if self.cplx else n
 
+    # ---- linear algebra (finitemps.jl:365-469; linalg.py) ----
+    __array_ufunc__ = None              # a NumPy scalar on the left defers to __rmul__
+
+    def __add__(self, other):
+        from . import linalg
+        return linalg.add(self, other) if isinstance(other, FiniteMPS) else NotImplemented
+
+    def __sub__(self, other):
+        from . import linalg
+        return linalg.sub(self, other) if isinstance(other, FiniteMPS) else NotImplemented
+
+    def __mul__(self, a):
+        from . import linalg
+        return linalg.scale(self, a) if isinstance(a, (int, float, complex, np.number)) else NotImplemented
+
+    __rmul__ = __mul__
+
+    def __neg__(self):
+        return self * -1.0
+
+    def normalize(self):
+        """normalize! (finitemps.jl:468): this state, scaled to norm 1"""
+        from . import linalg
+        return linalg.normalize_(self)
+
+    def dot(self, other):
+        from . import linalg
+        return linalg.dot(self, other)
+
     def download(self, t):
         """host copy of one of this state's tensors (complex if the state is complex: un-embedded)."""
         h = self.be.download(t)

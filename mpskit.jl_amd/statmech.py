@@ -351,12 +351,16 @@ def leading_boundary(psi, mpo: DenseMPO, alg=None, envs=None):
 
 
 def dot(a, b, c=None, krylovdim=30, tol=1e-12, rng=None):
-    """dot(psi1, psi2)  (infinitemps.jl:258-264): the leading (:LM) eigenvalue of the unit-cell transfer matrix
+    """dot(psi1, psi2) of two FiniteMPS / NativeFiniteMPS: linalg.dot.
+    dot(psi1, psi2)  (infinitemps.jl:258-264): the leading (:LM) eigenvalue of the unit-cell transfer matrix
     TransferMatrix(psi2.AL, psi1.AL); dot(a, mpo, b)  (densempo.jl:89-97): that of TransferMatrix(b.AL, mpo, a.AL).  Real
     states; the start vector is random (rng, default seed 0)."""
     from . import window
     if isinstance(a, window.WindowMPS) and c is None:                       # windowmps.jl:165-176
         return window.dot(a, b)
+    from . import linalg
+    if c is None and any(isinstance(a, t) and isinstance(b, t) for t in (linalg.FiniteMPS, linalg.NativeFiniteMPS)):
+        return linalg.dot(a, b)                                             # finitemps.jl:459-464
     mpo, ket = (None, b) if c is None else (b, c)
     bra = a
     if not isinstance(bra, InfiniteMPS) or not isinstance(ket, InfiniteMPS):
