@@ -14,7 +14,7 @@
 // so this agrees with Householder QRpos to O(cond * eps).
 // Shift policy: the bound of Fukaya et al. (s = 11 (mn + n(n+1)) u ||A||^2) is a worst-case constant, ~1e7 u here; a shift
 // that large leaves cond(Q1) ~ sqrt(s) / sigma_min, and on the benchmark sweep 28 % of the factorizations then needed a full
-// third Cholesky pass.  The callers (mpsk_api.hip) therefore try shift_scale * s with shift_scale = 1e-8 first (a shift at
+// third Cholesky pass.  The callers (mpsk_api_factor.hip) therefore try shift_scale * s with shift_scale = 1e-8 first (a shift at
 // the rounding level of the Gram matrix: 2 % repeats, no breakdown on the benchmark states) and repeat the factorization
 // with the published shift when the device flags a breakdown; MPSK_CQ_SHIFT_SCALE overrides the first attempt's scale.
 // Robustness: the first pass is shifted (Fukaya et al., "Shifted Cholesky QR", SIAM J. Sci. Comput.

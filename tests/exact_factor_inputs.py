@@ -254,7 +254,7 @@ def gauss_small_reference(kind):
 
 # ------------------------------------------------------------------------------------------------------------------
 # the plan, as the library makes it (mpsk_svd.hip: svd_plan, csvd_plan, svd_default_chains, the clamps of tsvd();
-# mpsk_api.hip: which matrix the Jacobi iteration sees; mpsk_cholqr.hip: cq_use_trsm, cq_bufs)
+# mpsk_api_factor.hip: which matrix the Jacobi iteration sees; mpsk_cholqr.hip: cq_use_trsm, cq_bufs)
 # ------------------------------------------------------------------------------------------------------------------
 N_XSTREAMS = 3                           # extra streams a ctx hands to tsvd(): at most 4 chains
 

@@ -150,9 +150,9 @@ TALL = [c for c in fi.house_cases() if c.family == "stacked"]
 
 
 def test_house_plan_lines_are_still_in_the_library_and_every_case_is_on_its_route():
-    """house_plan() restates the host lines of qrpos() in mpsk_gauge.hip and the two dispatch conditions of mpsk_api.hip"""
+    """house_plan() restates the host lines of qrpos() in mpsk_gauge.hip and the two dispatch conditions of mpsk_api_factor.hip"""
     g = open(os.path.join(CSRC, "mpsk_gauge.hip")).read()
-    api = open(os.path.join(CSRC, "mpsk_api.hip")).read()
+    api = open(os.path.join(CSRC, "mpsk_api_factor.hip")).read()
     for line in ("constexpr int QR_T = 512;", "constexpr int QR_NW = QR_T / 64;", "constexpr int QR_NBI = 8;",
                  "constexpr int QR_NB = 32;", "constexpr int QR_LDS_DOUBLES = 19968;", "constexpr int QR_SCRATCH = 32 * QR_NW;",
                  "if (m > QR_LDS_DOUBLES - QR_SCRATCH) {", "const int nbo = (n - j0 < QR_NB) ? n - j0 : QR_NB;",

@@ -1,5 +1,5 @@
 """The blocked Householder QRpos (qrpos() in mpsk_gauge.hip: qr_block_kernel, wy_solve_kernel, set_identity_kernel,
-qr_finish_kernel, transpose_kernel behind LQpos) and the complex gauge steps (qrpos_c128 / lqpos_c128 in mpsk_api.hip:
+qr_finish_kernel, transpose_kernel behind LQpos) and the complex gauge steps (qrpos_c128 / lqpos_c128 in mpsk_api_factor.hip:
 cx_embed_kernel, cx_half_kernel, cx_ctranspose_kernel) on inputs whose factors are known exactly
 (tests/exact_factor_inputs.py: qr_stacked, house_cases).
 
