@@ -281,6 +281,16 @@ int mpsk_dAC_proj(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
  *   MPSK_C128 (mpsk_ctx_set_dtype) gets MPSK_ERR_UNSUPPORTED.  Dro == Dr is mpsk_dC bit for bit (same launches, same tiles). */
 int mpsk_dC_proj(mpsk_ctx* ctx, int W, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR, const void* c,
                  void* y);
+/* mpsk_dC_proj_c == c_proj on interleaved complex128 operands (the zero-site step of approximate on a complex uniform state):
+ *   y[p,q] = sum_w GL[w][p,a] c[a,b] GR[w][b,q],  nothing conjugated;  GL: W slabs [Dlo, Dl], GR: W slabs [Dr, Dro] (slab
+ *   stride Dr Dro complex elements), c: [Dl, Dr], y: [Dlo, Dro], all interleaved ComplexF64, 16-byte aligned.
+ *   The rectangular form of the complex mpsk_dC: planes of c and GR in the workspace, one batched GEMM T[w] = GL[w] c on
+ *   2 Dlo rows, then one segmented-K complex GEMM over (w, b) with N = Dro:  8 W (Dlo Dl Dr + Dlo Dr Dro) flops; workspace
+ *   2 (Dl Dr + W Dr Dro) + 2 W Dlo Dr doubles (each plane rounded up to an even count).  Asynchronous on the ctx stream.
+ *   The ctx must be set to MPSK_C128 (mpsk_ctx_set_dtype); an MPSK_F64 ctx gets MPSK_ERR_UNSUPPORTED.  Dro == Dr is mpsk_dC
+ *   under MPSK_C128 bit for bit (same launches, same tiles). */
+int mpsk_dC_proj_c(mpsk_ctx* ctx, int W, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR, const void* c,
+                   void* y);
 /* mpsk_dAC2_proj == ac2_proj applied to the two factors of the state above, AC [Dl, d1, Dm] and AR [Dm, d2, Dr] (as
  * mpsk_dAC2_product takes them); Y: [Dlo, d1, Dro, d2] (the layout of mpsk_dAC2's result).
  *   MPSK_F64: factorised through the middle bond, Y = sum_u Lhalf[u] Rhalf[u] with Lhalf[u] [Dlo, d1, Dm] and Rhalf[u]
@@ -612,6 +622,11 @@ int mpsk_vscal(mpsk_ctx* ctx, int64_t n, double alpha, void* x);
  * multiplication by i of a complex tensor carried as 2x2 real blocks on its bond indices (integrators.jl:21
  * `-1im * dt` on the embedded representation, mpskit.jl_amd/cplx.py) */
 int mpsk_vtimes_i(mpsk_ctx* ctx, int64_t n, const void* x, void* y);
+/* interleaved complex z (n COMPLEX elements, 16-byte aligned) <-> planar p = [Re: n doubles | Im: n doubles], the vector
+ * layout of the complex Arnoldi of the host (krylov.eigsolve_lm_planar); out of place, one memory-bound launch each way
+ * (16 n bytes read, 16 n written), asynchronous, exact. */
+int mpsk_vsplit_c(mpsk_ctx* ctx, int64_t n, const void* z, void* p);
+int mpsk_vjoin_c(mpsk_ctx* ctx, int64_t n, const void* p, void* z);
 int mpsk_vcopy(mpsk_ctx* ctx, int64_t n, const void* x, void* y);
 int mpsk_vzero(mpsk_ctx* ctx, int64_t n, void* x);
 /* fused Gram-Schmidt helpers: xs = HOST array of k device pointers.

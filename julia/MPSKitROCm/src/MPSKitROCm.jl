@@ -171,6 +171,17 @@ function (h::MPO_∂∂C{<:ROCTensor,<:ROCTensor})(c::ROCTensor{2})
         CTX[], h.leftenv.dims[1], h.leftenv.dims[2], Dl, Dr, h.leftenv.ptr, h.rightenv.ptr, c.ptr, y.ptr))
     return y
 end
+"c_proj (derivatives.jl:204-207) on ComplexF64 tensors: GL [W, Dlo, Dl], GR [W, Dr, Dro], c [Dl, Dr] -> [Dlo, Dro]"
+function c_proj(GL::ROCTensor{3}, GR::ROCTensor{3}, c::ROCTensor{2})
+    @assert GL.cplx && GR.cplx && c.cplx
+    y = ROCTensor((GL.dims[2], GR.dims[3]); cplx=true)
+    with_dtype(true) do
+        check(ccall((:mpsk_dC_proj_c, libmpsk[]), Cint,
+            (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+            CTX[], GL.dims[1], GL.dims[2], c.dims[1], c.dims[2], GR.dims[3], GL.ptr, GR.ptr, c.ptr, y.ptr))
+    end
+    return y
+end
 function (h::MPO_∂∂AC2{ROCSlice,<:ROCTensor,<:ROCTensor})(x::ROCTensor{4})
     Dl, d1, Dr, d2 = x.dims
     y = ROCTensor((h.leftenv.dims[2], d1, Dr, d2))

@@ -133,6 +133,10 @@ SIGNATURES = {
                       C.c_void_p],
     "mpsk_dC_proj": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                      C.c_void_p],
+    "mpsk_dC_proj_c": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.c_void_p],
+    "mpsk_vsplit_c": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "mpsk_vjoin_c": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "mpsk_dAC2_proj": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mpsk_vdiff_nrm2": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, c_double_p],

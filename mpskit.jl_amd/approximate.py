@@ -117,9 +117,11 @@ def approximate(psi0, toapprox, alg, envs=None):
     Hamiltonian), alg = VOMPS() (approximate/vomps.jl; a VUMPS is converted, as the reference's deprecation does); eps is the
     Galerkin error.  psi0 an MPSMultiline: toapprox = (MPOMultiline, MPSMultiline), alg = VOMPS() (multiline.approximate).
     Not implemented for uniform states: IDMRG1 / IDMRG2 (approximate/idmrg.jl), complex tensors."""
-    from . import multiline, window
+    from . import multiline, native_cplx, window
     if isinstance(psi0, window.WindowMPS):
         return window.approximate(psi0, toapprox, alg, envs)
+    if isinstance(psi0, native_cplx.NativeInfiniteMPS):
+        return native_cplx.approximate(psi0, toapprox, alg, envs)
     if isinstance(psi0, multiline.MPSMultiline):
         return multiline.approximate(psi0, toapprox, alg, envs)
     if isinstance(psi0, InfiniteMPS):
@@ -157,7 +159,8 @@ def _approximate_inf(psi, toapprox, alg, envs=None):  # approximate/vomps.jl:1-8
         raise TypeError("approximate on an InfiniteMPS takes (O, above): a DenseMPO or SparseMPO and an InfiniteMPS")
     O, above = toapprox
     if getattr(psi, "cplx", False) or getattr(above, "cplx", False) or getattr(O, "cplx", False):
-        raise NotImplementedError("approximate on an InfiniteMPS: complex states / operators are not supported (real fp64 only)")
+        raise NotImplementedError("approximate on an InfiniteMPS: complex states / operators are not supported (real fp64 only); "
+                                  "native_cplx.NativeInfiniteMPS runs them on interleaved storage (native_cplx.approximate)")
     if len(above) != len(psi):
         raise ValueError(f"unit cells of the states above ({len(above)}) and below ({len(psi)}) differ")
     be, n = psi.be, len(psi)
@@ -278,7 +281,9 @@ def _site_matrices(sl, odim, d):
 def make_time_mpo(H: MPOHamiltonian, dt, alg=None):
     """make_time_mpo(H, dt, alg)  (timeevmpo.jl:12-207): the MPO of exp(tau H), tau = -i dt, to second order in tau per
     application: alg = WII() (arXiv:1407.1832 / 1901.05824, odim - 1 levels) or TaylorCluster(1) == WI().  The result is a
-    SparseMPO (both boundary vectors on level 0), stored real when tau is real (dt purely imaginary)."""
+    SparseMPO (both boundary vectors on level 0), stored real when tau is real (dt purely imaginary).  A dt with a real part
+    gives a complex SparseMPO, for a finite chain and for an infinite Hamiltonian alike: native_cplx.approximate applies it
+    (NativeFiniteMPS; NativeInfiniteMPS with VOMPS)."""
     from scipy.linalg import expm
     alg = WII() if alg is None else alg
     tau = -1j * complex(dt)

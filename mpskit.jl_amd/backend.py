@@ -443,6 +443,33 @@ class Backend:
         check(self.lib.mpsk_dC_proj(self.ctx, W, Dlo, Dl, Dr, Dro, GL.ptr, GR.ptr, c.ptr, y.ptr), "mpsk_dC_proj")
         return y
 
+    def dC_proj_c(self, GL: DTensor, GR: DTensor, c: DTensor, out: DTensor = None):
+        """mpsk_dC_proj_c (c_proj on interleaved complex128): GL (W, 2 Dlo, Dl), GR (W, 2 Dr, Dro), c (2 Dl, Dr); the result is
+        (2 Dlo, Dro).  Nothing is conjugated; asynchronous."""
+        Dl2, Dr = c.shape
+        W, Dlo2, Dl = GL.shape
+        W2, Dr2, Dro = GR.shape
+        assert W2 == W and Dl2 == 2 * Dl and Dr2 == 2 * Dr, (GL.shape, GR.shape, c.shape)
+        y = self.empty(Dlo2, Dro) if out is None else out
+        self._set_dtype(True)
+        try:
+            check(self.lib.mpsk_dC_proj_c(self.ctx, W, Dlo2 // 2, Dl, Dr, Dro, GL.ptr, GR.ptr, c.ptr, y.ptr), "mpsk_dC_proj_c")
+        finally:
+            self._set_dtype(False)
+        return y
+
+    def split_c(self, z: DTensor, out: DTensor = None):
+        """mpsk_vsplit_c: interleaved complex tensor (z.size doubles) -> planar vector [Re | Im] of the same length."""
+        p = self.empty(z.size) if out is None else out
+        check(self.lib.mpsk_vsplit_c(self.ctx, z.size // 2, z.ptr, p.ptr), "mpsk_vsplit_c")
+        return p
+
+    def join_c(self, p: DTensor, shape, out: DTensor = None):
+        """mpsk_vjoin_c: planar vector [Re | Im] -> interleaved complex tensor of `shape` (first dimension doubled)."""
+        z = self.empty(*shape) if out is None else out
+        check(self.lib.mpsk_vjoin_c(self.ctx, p.size // 2, p.ptr, z.ptr), "mpsk_vjoin_c")
+        return z
+
     def dAC2_proj(self, H1, H2, GL: DTensor, GR: DTensor, AC: DTensor, AR: DTensor, out: DTensor = None):
         """mpsk_dAC2_proj (ac2_proj) on the two factors of the state above, AC [Dl, d1, Dm] and AR [Dm, d2, Dr], with
         GL (Wl, Dlo, Dl) and GR (Wr, Dr, Dro).  Returns Y[Dlo, d1, Dro, d2]; the two-site tensor is not formed (fp64)."""

@@ -374,9 +374,11 @@ def changebonds(psi, H=None, alg=None, envs=None, rng=None):
     InfiniteMPS: also RandExpand.  The envs returned are the ones passed in (None when none were passed and the algorithm
     needs none: RandExpand, SvdCut), still attached to the OLD state, as in the reference: infinite environments recalculate
     themselves when they are next read with the new state, and None makes the next algorithm build its own."""
-    from . import window
+    from . import native_cplx, window
     if isinstance(psi, window.WindowMPS):
         return window.changebonds(psi, H, alg, envs, rng)
+    if isinstance(psi, native_cplx.NativeInfiniteMPS):
+        raise NotImplementedError("changebonds is not implemented for NativeInfiniteMPS (interleaved complex storage)")
     if isinstance(H, (OptimalExpand, SvdCut, RandExpand)) and alg is None:
         H, alg = None, H
     if isinstance(psi, InfiniteMPS):

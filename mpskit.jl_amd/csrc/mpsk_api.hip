@@ -607,10 +607,12 @@ static int dAC_c128(mpsk_ctx* c, const mpsk_mposlice* H, int Dlo, int Dl, int Dr
   return MPSK_OK;
 }
 
-static int dC_c128(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, const double* GL, const double* GR, const double* cm,
+// Dro: columns of the GR slabs [Dr, Dro] = columns of y (mpsk_dC passes Dro = Dr; mpsk_dC_proj_c the bond dimension of the
+// state below).
+static int dC_c128(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, int Dro, const double* GL, const double* GR, const double* cm,
                    double* y) {
   HIPCHK(hipSetDevice(c->device));
-  const size_t nx = (size_t)Dl * Dr, nG = (size_t)W * Dr * Dr, slab = (size_t)2 * Dlo * Dr;
+  const size_t nx = (size_t)Dl * Dr, nG = (size_t)W * Dr * Dro, slab = (size_t)2 * Dlo * Dr;
   Ws ws;
   const CxPlanes xpl(ws, nx), gpl(ws, nG);
   const size_t o_t1 = ws.take(slab * W);
@@ -620,8 +622,8 @@ static int dC_c128(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, const double* GL
   HIPCHK(gpl.split(c, GR));
   HIPCHK(stage1(c, W, 2 * Dlo, Dl, Dr, GL, xpl.at(c), T1, 0, 1, xpl.stride()));
   Segs sg;
-  level_segs(sg, W, (int64_t)slab, (int64_t)Dr * Dr, nullptr, 2, gpl.stride());
-  GemmArgs g3 = mk(T1, gpl.at(c), y, 2 * Dlo, Dr, Dr, 2 * Dlo, Dr, 2 * Dlo);
+  level_segs(sg, W, (int64_t)slab, (int64_t)Dr * Dro, nullptr, 2, gpl.stride());
+  GemmArgs g3 = mk(T1, gpl.at(c), y, 2 * Dlo, Dro, Dr, 2 * Dlo, Dr, 2 * Dlo);
   g3.cplx = 1;
   HIPCHK(gemm_segments(g3, sg, c->stream));
   return MPSK_OK;
@@ -1560,7 +1562,7 @@ int mpsk_dC(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, const void* GL, const v
   REQUIRE(c && GL && GR && cm && y, "NULL argument");
   REQUIRE(W > 0 && Dlo > 0 && Dl > 0 && Dr > 0, "dimensions must be positive");
   if (c->dtype == MPSK_C128)
-    return dC_c128(c, W, Dlo, Dl, Dr, (const double*)GL, (const double*)GR, (const double*)cm, (double*)y);
+    return dC_c128(c, W, Dlo, Dl, Dr, Dr, (const double*)GL, (const double*)GR, (const double*)cm, (double*)y);
   return dC_f64(c, W, Dlo, Dl, Dr, Dr, (const double*)GL, (const double*)GR, (const double*)cm, (double*)y);
 }
 
@@ -1572,6 +1574,15 @@ int mpsk_dC_proj(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, int Dro, const voi
   REQUIRE(W > 0 && Dlo > 0 && Dl > 0 && Dr > 0 && Dro > 0, "dimensions must be positive");
   if (c->dtype == MPSK_C128) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_dC_proj: implemented for MPSK_F64 only");
   return dC_f64(c, W, Dlo, Dl, Dr, Dro, (const double*)GL, (const double*)GR, (const double*)cm, (double*)y);
+}
+
+// c_proj on interleaved complex128 operands: the body of the complex mpsk_dC with GR slabs [Dr, Dro]; nothing is conjugated.
+int mpsk_dC_proj_c(mpsk_ctx* c, int W, int Dlo, int Dl, int Dr, int Dro, const void* GL, const void* GR, const void* cm,
+                   void* y) {
+  REQUIRE(c && GL && GR && cm && y, "NULL argument");
+  REQUIRE(W > 0 && Dlo > 0 && Dl > 0 && Dr > 0 && Dro > 0, "dimensions must be positive");
+  if (c->dtype != MPSK_C128) return fail(MPSK_ERR_UNSUPPORTED, "mpsk_dC_proj_c: the ctx must be set to MPSK_C128");
+  return dC_c128(c, W, Dlo, Dl, Dr, Dro, (const double*)GL, (const double*)GR, (const double*)cm, (double*)y);
 }
 
 int mpsk_dAC2(mpsk_ctx* c, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dlo, int Dl, int Dr,

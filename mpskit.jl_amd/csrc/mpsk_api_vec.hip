@@ -366,6 +366,23 @@ int mpsk_vtimes_i(mpsk_ctx* c, int64_t n, const void* x, void* y) {
   HIPCHK(vec_times_i((const double*)x, (double*)y, n, c->stream));
   return MPSK_OK;
 }
+// interleaved complex z[n] <-> planar p = [Re (n doubles) | Im (n doubles)], one memory-bound launch each way
+int mpsk_vsplit_c(mpsk_ctx* c, int64_t n, const void* z, void* p) {
+  REQUIRE(c && z && p, "NULL argument");
+  REQUIRE(n > 0 && z != p, "needs n > 0 and out-of-place operands");
+  REQUIRE(aligned16(z), "the interleaved operand must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(deinterleave((const double*)z, n, (double*)p, (double*)p + n, c->stream));
+  return MPSK_OK;
+}
+int mpsk_vjoin_c(mpsk_ctx* c, int64_t n, const void* p, void* z) {
+  REQUIRE(c && z && p, "NULL argument");
+  REQUIRE(n > 0 && z != p, "needs n > 0 and out-of-place operands");
+  REQUIRE(aligned16(z), "the interleaved operand must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(interleave((const double*)p, (const double*)p + n, n, (double*)z, c->stream));
+  return MPSK_OK;
+}
 int mpsk_vcopy(mpsk_ctx* c, int64_t n, const void* x, void* y) {
   REQUIRE(c && x && y, "NULL argument");
   HIPCHK(hipMemcpyAsync(y, x, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));

@@ -151,6 +151,24 @@ hipError_t deinterleave(const double* z, int64_t n, double* re, double* im, hipS
   return hipGetLastError();
 }
 
+// two planes -> interleaved complex, one pass (one 16-byte store per element)
+__global__ __launch_bounds__(256) void interleave_kernel(const double* __restrict__ re, const double* __restrict__ im,
+                                                         d2* __restrict__ z, int64_t n) {
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    d2 v;
+    v.x = re[e];
+    v.y = im[e];
+    z[e] = v;
+  }
+}
+hipError_t interleave(const double* re, const double* im, int64_t n, double* z, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  int64_t nb = (n + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(interleave_kernel, dim3((unsigned)nb), dim3(256), 0, s, re, im, reinterpret_cast<d2*>(z), n);
+  return hipGetLastError();
+}
+
 hipError_t copy_strided(const double* src, int64_t srs, int64_t scs, double* dst, int64_t drs, int64_t dcs, int64_t R,
                         int64_t C, hipStream_t s) {
   if (R <= 0 || C <= 0) return hipSuccess;

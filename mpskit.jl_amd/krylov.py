@@ -653,6 +653,8 @@ def eigsolve_lm_planar(be: Backend, matvec, x0: DTensor, num=1, tol=1e-10, krylo
         conv = int(np.sum(res[:num] < tol))
         if conv >= num or H[k, k - 1].real < 1e-300 or k < m:
             break
+        if _restart == maxiter - 1:      # out of restarts: the Ritz pairs above belong to THIS factorisation, keep it
+            break
         keep = min(max(num + 2, m // 3), m - 1)
         Q, _ = np.linalg.qr(S[:, :keep])
         newV = [be.lincomb(V[:k] + IV[:k], list(Q[:, j].real) + list(Q[:, j].imag)) for j in range(keep)]

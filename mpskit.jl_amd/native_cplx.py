@@ -12,6 +12,8 @@ right of it right-orthonormal), which is all the one-site algorithms need --
     timestep (TDVP, tdvp.jl:61-94)           ->  tdvp_step
     timestep (TDVP2, tdvp.jl:113-146)        ->  tdvp2_step
     approximate (fvomps.jl:11-87)            ->  approximate   (mpsk_dAC_proj / mpsk_dAC2_proj complex, NativeFinEnvPair)
+    approximate (approximate/vomps.jl)       ->  approximate on a NativeInfiniteMPS (uniform state, second half of this file:
+                                                 mpsk_dAC_proj / mpsk_dC_proj_c, NativePerMPOInfEnv, VOMPS)
 The lazy-gauge FiniteMPS of states.py (all drivers, two-site algorithms, infinite systems, excitations) stays on the embedded
 representation; the Krylov solvers are shared (real inner products on the 2n doubles of an interleaved vector are all a
 Hermitian Lanczos / Arnoldi iteration needs, and multiplication by i is mpsk_vtimes_i)."""
@@ -600,12 +602,16 @@ def _rel_diff(be, x: DTensor, y: DTensor):
     return float(np.sqrt(max(d2, 0.0) / n2))
 
 
-def approximate(psi0: NativeFiniteMPS, toapprox, alg, envs: NativeFinEnvPair = None):
+def approximate(psi0, toapprox, alg, envs=None, device=None):
     """approximate(psi0, (O, above), DMRG(...) | DMRG2(...)) on interleaved complex states (fvomps.jl:11-87): every site visit
     is one mpsk_dAC_proj / mpsk_dAC2_proj under MPSK_C128, one complex gauge step and one mixed transfer.  O may be the
     complex SparseMPO of a real-time make_time_mpo.  Returns (psi, envs, eps) with eps of the last sweep as in the
-    reference; the eps of every sweep is kept in envs.history."""
+    reference; the eps of every sweep is kept in envs.history.
+    psi0 a NativeInfiniteMPS: approximate(psi0, (O, above), VOMPS(...)) (approximate/vomps.jl), per site one mpsk_dAC_proj, one
+    mpsk_dC_proj_c (device: the route of c_proj, see NativePerMPOInfEnv), a regauge; eps is the Galerkin error."""
     from .algorithms import DMRG, DMRG2
+    if isinstance(psi0, NativeInfiniteMPS):
+        return _approximate_inf(psi0, toapprox, alg, envs, device=device)
     O, above = toapprox
     be, L = psi0.be, len(psi0)
     psi = psi0.copy()
@@ -724,6 +730,8 @@ def expectation_value(psi: NativeFiniteMPS, O, device=None):
     One mpsk_site_gram(AC_i, AC_i) under MPSK_C128 per site, one download (measure.py).  The centre is moved on a copy: psi
     and the environments that follow its gauge stay as they are."""
     from . import measure
+    if isinstance(psi, NativeInfiniteMPS):
+        return _expval_inf(psi, O)
     return measure.expectation_value(psi.copy(), O, None, device=device)
 
 
@@ -732,3 +740,437 @@ def correlator(psi: NativeFiniteMPS, O1, O2, i=None, js=None, device=None):
     copy, then one mpsk_transfer_left_gram under MPSK_C128 per site asked for through the right-canonical tensors."""
     from . import measure
     return measure.correlator(psi.copy(), O1, O2, i, js, device=device)
+
+
+# ---- uniform states on interleaved storage (infinitemps.jl, ortho.jl, permpoinfenv.jl, approximate/vomps.jl) ---------------
+# The same storage as above: every tensor is ONE buffer of interleaved complex128, first dimension doubled.  The gauge runs
+# on qrpos_c / lqpos_c / gemm_c, the transfers on the complex mpsk_transfer_left / _right (the kernel conjugates the bra), and
+# the non-Hermitian fixed points on krylov.eigsolve_lm_planar, whose planar [Re | Im] vectors are one mpsk_vsplit_c /
+# mpsk_vjoin_c away from the interleaved tensors the operators take.
+
+def _mul_CA(be, C: DTensor, A: DTensor):
+    Dl2, d, Dr = A.shape
+    return be.gemm_c(C, A.reshape(Dl2, d * Dr)).reshape(C.shape[0], d, Dr)
+
+
+def _mul_AC(be, A: DTensor, C: DTensor):
+    Dl2, d, Dr = A.shape
+    return be.gemm_c(A.reshape(Dl2 * d, Dr), C).reshape(Dl2, d, C.shape[1])
+
+
+def _dotc(be, x: DTensor, y: DTensor):
+    """conj(x) . y from real inner products of the interleaved doubles: Re = x . y, Im = -(x . (i y))"""
+    return complex(be.dot(x, y), -be.dot(x, be.times_i(y)))
+
+
+def _eig_lm_c(be, op, x0: DTensor, tol, krylovdim=30, maxiter=100):
+    """Leading (:LM) eigenpair of a complex-linear `op` on interleaved tensors of the shape of x0: the complex Arnoldi of
+    krylov.eigsolve_lm_planar, one split / join per application.  tol is relative to the operator's scale |op x0| / |x0|, as
+    statmech._eig_lm takes it.  Returns (complex eigenvalue, interleaved eigenvector of unit norm)."""
+    import warnings
+    shape = x0.shape
+    z = be.empty(*shape)
+
+    def mv(p, out):
+        be.join_c(p, shape, out=z)
+        return be.split_c(op(z), out=out)
+
+    scale = be.norm(op(x0)) / be.norm(x0)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")      # an unconverged restart only costs the caller another outer iteration
+        vals, vecs, _, _ = krylov.eigsolve_lm_planar(be, mv, be.split_c(x0), num=1, tol=tol * max(scale, 1e-300),
+                                                     krylovdim=krylovdim, maxiter=maxiter)
+    return complex(vals[0]), be.join_c(vecs[0], shape)
+
+
+def _bond_tl(be, v: DTensor, A: DTensor, Ab: DTensor):
+    """v'[q, b] = sum conj(Ab[p, s, q]) v[p, a] A[a, s, b] on one interleaved slab (transfer.jl:18-25)"""
+    r = be.transfer_left(None, v.reshape(1, *v.shape), A, Ab, cplx=True)
+    return r.reshape(r.shape[1], r.shape[2])
+
+
+def _bond_tr(be, v: DTensor, A: DTensor, Ab: DTensor):
+    """v'[a, p] = sum A[a, s, b] v[b, q] conj(Ab[p, s, q])"""
+    r = be.transfer_right(None, v.reshape(1, *v.shape), A, Ab, cplx=True)
+    return r.reshape(r.shape[1], r.shape[2])
+
+
+def _gauge_change(be, new: DTensor, old: DTensor):
+    """|new - old| of two bond matrices"""
+    if hasattr(be, "vdiff_nrm2"):
+        return float(np.sqrt(max(be.vdiff_nrm2(new, old)[0], 0.0)))
+    return be.norm(be.axpby(-1.0, old, 1.0, be.copy(new)))
+
+
+def uniform_leftorth(be, A, C0: DTensor, tol=1e-14, maxiter=100, eig_miniter=10):
+    """ortho.jl uniform_leftorth! on interleaved tensors: per site C A -> QRpos until |C0 - C1| < tol; from iteration
+    eig_miniter on the sweep starts from the leading eigenvector of flip(TransferMatrix(A, AL)).  Returns (AL, CR)."""
+    n = len(A)
+    c = be.copy(C0)
+    be.scal(1.0 / be.norm(c), c)
+    CR, AL = [None] * n, [None] * n
+    CR[n - 1] = c
+    eps, it = np.inf, 0
+    while True:
+        if it >= eig_miniter:
+            def tm(v):
+                for i in range(n):
+                    v = _bond_tl(be, v, A[i], AL[i])
+                return v
+            _, vec = _eig_lm_c(be, tm, CR[n - 1], max(eps * eps, tol / 10, 1e-15), maxiter=10)
+            _, CR[n - 1] = be.qrpos_c(vec)
+        C_old = CR[n - 1]
+        for i in range(n):
+            x = _mul_CA(be, CR[(i - 1) % n], A[i])
+            Dl2, d, Dr = x.shape
+            Q, R = be.qrpos_c(x.reshape(Dl2 * d, Dr))
+            AL[i], CR[i] = Q.reshape(Dl2, d, Dr), R
+        be.scal(1.0 / be.norm(CR[n - 1]), CR[n - 1])
+        eps = _gauge_change(be, CR[n - 1], C_old)
+        it += 1
+        if eps < tol or it > maxiter:
+            return AL, CR
+
+
+def uniform_rightorth(be, A, C0: DTensor, tol=1e-14, maxiter=100, eig_miniter=10):
+    """ortho.jl uniform_rightorth! on interleaved tensors: per site A C -> LQpos, right to left.  Returns (AR, CR)."""
+    n = len(A)
+    c = be.copy(C0)
+    be.scal(1.0 / be.norm(c), c)
+    CR, AR = [None] * n, [None] * n
+    CR[n - 1] = c
+    eps, it = np.inf, 0
+    while True:
+        if it >= eig_miniter:
+            def tm(v):
+                for i in range(n - 1, -1, -1):
+                    v = _bond_tr(be, v, A[i], AR[i])
+                return v
+            _, vec = _eig_lm_c(be, tm, CR[n - 1], max(eps * eps, tol / 10, 1e-15), maxiter=10)
+            CR[n - 1], _ = be.lqpos_c(vec)
+        C_old = CR[n - 1]
+        for i in range(n - 1, -1, -1):
+            x = _mul_AC(be, A[i], CR[i])
+            Dl2, d, Dr = x.shape
+            Lm, Q = be.lqpos_c(x.reshape(Dl2, d * Dr))
+            CR[(i - 1) % n], AR[i] = Lm, Q.reshape(Dl2, d, Dr)
+        be.scal(1.0 / be.norm(CR[n - 1]), CR[n - 1])
+        eps = _gauge_change(be, CR[n - 1], C_old)
+        it += 1
+        if eps < tol or it > maxiter:
+            return AR, CR
+
+
+class NativeInfiniteMPS:
+    """InfiniteMPS (infinitemps.jl:46-104) with interleaved complex128 tensors: AL, AR, AC [Dl, d, Dr] as (2 Dl, d, Dr) and CR
+    (bond right of site i) as (2 D, D), per site of a unit cell of any length.  |CR| = 1, AL CR = CR AR = AC."""
+
+    def __init__(self, tensors, be: Backend = None, tol=1e-14, maxiter=100):
+        from .backend import default_backend
+        be = self.be = default_backend() if be is None else be
+        A = [be.upload_c(np.asarray(t, dtype=np.complex128)) for t in tensors]
+        D = A[0].shape[0] // 2
+        if A[-1].shape[2] != D or any(A[i].shape[2] != A[i + 1].shape[0] // 2 for i in range(len(A) - 1)):
+            raise ValueError("the bond dimensions of the unit cell do not chain")
+        AL, CR = uniform_leftorth(be, A, be.upload_c(np.eye(D, dtype=np.complex128)), tol, maxiter)      # gaugefix! order :LR
+        self.AL = AL
+        self.AR, self.CR = uniform_rightorth(be, AL, CR[-1], tol, maxiter)
+        self.AC = [_mul_AC(be, self.AL[i], self.CR[i]) for i in range(len(A))]
+
+    @classmethod
+    def _of(cls, AL, AR, CR, AC, be):
+        out = object.__new__(cls)
+        out.AL, out.AR, out.CR, out.AC, out.be = list(AL), list(AR), list(CR), list(AC), be
+        return out
+
+    @classmethod
+    def random(cls, d, D, rng, n=1, be=None):
+        return cls([rng.standard_normal((D, d, D)) + 1j * rng.standard_normal((D, d, D)) for _ in range(n)], be=be)
+
+    @classmethod
+    def from_AL(cls, AL, C0: DTensor, tol=1e-14, maxiter=100, be=None):
+        """infinitemps.jl:172-186 (gaugefix! order = :R): AL are kept, AR / CR / AC follow from them."""
+        from .backend import default_backend
+        be = default_backend() if be is None else be
+        AR, CR = uniform_rightorth(be, AL, C0, tol, maxiter)
+        return cls._of(AL, AR, CR, [_mul_AC(be, AL[i], CR[i]) for i in range(len(AL))], be)
+
+    @classmethod
+    def from_real(cls, psi):
+        """an InfiniteMPS (real, or complex on the bond embedding of cplx.py) on interleaved storage, in the gauge it has"""
+        from .states import InfiniteMPS
+        if not isinstance(psi, InfiniteMPS):
+            raise TypeError(f"from_real takes an InfiniteMPS, not {type(psi).__name__}")
+        be = psi.be
+
+        def cv(t):
+            h = be.download(t)
+            if getattr(psi, "cplx", False):
+                from .cplx import extract
+                h = extract(h)
+            return be.upload_c(h)
+        return cls._of(*([cv(t) for t in ts] for ts in (psi.AL, psi.AR, psi.CR, psi.AC)), be)
+
+    def __len__(self):
+        return len(self.AL)
+
+    def dims(self, i):
+        Dl2, d, Dr = self.AL[i % len(self)].shape
+        return Dl2 // 2, d, Dr
+
+    def copy(self):
+        cp = lambda ts: [self.be.copy(t) for t in ts]
+        return NativeInfiniteMPS._of(cp(self.AL), cp(self.AR), cp(self.CR), cp(self.AC), self.be)
+
+    def to_host(self):
+        """{"AL", "AR", "AC", "CR"}: lists of complex arrays, one per site"""
+        return {k: [self.be.download_c(t) for t in getattr(self, k)] for k in ("AL", "AR", "AC", "CR")}
+
+    def bytes(self):
+        return 8 * sum(t.size for k in ("AL", "AR", "AC", "CR") for t in getattr(self, k))
+
+
+def as_complex_mpo(O):
+    """a SparseMPO in complex storage (the same operator; every slice an MPSK_C128 slice), a complex one as it is"""
+    from .operators import SparseMPO
+    if not isinstance(O, SparseMPO):
+        raise TypeError(f"as_complex_mpo takes a SparseMPO, not {type(O).__name__}")
+    if O.cplx:
+        return O
+    out = SparseMPO(O.data, O.d, be=O.be, chis=O.chis)
+    out.cplx = True                  # the slices are built on first use, as MPSK_C128 slices of the same blocks
+    return out
+
+
+def dC_proj_c_composed(be, GL: DTensor, GR: DTensor, c: DTensor):
+    """sum_w GL[w] c GR[w] on interleaved operands from plain complex products, one pair per slab, summed with axpby: the
+    route of backends without dC_proj_c (the pattern of statmech.dC_proj_composed)."""
+    W, Dlo2, Dl = GL.shape
+    _, Dr2, Dro = GR.shape
+    acc = None
+    for w in range(W):
+        gl = DTensor(GL.buf[w * Dlo2 * Dl:(w + 1) * Dlo2 * Dl], (Dlo2, Dl))
+        gr = DTensor(GR.buf[w * Dr2 * Dro:(w + 1) * Dr2 * Dro], (Dr2, Dro))
+        y = be.gemm_c(be.gemm_c(gl, c), gr)
+        acc = y if acc is None else be.axpby(1.0, y, 1.0, acc)
+    return acc
+
+
+# route of c_proj when the caller does not force one: the fused mpsk_dC_proj_c wherever the backend has it
+C_PROJ_FUSED_DEFAULT = True
+
+
+def _c_proj_route(be, device):
+    has = hasattr(be, "dC_proj_c")
+    if device and not has:
+        from ._lib import MpskError
+        raise MpskError("device=True: this backend has no dC_proj_c")
+    return (has and C_PROJ_FUSED_DEFAULT) if device is None else bool(device)
+
+
+class NativePerMPOInfEnv:
+    """environments(below, (O, above)) of permpoinfenv.jl:29-42 on interleaved storage: lw[i] (W, 2 D_below, D_above) and
+    rw[i] (W, 2 D_above, D_below), the left / right fixed points of the mixed transfer operators of <below| O |above> across
+    the unit cell.  O: a SparseMPO, complex (a real-time make_time_mpo) or real (its slices get complex twins); `above` is
+    fixed for the life of the object.  device: the route of c_proj (None: the default, True: mpsk_dC_proj_c, False: composed)."""
+
+    def __init__(self, below: NativeInfiniteMPS, toapprox, tol=1e-12, krylovdim=30, maxiter=100, rng=None, device=None):
+        from .operators import SparseMPO
+        if not (isinstance(toapprox, tuple) and len(toapprox) == 2):
+            raise TypeError("NativePerMPOInfEnv takes (below, (O, above))")
+        O, above = toapprox
+        _refuse_out_of_scope(O, above)
+        if not isinstance(O, SparseMPO):
+            raise TypeError(f"NativePerMPOInfEnv takes a SparseMPO, not {type(O).__name__}")
+        if not isinstance(above, NativeInfiniteMPS) or not isinstance(below, NativeInfiniteMPS):
+            raise TypeError("NativePerMPOInfEnv takes NativeInfiniteMPS states (NativeInfiniteMPS.from_real converts one)")
+        if len(above) != len(below):
+            raise ValueError(f"unit cells of the states above ({len(above)}) and below ({len(below)}) differ")
+        if len(below) % len(O) != 0:
+            raise ValueError(f"unit cell of the state ({len(below)}) is not a multiple of the MPO's ({len(O)})")
+        be = self.be = below.be
+        if O.be is None:
+            O.be = be
+        if O.be is not be:
+            raise ValueError("the SparseMPO and the state live on different backends")
+        self.opp, self.above, self.device = O, above, device
+        self.slices = list(O.slices) if O.cplx else [HalfEmbeddedOp._cslice(be, s) for s in O.slices]
+        self.tol, self.krylovdim, self.maxiter = tol, krylovdim, maxiter
+        self.rng = np.random.default_rng(0) if rng is None else rng
+        self.lw = self.rw = self.dependency = None
+        self.recalculate(below, tol)
+
+    def O(self, pos):
+        return self.slices[pos % len(self.slices)]
+
+    def _random(self, W, D1, D2):
+        z = self.rng.standard_normal((D1, W, D2)) + 1j * self.rng.standard_normal((D1, W, D2))
+        return self.be.upload_env_c([z])
+
+    def recalculate(self, psi: NativeInfiniteMPS, tol=None):
+        """permpoinfenv.jl recalculate!: restart from the previous fixed points when the bonds of the state below are
+        unchanged, from random start vectors otherwise."""
+        tol = self.tol if tol is None else tol
+        n, old, ab = len(psi), self.dependency, self.above
+        if len(ab) != n:
+            raise ValueError(f"unit cells of the states above ({len(ab)}) and below ({n}) differ")
+        if old is not None and len(old) == n and all(a.shape == b.shape for a, b in zip(old.CR, psi.CR)):
+            L0, R0 = self.be.copy(self.lw[0]), self.be.copy(self.rw[n - 1])
+        else:
+            L0 = self._random(self.O(0).Wl, psi.dims(0)[0], ab.dims(0)[0])
+            R0 = self._random(self.O(n - 1).Wr, ab.dims(n - 1)[2], psi.dims(n - 1)[2])
+        self.lw, self.rw = self._mixed_fixpoints(psi, L0, R0, tol)
+        self.dependency, self.tol = psi, tol
+        return self
+
+    def leftenv(self, pos, psi):
+        if self.dependency is not psi:
+            self.recalculate(psi)
+        return self.lw[pos % len(psi)]
+
+    def rightenv(self, pos, psi):
+        if self.dependency is not psi:
+            self.recalculate(psi)
+        return self.rw[pos % len(psi)]
+
+    def ac_proj(self, pos, below):
+        """ac_proj (derivatives.jl:216-219): mpsk_dAC_proj of above.AC[pos] on the environments of `below`"""
+        return self.be.dAC_proj(self.O(pos), self.leftenv(pos, below), self.rightenv(pos, below), self.above.AC[pos % len(below)])
+
+    def c_proj(self, pos, below):
+        """c_proj (derivatives.jl:204-207): mpsk_dC_proj_c of above.CR[pos] on the environments of `below`"""
+        return self._dC(self.leftenv(pos + 1, below), self.rightenv(pos, below), self.above.CR[pos % len(below)])
+
+    def _dC(self, GL, GR, c):
+        if _c_proj_route(self.be, self.device):
+            return self.be.dC_proj_c(GL, GR, c)
+        return dC_proj_c_composed(self.be, GL, GR, c)
+
+    def _mixed_fixpoints(self, psi, L0, R0, tol):  # permpoinfenv.jl:138-189 (one row)
+        be, n, top = self.be, len(psi), self.above
+
+        def tl(v):
+            for i in range(n):
+                v = be.transfer_left(self.O(i), v, top.AL[i], psi.AL[i])
+            return v
+
+        def tr(v):
+            for i in range(n - 1, -1, -1):
+                v = be.transfer_right(self.O(i), v, top.AR[i], psi.AR[i])
+            return v
+
+        _, gl = _eig_lm_c(be, tl, L0, tol, self.krylovdim, self.maxiter)
+        _, gr = _eig_lm_c(be, tr, R0, tol, self.krylovdim, self.maxiter)
+        GL, GR = [None] * n, [None] * n
+        GL[0], GR[n - 1] = gl, gr
+        for i in range(1, n):
+            GL[i] = be.transfer_left(self.O(i - 1), GL[i - 1], top.AL[i - 1], psi.AL[i - 1])
+        for i in range(n - 2, -1, -1):
+            GR[i] = be.transfer_right(self.O(i + 1), GR[i + 1], top.AR[i + 1], psi.AR[i + 1])
+        # |dot(CR_below, c_proj)| = 1 for every column (permpoinfenv.jl:178-185): both factors by 1 / sqrt|lambda|
+        for col in range(n):
+            lam = _dotc(be, psi.CR[col], self._dC(GL[(col + 1) % n], GR[col], top.CR[col]))
+            f = 1.0 / np.sqrt(abs(lam))
+            be.scal(f, GL[(col + 1) % n])
+            be.scal(f, GR[col])
+        return GL, GR
+
+
+def _refuse_out_of_scope(O, *states):
+    from .statmech import DenseMPO
+    from .multiline import MPSMultiline, MPOMultiline
+    if isinstance(O, DenseMPO):
+        raise NotImplementedError("DenseMPO targets are not implemented on NativeInfiniteMPS (SparseMPO only)")
+    if isinstance(O, MPOMultiline) or any(isinstance(s, MPSMultiline) for s in states):
+        raise NotImplementedError("MPSMultiline / MPOMultiline are not implemented on interleaved complex storage")
+
+
+def regauge(be, AC: DTensor, C: DTensor):
+    """regauge!(AC, C; alg = QRpos()) -> AL = Q_AC Q_C^dag   (ortho.jl:127-131) on interleaved tensors"""
+    Dl2, d, Dr = AC.shape
+    Qac, _ = be.qrpos_c(AC.reshape(Dl2 * d, Dr))
+    Qc, _ = be.qrpos_c(C)
+    return be.gemm_c(Qac, Qc, transB=True).reshape(Dl2, d, Dr)
+
+
+def calc_galerkin(psi: NativeInfiniteMPS, envs: NativePerMPOInfEnv):
+    """max over the unit cell of || (1 - AL AL^dag) normalize(ac_proj) ||  (toolbox.jl:26-38, environments with a state above)"""
+    be, out = psi.be, 0.0
+    for loc in range(len(psi)):
+        g = envs.ac_proj(loc, psi)
+        be.scal(1.0 / be.norm(g), g)
+        Dl2, d, Dr = psi.AL[loc].shape
+        alm, gm = psi.AL[loc].reshape(Dl2 * d, Dr), g.reshape(Dl2 * d, g.shape[2])
+        be.gemm_c(alm, be.gemm_c(alm, gm, transA=True), alpha=-1.0, beta=1.0, out=gm)
+        out = max(out, be.norm(gm))
+    return out
+
+
+def _approximate_inf(psi: NativeInfiniteMPS, toapprox, alg, envs=None, device=None):  # approximate/vomps.jl:1-80 (one row)
+    import time
+    from .algorithms import IDMRG1, IDMRG2, VOMPS, VUMPS, updatetol, _log
+    if isinstance(alg, (IDMRG1, IDMRG2)):
+        raise NotImplementedError(f"approximate on a NativeInfiniteMPS: {type(alg).__name__} is not implemented (VOMPS only)")
+    if isinstance(alg, VUMPS):           # vomps.jl:12-17
+        alg = VOMPS(tol=alg.tol, maxiter=alg.maxiter, finalize=alg.finalize, verbosity=alg.verbosity,
+                    gauge_tol_min=alg.gauge_tol_min, gauge_tol_max=alg.gauge_tol_max, gauge_tol_factor=alg.gauge_tol_factor,
+                    env_tol_min=alg.env_tol_min, env_tol_max=alg.env_tol_max, env_tol_factor=alg.env_tol_factor)
+    if not isinstance(alg, VOMPS):
+        raise TypeError(f"approximate on a NativeInfiniteMPS takes VOMPS (or VUMPS), not {type(alg).__name__}")
+    be, n = psi.be, len(psi)
+    envs = NativePerMPOInfEnv(psi, toapprox, device=device) if envs is None else envs
+    eps = calc_galerkin(psi, envs)
+    t0, history = time.time(), []
+    for it in range(1, alg.maxiter + 1):
+        newAL = [regauge(be, envs.ac_proj(loc, psi), envs.c_proj(loc, psi)) for loc in range(n)]
+        gtol = updatetol(alg.gauge_tol_min, alg.gauge_tol_max, alg.gauge_tol_factor, it, eps)
+        psi = NativeInfiniteMPS.from_AL(newAL, psi.CR[n - 1], tol=gtol, be=be)
+        envs.recalculate(psi, updatetol(alg.env_tol_min, alg.env_tol_max, alg.env_tol_factor, it, eps))
+        if alg.finalize is not None:
+            psi, envs = alg.finalize(it, psi, toapprox, envs)
+        eps = calc_galerkin(psi, envs)
+        history.append((it, eps))
+        _log(alg, "VOMPS (interleaved complex)", it, float("nan"), eps, t0)
+        if eps <= alg.tol:
+            break
+    envs.history = history
+    return psi, envs, eps
+
+
+def dot(psi1, psi2, krylovdim=30, tol=1e-12, rng=None):
+    """dot(psi1, psi2) of two NativeInfiniteMPS (infinitemps.jl:258-264): the leading (:LM) eigenvalue of the mixed pass-through
+    transfer TransferMatrix(psi2.AL, psi1.AL) of one unit cell, complex.  Two NativeFiniteMPS: linalg.dot."""
+    if isinstance(psi1, NativeFiniteMPS) and isinstance(psi2, NativeFiniteMPS):
+        from . import linalg
+        return linalg.dot(psi1, psi2)
+    if not (isinstance(psi1, NativeInfiniteMPS) and isinstance(psi2, NativeInfiniteMPS)):
+        raise TypeError("native_cplx.dot takes two NativeInfiniteMPS or two NativeFiniteMPS")
+    if len(psi1) != len(psi2):
+        raise ValueError("dot: the unit cells do not match")
+    be, n = psi1.be, len(psi1)
+    rng = np.random.default_rng(0) if rng is None else rng
+    Db, Dk = psi1.dims(0)[0], psi2.dims(0)[0]
+    v0 = be.upload_c(rng.standard_normal((Db, Dk)) + 1j * rng.standard_normal((Db, Dk)))
+
+    def tl(v):
+        for i in range(n):
+            v = _bond_tl(be, v, psi2.AL[i], psi1.AL[i])
+        return v
+
+    val, _ = _eig_lm_c(be, tl, v0, tol, krylovdim, 100)
+    return val
+
+
+def _expval_inf(psi: NativeInfiniteMPS, O):
+    """<O_i> of every site of the unit cell for a [d, d] operator or a list of one per site: one mpsk_site_gram(AC_i, AC_i)
+    under MPSK_C128 per site (expval.jl:23-37)"""
+    be, n = psi.be, len(psi)
+    ops = [np.asarray(O)] * n if np.asarray(O[0]).ndim == 1 else [np.asarray(o) for o in O]
+    if len(ops) != n:
+        raise ValueError(f"{len(ops)} operators for a unit cell of {n} sites")
+    out = np.zeros(n, dtype=np.complex128)
+    for i in range(n):
+        d = psi.AC[i].shape[1]
+        rho = be.download_c(be.site_gram(psi.AC[i], psi.AC[i], cplx=True).reshape(2 * d, d))     # rho[t, s]
+        out[i] = np.sum(ops[i] * rho)
+    return out

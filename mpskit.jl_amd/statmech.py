@@ -308,7 +308,9 @@ def leading_boundary(psi, mpo: DenseMPO, alg=None, envs=None):
     (statmech/vomps.jl:27-87), ONE application of H_AC / H_C per site in place of the eigensolves.  An MPSMultiline with an
     MPOMultiline: multiline.leading_boundary."""
     from .algorithms import VOMPS, VUMPS, updatetol, regauge, _log
-    from . import multiline
+    from . import multiline, native_cplx
+    if isinstance(psi, native_cplx.NativeInfiniteMPS):
+        raise NotImplementedError("leading_boundary is not implemented for NativeInfiniteMPS (interleaved complex storage)")
     if isinstance(psi, multiline.MPSMultiline):
         return multiline.leading_boundary(psi, mpo, alg, envs)
     alg = VUMPS() if alg is None else alg
@@ -358,9 +360,11 @@ def dot(a, b, c=None, krylovdim=30, tol=1e-12, rng=None):
     from . import window
     if isinstance(a, window.WindowMPS) and c is None:                       # windowmps.jl:165-176
         return window.dot(a, b)
-    from . import linalg
+    from . import linalg, native_cplx
     if c is None and any(isinstance(a, t) and isinstance(b, t) for t in (linalg.FiniteMPS, linalg.NativeFiniteMPS)):
         return linalg.dot(a, b)                                             # finitemps.jl:459-464
+    if c is None and isinstance(a, native_cplx.NativeInfiniteMPS) and isinstance(b, native_cplx.NativeInfiniteMPS):
+        return native_cplx.dot(a, b, krylovdim=krylovdim, tol=tol, rng=rng)
     mpo, ket = (None, b) if c is None else (b, c)
     bra = a
     if not isinstance(bra, InfiniteMPS) or not isinstance(ket, InfiniteMPS):
