@@ -56,7 +56,8 @@
  *    The remaining entry points (mpsk_qrpos2, mpsk_qrlq_pair, Krylov vector helpers, mpsk_regularize) are fp64 only and
  *    ignore the ctx dtype: a complex host runs its vector arithmetic on the 2n doubles of an interleaved vector (real
  *    inner products suffice for the Hermitian Lanczos solvers).  Solvers that need a Krylov space over the complex
- *    numbers (GMRES with a complex shift) use the mpsk_v*_c forms at the end of this header.
+ *    numbers (GMRES with a complex shift) use the mpsk_v*_c forms at the end of this header.  mpsk_regularize_axpby, the
+ *    regulariser of those solves on a uniform state, follows mpsk_ctx_set_dtype.
  */
 #ifndef MPSK_H
 #define MPSK_H
@@ -476,6 +477,20 @@ int mpsk_qp_heff_site(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dl, int DrL, in
 /* regularize!(v, lvec, rvec)   src/transfermatrix/transfermatrix.jl:70-76
  *   v[w] -= <lvec^T, v[w]> * rvec  for each of the W slabs [D1, D2]; lvec: [D2, D1]; rvec: [D1, D2] */
 int mpsk_regularize(mpsk_ctx* ctx, int W, int D1, int D2, void* v, const void* lvec, const void* rvec);
+/* The regulariser fused with the sum a GMRES step on (1 - T_reg) needs (mpohaminfenv.jl:95, :146), for both dtypes:
+ *   coef_w = sum_{p,q} lvec[q,p] y[w][p,q]             (bilinear: NO conjugate, transfermatrix.jl:70-76)
+ *   out[w] = a0 x[w] + a1 (y[w] - coef_w rvec)          w = 0 .. W-1
+ * y, x, out: W slabs [D1, D2]; lvec: [D2, D1]; rvec: [D1, D2]; column-major.  Follows mpsk_ctx_set_dtype: under MPSK_C128
+ * every array is interleaved complex and coef_w is a complex number; a0 and a1 stay real doubles (the solve needs 1 and -1).
+ * x == NULL drops the a0 x term (a0 is not read).  out may alias y or x.  With x == NULL, a1 = 1 and out == y this is
+ * regularize! in place: the complex twin of mpsk_regularize.
+ * Two launches on the ctx stream, asynchronous, no atomics, nothing written to the host: a tiled dot (the lvec tile is
+ * transposed through LDS so that both reads coalesce) whose per-tile partials go to the ctx workspace, one (re, im) pair per
+ * tile for complex operands; then one pass in which every workgroup sums the partials of its slab in the same fixed order
+ * and writes its part of out.  Bit-identical from run to run.  Workspace: W ceil(D1 / 32) ceil(D2 / 32) doubles, twice that
+ * for MPSK_C128.  MPSK_ERR_INVALID: a dimension < 1, W > 65535, NULL y / lvec / rvec / out. */
+int mpsk_regularize_axpby(mpsk_ctx* ctx, int W, int D1, int D2, const void* y, const void* lvec, const void* rvec, double a1,
+                          const void* x, double a0, void* out);
 
 /* ---- gauge steps: TensorKit leftorth!(QRpos) / rightorth!(LQpos) / tsvd! ----------------------
  * call sites: src/states/orthoview.jl:52,56 ; finitemps.jl:149 ; ortho.jl:128-136 ; dmrg.jl:96 */

@@ -301,6 +301,14 @@ function regularize!(v::ROCTensor{3}, lvec::ROCTensor{2}, rvec::ROCTensor{2})
         CTX[], v.dims[1], v.dims[2], v.dims[3], v.ptr, lvec.ptr, rvec.ptr))
     return v
 end
+"out[w] = a0 x[w] + a1 (y[w] - <lvec, y[w]> rvec): one GMRES step on (1 - T_reg); follows the ctx dtype (ComplexF64 slabs)"
+function regularize_axpby!(out::ROCTensor{3}, y::ROCTensor{3}, lvec::ROCTensor{2}, rvec::ROCTensor{2}, a1::Real,
+                           x::Union{ROCTensor{3},Nothing}, a0::Real)
+    check(ccall((:mpsk_regularize_axpby, libmpsk[]), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Ptr{Cvoid}, Cdouble, Ptr{Cvoid}),
+        CTX[], y.dims[1], y.dims[2], y.dims[3], y.ptr, lvec.ptr, rvec.ptr, a1, x === nothing ? C_NULL : x.ptr, a0, out.ptr))
+    return out
+end
 
 # ---- small gauge products  AC = AL*C, C*AR, theta = AC*AR  (orthoview.jl:99,103 ; dmrg.jl:92) ----
 # (complex operands: trans = adjoint, alpha real; mpsk_gemm follows the ctx dtype)

@@ -160,6 +160,9 @@ def calc_galerkin(psi, pos, envs=None, h=None, g=None):
     from . import window
     if isinstance(psi, window.WindowMPS):
         return window.calc_galerkin(psi, pos, envs)
+    from . import native_cplx
+    if isinstance(psi, native_cplx.NativeInfiniteMPS):      # calc_galerkin(psi, envs): the maximum over the unit cell
+        return native_cplx.calc_galerkin(psi, pos if envs is None else envs)
     if isinstance(pos, PerMPOInfEnv):
         return _galerkin_dense(psi, pos)
     if isinstance(envs, PerMPOInfEnv):
@@ -183,6 +186,9 @@ def expectation_value(psi, H, envs=None, *, device=None):
     from . import measure, window
     if isinstance(psi, window.WindowMPS):               # (vals, tot) for a Hamiltonian (expval.jl:76-87)
         return window.expectation_value(psi, H, envs, device=device)
+    from . import native_cplx
+    if isinstance(psi, native_cplx.NativeInfiniteMPS):  # complex values: local operators, or the energy per site
+        return native_cplx.expectation_value(psi, H, envs)
     if measure.is_local_operator(H, envs):
         return measure.expectation_value(psi, H, envs, device=device)
     from .statmech import DenseMPO, expectation_value as _expval_dense
@@ -275,6 +281,12 @@ def find_groundstate(psi, H, alg=None, envs=None, *, tol=None, maxiter=None, ver
         raise ValueError("find_groundstate needs a time-independent operator: evaluate the time-dependent one first, H(t)")
     if isinstance(psi, window.WindowMPS):
         return window.find_groundstate(psi, H, alg, envs, tol=tol, maxiter=maxiter, verbosity=verbosity, trscheme=trscheme)
+    from . import native_cplx
+    if isinstance(psi, native_cplx.NativeInfiniteMPS):      # interleaved complex uniform state: VUMPS (native_cplx._vumps_inf)
+        if not (tol is None and maxiter is None and verbosity is None and trscheme is None):
+            raise NotImplementedError("find_groundstate on a NativeInfiniteMPS: the keyword form builds GradientGrassmann / "
+                                      "IDMRG2 stages, which are not implemented there; pass VUMPS(...)")
+        return native_cplx.find_groundstate(psi, H, VUMPS() if alg is None else alg, envs)
     if alg is None:
         if tol is None and maxiter is None and verbosity is None and trscheme is None:
             alg = DMRG() if isinstance(psi, FiniteMPS) else VUMPS()
@@ -667,6 +679,9 @@ def timestep(psi, H, t, dt, alg=None, envs=None):
     from . import window
     if isinstance(psi, window.WindowMPS):
         return window.timestep(psi, H, t, dt, alg, envs)
+    from . import native_cplx
+    if isinstance(psi, native_cplx.NativeInfiniteMPS):
+        return native_cplx.timestep(psi, H, t, dt, alg, envs)
     if isinstance(psi, InfiniteMPS):
         envs = environments(psi, H) if envs is None else envs
         return _timestep_inf(psi, H, t, dt, alg, envs)

@@ -651,6 +651,25 @@ class Backend:
         check(self.lib.mpsk_regularize(self.ctx, W, D1, D2, v.ptr, lvec.ptr, rvec.ptr), "mpsk_regularize")
         return v
 
+    def regularize_axpby(self, y: DTensor, lvec: DTensor, rvec: DTensor, a1=1.0, x: DTensor = None, a0=0.0,
+                         out: DTensor = None, cplx=False):
+        """mpsk_regularize_axpby: out[w] = a0 x[w] + a1 (y[w] - <lvec^T, y[w]> rvec), bilinear, W slabs (W, D1, D2) -- cplx:
+        interleaved (W, 2 D1, D2).  x=None drops the a0 term; out may be y or x (default: a new tensor); asynchronous."""
+        m = 2 if cplx else 1
+        W, D1, D2 = y.shape[0], y.shape[1] // m, y.shape[2]
+        if lvec.size != m * D1 * D2 or rvec.size != m * D1 * D2 or (x is not None and x.size != y.size):
+            raise MpskError(f"regularize_axpby: lvec {lvec.shape} / rvec {rvec.shape} / x do not fit y {y.shape}")
+        o = self.empty(*y.shape) if out is None else out
+        if o.size != y.size:
+            raise MpskError(f"regularize_axpby: out {o.shape} does not fit y {y.shape}")
+        self._set_dtype(cplx)
+        try:
+            check(self.lib.mpsk_regularize_axpby(self.ctx, W, D1, D2, y.ptr, lvec.ptr, rvec.ptr, float(a1),
+                                                 None if x is None else x.ptr, float(a0), o.ptr), "mpsk_regularize_axpby")
+        finally:
+            self._set_dtype(False)
+        return o
+
     def gemm(self, A: DTensor, B: DTensor, transA=False, transB=False, alpha=1.0, beta=0.0, out: DTensor = None,
              m=None, n=None, k=None, lda=None, ldb=None, ldc=None):
         """C = alpha op(A) op(B) + beta C on 2-D column-major views (leading dims default to rows)."""

@@ -2056,6 +2056,21 @@ int mpsk_regularize(mpsk_ctx* c, int W, int D1, int D2, void* v, const void* lve
   HIPCHK(regularize(W, D1, D2, (double*)v, (const double*)lvec, (const double*)rvec, c->ws.d(), c->stream));
   return MPSK_OK;
 }
+
+int mpsk_regularize_axpby(mpsk_ctx* c, int W, int D1, int D2, const void* y, const void* lvec, const void* rvec, double a1,
+                          const void* x, double a0, void* out) {
+  REQUIRE(c && y && lvec && rvec && out, "NULL argument (only x may be NULL)");
+  REQUIRE(W > 0 && D1 > 0 && D2 > 0, "dimensions must be positive");
+  REQUIRE(W <= 65535, "at most 65535 slabs");
+  HIPCHK(hipSetDevice(c->device));
+  const bool cplx = c->dtype == MPSK_C128;
+  auto al16 = [](const void* p) { return (uintptr_t)p % 16 == 0; };     // the complex kernels move (re, im) pairs
+  REQUIRE(!cplx || (al16(y) && al16(lvec) && al16(rvec) && al16(out) && al16(x)), "complex operands must be 16-byte aligned");
+  if (int rc = ensure_ws(c, sizeof(double) * regularize_workspace_doubles(W, D1, D2) * (cplx ? 2 : 1))) return rc;
+  HIPCHK(regularize_axpby(cplx, W, D1, D2, (const double*)y, (const double*)lvec, (const double*)rvec, a1, (const double*)x,
+                          a0, (double*)out, c->ws.d(), c->stream));
+  return MPSK_OK;
+}
 }  // extern "C"
 
 // --------------------------------------------------------------------------------------------

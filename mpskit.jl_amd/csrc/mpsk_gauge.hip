@@ -13,6 +13,8 @@ namespace mpsk {
 // 1024 x 1024 slab -- the dominant cost of every GMRES step on the regularised transfer matrix).
 // Phase 2: every workgroup sums the tile partials of its slab in the same order (deterministic) and updates its chunk.
 constexpr int RG_T = 32;
+constexpr int RGA_MAX_BLOCKS = 1024, RGA_BLOCK_ELEMS = 2048;     // phase 2 of regularize_axpby: grid cap per slab, elements per
+                                                                 // workgroup below the cap (a grid-stride loop above it)
 __global__ __launch_bounds__(256) void regularize_dot_kernel(const double* __restrict__ v, const double* __restrict__ lvec,
                                                              double* __restrict__ partial, int D1, int D2, int tx_n) {
   __shared__ double tile[RG_T][RG_T + 1];
@@ -65,6 +67,114 @@ hipError_t regularize(int W, int D1, int D2, double* v, const double* lvec, cons
   int nb = (int)((n + 2047) / 2048);
   if (nb > 1024) nb = 1024;
   hipLaunchKernelGGL(regularize_apply_kernel, dim3(nb, W), dim3(256), 0, s, v, rvec, partial, ntiles, n);
+  return hipGetLastError();
+}
+
+// out[w] = a0 x[w] + a1 (y[w] - coef_w rvec),  coef_w = sum_{p,q} lvec[q, p] y_w[p, q]  (bilinear: nothing is conjugated).
+// One step of GMRES on the regularised transfer matrix of an identity level (1 - T_reg) x in two launches: the dot of
+// regularize_dot_kernel (fp64), or its interleaved complex twin below, which writes one (re, im) pair per tile; then one
+// pass in which every workgroup sums its slab's partials in the same order and writes its chunk of `out`.  y, x and out
+// carry no __restrict__: out may be y or x (the pass is elementwise and the coefficient is complete before it starts).
+__global__ __launch_bounds__(256) void regularize_dot_c128_kernel(const double2* __restrict__ v, const double2* __restrict__ lvec,
+                                                                  double2* __restrict__ partial, int D1, int D2, int tx_n) {
+  __shared__ double2 tile[RG_T][RG_T + 1];
+  __shared__ double2 sh[4];
+  const int t = blockIdx.x, w = blockIdx.y;
+  const int x0 = (t % tx_n) * RG_T, y0 = (t / tx_n) * RG_T;      // v[y, x], y in [0, D1), x in [0, D2); lvec[x, y] (D2 x D1)
+  const double2* vw = v + (int64_t)w * D1 * D2;
+  const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+  for (int r = r0; r < RG_T; r += 8) {                           // lvec tile: fast index x
+    const int x = x0 + c, y = y0 + r;
+    tile[r][c] = (x < D2 && y < D1) ? lvec[x + (int64_t)D2 * y] : make_double2(0.0, 0.0);
+  }
+  __syncthreads();
+  double re = 0.0, im = 0.0;
+  for (int r = r0; r < RG_T; r += 8) {                           // v tile: fast index y
+    const int y = y0 + c, x = x0 + r;
+    if (x < D2 && y < D1) {
+      const double2 l = tile[c][r], e = vw[y + (int64_t)D1 * x];
+      re += l.x * e.x - l.y * e.y;
+      im += l.x * e.y + l.y * e.x;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    re += __shfl_down(re, off, 64);
+    im += __shfl_down(im, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = make_double2(re, im);
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partial[(int64_t)w * gridDim.x + t] = make_double2((sh[0].x + sh[1].x) + (sh[2].x + sh[3].x),
+                                                       (sh[0].y + sh[1].y) + (sh[2].y + sh[3].y));
+}
+
+template <bool CPLX, bool HASX>
+__global__ __launch_bounds__(256) void regularize_axpby_kernel(const double* y, const double* __restrict__ rvec,
+                                                               const double* __restrict__ partial, int ntiles, int64_t n,
+                                                               double a1, const double* x, double a0, double* out) {
+  constexpr int C = CPLX ? 2 : 1;
+  __shared__ double sh[4][C];
+  __shared__ double coef[C];
+  const int w = blockIdx.y;
+  double acc[C];
+  for (int k = 0; k < C; ++k) acc[k] = 0.0;
+  for (int i = threadIdx.x; i < ntiles; i += 256)
+    for (int k = 0; k < C; ++k) acc[k] += partial[C * ((int64_t)w * ntiles + i) + k];
+  for (int k = 0; k < C; ++k) {
+    for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int k = 0; k < C; ++k) coef[k] = (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
+  __syncthreads();
+  const int64_t base = (int64_t)w * n;
+  if constexpr (CPLX) {
+    const double cr = coef[0], ci = coef[1];
+    const double2* yw = reinterpret_cast<const double2*>(y) + base;
+    const double2* xw = HASX ? reinterpret_cast<const double2*>(x) + base : nullptr;
+    const double2* rv = reinterpret_cast<const double2*>(rvec);
+    double2* ow = reinterpret_cast<double2*>(out) + base;
+    for (int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+      const double2 r = rv[e], yv = yw[e];
+      double2 o = make_double2(a1 * (yv.x - (cr * r.x - ci * r.y)), a1 * (yv.y - (cr * r.y + ci * r.x)));
+      if constexpr (HASX) {
+        const double2 xv = xw[e];
+        o.x += a0 * xv.x;
+        o.y += a0 * xv.y;
+      }
+      ow[e] = o;
+    }
+  } else {
+    const double cf = coef[0];
+    for (int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+      double o = a1 * (y[base + e] - cf * rvec[e]);
+      if constexpr (HASX) o += a0 * x[base + e];
+      out[base + e] = o;
+    }
+  }
+}
+
+hipError_t regularize_axpby(bool cplx, int W, int D1, int D2, const double* y, const double* lvec, const double* rvec, double a1,
+                            const double* x, double a0, double* out, double* partial, hipStream_t s) {
+  const int tx_n = (D2 + RG_T - 1) / RG_T, ty_n = (D1 + RG_T - 1) / RG_T, ntiles = tx_n * ty_n;
+  if (cplx)
+    hipLaunchKernelGGL(regularize_dot_c128_kernel, dim3(ntiles, W), dim3(256), 0, s, reinterpret_cast<const double2*>(y),
+                       reinterpret_cast<const double2*>(lvec), reinterpret_cast<double2*>(partial), D1, D2, tx_n);
+  else
+    hipLaunchKernelGGL(regularize_dot_kernel, dim3(ntiles, W), dim3(256), 0, s, y, lvec, partial, D1, D2, tx_n);
+  const int64_t n = (int64_t)D1 * D2;                             // elements of one slab (complex ones when cplx)
+  int nb = (int)((n + RGA_BLOCK_ELEMS - 1) / RGA_BLOCK_ELEMS);
+  if (nb > RGA_MAX_BLOCKS) nb = RGA_MAX_BLOCKS;
+  const dim3 grid(nb, W), block(256);
+  if (cplx && x)
+    hipLaunchKernelGGL((regularize_axpby_kernel<true, true>), grid, block, 0, s, y, rvec, partial, ntiles, n, a1, x, a0, out);
+  else if (cplx)
+    hipLaunchKernelGGL((regularize_axpby_kernel<true, false>), grid, block, 0, s, y, rvec, partial, ntiles, n, a1, x, 0.0, out);
+  else if (x)
+    hipLaunchKernelGGL((regularize_axpby_kernel<false, true>), grid, block, 0, s, y, rvec, partial, ntiles, n, a1, x, a0, out);
+  else
+    hipLaunchKernelGGL((regularize_axpby_kernel<false, false>), grid, block, 0, s, y, rvec, partial, ntiles, n, a1, x, 0.0, out);
   return hipGetLastError();
 }
 

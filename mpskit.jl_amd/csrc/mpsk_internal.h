@@ -238,6 +238,10 @@ hipError_t gram_env(int d, int Dlb, int Dr, int Drb, const double* T1, const dou
 // ---- gauge kernels ----------------------------------------------------------------------------
 size_t regularize_workspace_doubles(int W, int D1, int D2);
 hipError_t regularize(int W, int D1, int D2, double* v, const double* lvec, const double* rvec, double* partial, hipStream_t s);
+// out[w] = a0 x[w] + a1 (y[w] - <lvec^T, y[w]> rvec) (bilinear), two launches; x may be NULL (a0 unused); out may be y or x.
+// cplx: interleaved complex operands, `partial` then holds 2 * regularize_workspace_doubles(W, D1, D2) doubles.
+hipError_t regularize_axpby(bool cplx, int W, int D1, int D2, const double* y, const double* lvec, const double* rvec, double a1,
+                            const double* x, double a0, double* out, double* partial, hipStream_t s);
 hipError_t transpose(const double* in, int ldi, int rows, int cols, double* out, int ldo, hipStream_t s);
 size_t qrpos_workspace_doubles(int m, int n);
 int qrpos_max_rows();   // row limit of the blocked Householder route (one panel column in the LDS)

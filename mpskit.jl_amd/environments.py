@@ -200,6 +200,9 @@ def environments(psi, H, *args, **kw):
         return window.environments(psi, H, *args, **kw)
     if args:
         raise TypeError("environments(psi, H): start environments are taken for a WindowMPS only")
+    from . import native_cplx
+    if isinstance(psi, native_cplx.NativeInfiniteMPS):                         # interleaved complex uniform state
+        return native_cplx.environments(psi, H, **kw)
     if isinstance(H, MultipliedOperator):                                       # multipliedoperator.jl:50-52
         return environments(psi, H.op, **kw)
     if isinstance(psi, FiniteMPS) and isinstance(H, (tuple, FiniteMPS)):       # FinEnv.jl:21-23, :91-99

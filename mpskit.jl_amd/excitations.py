@@ -125,6 +125,9 @@ def excitations(H, alg, *args, **kw):
                             excitations(H::DenseMPO | MPOMultiline, alg, momentum | momenta | [LeftGaugedQP per row],
                                         psi::InfiniteMPS | MPSMultiline[, envs]; num, device)   :170-228"""
     from .quasiparticle import QuasiparticleAnsatz, LeftGaugedQP, excitations_qp, excitations_momenta
+    from . import native_cplx
+    if any(isinstance(a, native_cplx.NativeInfiniteMPS) for a in args):
+        raise NotImplementedError("excitations is not implemented for NativeInfiniteMPS (interleaved complex storage)")
     if isinstance(alg, FiniteExcited):
         return _excitations_finite_excited(H, alg, *args, **kw)
     if not isinstance(alg, QuasiparticleAnsatz):

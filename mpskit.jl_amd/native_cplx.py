@@ -170,6 +170,13 @@ class ComplexMPOHamiltonian:
     def __len__(self):
         return self.period
 
+    def isid(self, i):  # mpohamiltonian.jl:53-58
+        return all(s.isscal(i, i) and abs(s.blocks[(i, i)] - 1) < 1e-14 for s in self.slices)
+
+    def contains(self, site, i, j):
+        """whether block (i, j) of the slice of `site` is present; the block itself is self[site].blocks[(i, j)]"""
+        return self[site].contains(i, j)
+
 
 def _boundary(be, chis, D, active):
     """FinEnv.jl:49-67: identity on the active level, zeros elsewhere -- complex interleaved slabs (W, 2 D, D)."""
@@ -678,7 +685,13 @@ def approximate(psi0, toapprox, alg, envs=None, device=None):
 def find_groundstate(psi: NativeFiniteMPS, H, alg, envs: NativeFinEnv = None):
     """find_groundstate(psi, H, DMRG(...) | DMRG2(...))  (dmrg.jl:22-55, :80-137): sweeps until the energy moves by less than
     alg.tol (relative) or alg.maxiter is reached.  Returns (psi, envs, |dE| of the last sweep)."""
-    from .algorithms import DMRG, DMRG2
+    from .algorithms import DMRG, DMRG2, VUMPS
+    if isinstance(psi, NativeInfiniteMPS):       # find_groundstate(psi, H, VUMPS(...)) (vumps.jl:29-92): (psi, envs, galerkin)
+        _refuse_inf_alg(alg, "find_groundstate")
+        if not isinstance(alg, VUMPS):
+            raise TypeError(f"find_groundstate on a NativeInfiniteMPS takes VUMPS, not {type(alg).__name__}")
+        _refuse_ham(H)
+        return _vumps_inf(psi, H, alg, envs)
     envs = NativeFinEnv(psi, H) if envs is None else envs
     ws = krylov.KrylovWorkspace(psi.be)
     E_old, delta = np.inf, np.inf
@@ -715,6 +728,13 @@ def timestep(psi: NativeFiniteMPS, H, t, dt, alg, envs: NativeFinEnv = None):
     """timestep(psi, H, t, dt, TDVP() | TDVP2(...))  (tdvp.jl:61-94, :113-146).  H: an MPOHamiltonian, or a LazySum /
     MultipliedOperator of them, timed or not (environments: NativeMultipleEnv).  Returns (psi, envs)."""
     from .algorithms import TDVP, TDVP2
+    if isinstance(psi, NativeInfiniteMPS):       # tdvp.jl:21-59; the reference has no two-site scheme for a uniform state
+        if isinstance(alg, TDVP2):
+            raise NotImplementedError("timestep on a NativeInfiniteMPS: TDVP2 is not defined for a uniform state (TDVP only)")
+        if not isinstance(alg, TDVP):
+            raise TypeError(f"timestep on a NativeInfiniteMPS takes TDVP, not {type(alg).__name__}")
+        _refuse_ham(H)
+        return _timestep_inf(psi, H, t, dt, alg, envs)
     if envs is None:
         envs = NativeFinEnv(psi, H) if _sum_terms(H) is None else NativeMultipleEnv(psi, H)
     if isinstance(alg, TDVP2):
@@ -725,12 +745,17 @@ def timestep(psi: NativeFiniteMPS, H, t, dt, alg, envs: NativeFinEnv = None):
     raise TypeError(f"timestep on interleaved states takes TDVP or TDVP2, not {type(alg).__name__}")
 
 
-def expectation_value(psi: NativeFiniteMPS, O, device=None):
+def expectation_value(psi: NativeFiniteMPS, O, envs=None, device=None):
     """expectation_value(psi, O): <O_i> of every site for a [d,d] operator or a list of one per site (expval.jl:23-37), complex.
     One mpsk_site_gram(AC_i, AC_i) under MPSK_C128 per site, one download (measure.py).  The centre is moved on a copy: psi
     and the environments that follow its gauge stay as they are."""
     from . import measure
     if isinstance(psi, NativeInfiniteMPS):
+        from .operators import MPOHamiltonian
+        if isinstance(O, (MPOHamiltonian, ComplexMPOHamiltonian)) or isinstance(envs, NativeMPOHamInfEnv):
+            return _energy_inf(psi, O, envs)       # the energy per site of the unit cell (expval.jl:111-124), complex
+        if not isinstance(O, (np.ndarray, list, tuple)):
+            _refuse_ham(O)
         return _expval_inf(psi, O)
     return measure.expectation_value(psi.copy(), O, None, device=device)
 
@@ -1095,6 +1120,8 @@ def regauge(be, AC: DTensor, C: DTensor):
 
 def calc_galerkin(psi: NativeInfiniteMPS, envs: NativePerMPOInfEnv):
     """max over the unit cell of || (1 - AL AL^dag) normalize(ac_proj) ||  (toolbox.jl:26-38, environments with a state above)"""
+    if isinstance(envs, NativeMPOHamInfEnv):     # toolbox.jl:17-22 with the Hamiltonian's H_AC
+        return max(_galerkin_ham(psi, envs, loc) for loc in range(len(psi)))
     be, out = psi.be, 0.0
     for loc in range(len(psi)):
         g = envs.ac_proj(loc, psi)
@@ -1174,3 +1201,425 @@ def _expval_inf(psi: NativeInfiniteMPS, O):
         rho = be.download_c(be.site_gram(psi.AC[i], psi.AC[i], cplx=True).reshape(2 * d, d))     # rho[t, s]
         out[i] = np.sum(ops[i] * rho)
     return out
+
+
+# ---- Hamiltonian environments and the uniform drivers on interleaved storage (mpohaminfenv.jl, vumps.jl, tdvp.jl:21-59) ----
+
+# route of the regularised transfer matrix when the caller does not force one: mpsk_regularize_axpby wherever the backend has
+# it (profiles/native_ham_inf_timings.json, section "reg_op": the fused route is the faster one at D = 256 and D = 1024)
+REG_FUSED_DEFAULT = True
+
+
+def _reg_route(be, device):
+    has = hasattr(be, "regularize_axpby")
+    if device and not has:
+        from ._lib import MpskError
+        raise MpskError("device=True: this backend has no regularize_axpby")
+    return (has and REG_FUSED_DEFAULT) if device is None else bool(device)
+
+
+def _refuse_ham(H):
+    from .operators import LazySum, MultipliedOperator, MPOHamiltonian
+    from .statmech import DenseMPO
+    from .multiline import MPOMultiline
+    if isinstance(H, LazySum):
+        raise NotImplementedError("LazySum Hamiltonians are not implemented on NativeInfiniteMPS (NativeMPOHamInfEnv)")
+    if isinstance(H, MultipliedOperator):
+        raise NotImplementedError("MultipliedOperator / TimedOperator Hamiltonians are not implemented on NativeInfiniteMPS")
+    if isinstance(H, DenseMPO):
+        raise NotImplementedError("DenseMPO is not implemented on NativeInfiniteMPS (NativeMPOHamInfEnv takes an MPOHamiltonian)")
+    if isinstance(H, MPOMultiline):
+        raise NotImplementedError("MPOMultiline is not implemented on NativeInfiniteMPS")
+    if not isinstance(H, (MPOHamiltonian, ComplexMPOHamiltonian)):
+        raise TypeError(f"NativeMPOHamInfEnv takes an MPOHamiltonian or a ComplexMPOHamiltonian, not {type(H).__name__}")
+
+
+def _slab(t: DTensor, w):
+    """slab w of an environment (W, 2 D1, D2) as a (1, 2 D1, D2) view"""
+    n = t.shape[1] * t.shape[2]
+    return DTensor(t.buf[w * n:(w + 1) * n], (1, t.shape[1], t.shape[2]))
+
+
+class _RegOp:
+    """x -> x - regularize(T x) on interleaved slabs (transfermatrix.jl:29-33, :70-76), the operator of the GMRES solve of an
+    identity level: `cell` applies the n pass-through transfers, lvec / rvec are the two fixed points as mpsk_regularize_axpby
+    takes them.  fused: one regularize_axpby(y, lvec, rvec, a1=-1, x=x, a0=1, out=out); composed: conj(lvec^T) is uploaded
+    once, the coefficient of a slab is one dotc, the rank-one update and the sum are axpby_c."""
+
+    def __init__(self, be, cell, lvec, rvec, fused):
+        self.be, self.cell, self.lvec, self.rvec, self.fused = be, cell, lvec, rvec, fused
+        if not fused:
+            self.vs = krylov.ComplexVec(be)
+            self.u = be.upload_c(np.conj(be.download_c(lvec).T))
+
+    def project(self, v):
+        """regularize!(v, lvec, rvec) in place"""
+        be = self.be
+        if self.fused:
+            return be.regularize_axpby(v, self.lvec, self.rvec, out=v, cplx=True)
+        rv = self.rvec.reshape(1, *self.rvec.shape)
+        for w in range(v.shape[0]):
+            vw = _slab(v, w)
+            self.vs.axpby(-self.vs.dot(self.u.reshape(vw.shape), vw), rv, 1.0, vw)
+        return v
+
+    def __call__(self, x, out):
+        be = self.be
+        y = self.cell(x)
+        if self.fused:
+            return be.regularize_axpby(y, self.lvec, self.rvec, a1=-1.0, x=x, a0=1.0, out=out, cplx=True)
+        self.project(y)
+        self.vs.axpby(1.0, x, 0.0, out)
+        return self.vs.axpby(-1.0, y, 1.0, out)
+
+    def apply_axpby(self, a1, x, a0, out):          # krylov.linsolve: the operator itself is the shifted one (a0 = 0, a1 = 1)
+        assert a0 == 0 and a1 == 1
+        return self(x, out)
+
+
+class _PlainOp:
+    """x -> x - T x for a diagonal level that is not the identity (mpohaminfenv.jl:109-115)"""
+
+    def __init__(self, be, cell):
+        self.be, self.cell, self.vs = be, cell, krylov.ComplexVec(be)
+
+    def __call__(self, x, out):
+        y = self.cell(x)
+        self.vs.axpby(1.0, x, 0.0, out)
+        return self.vs.axpby(-1.0, y, 1.0, out)
+
+    def apply_axpby(self, a1, x, a0, out):
+        assert a0 == 0 and a1 == 1
+        return self(x, out)
+
+
+class NativeMPOHamInfEnv:
+    """environments(psi::NativeInfiniteMPS, H) of mpohaminfenv.jl:40-215 on interleaved storage: the counterpart of
+    environments.MPOHamInfEnv.  Level i of site s is its own (chi, 2 D, D) tensor of interleaved slabs, a site's environment for
+    the matvec kernels is assembled on demand and cached.  The triangular system is solved level by level; identity levels by
+    GMRES over the complex numbers (krylov.linsolve, cplx=True) on the regularised transfer matrix, whose application is the n
+    pass-through complex transfers and one mpsk_regularize_axpby.
+    H: a real MPOHamiltonian (its slices get complex twins) or a ComplexMPOHamiltonian whose period divides the unit cell.
+    device: the route of the regulariser (None: REG_FUSED_DEFAULT, True: mpsk_regularize_axpby, False: composed from
+    dotc / axpby_c)."""
+
+    def __init__(self, psi: NativeInfiniteMPS, H, tol=1e-12, maxiter=100, rng=None, device=None):
+        _refuse_ham(H)
+        if not isinstance(psi, NativeInfiniteMPS):
+            raise TypeError("NativeMPOHamInfEnv takes a NativeInfiniteMPS (NativeInfiniteMPS.from_real converts one)")
+        if len(psi) % H.period != 0:
+            raise ValueError(f"unit cell of the state ({len(psi)}) is not a multiple of the Hamiltonian's period ({H.period})")
+        be = self.be = psi.be
+        self.H, self.tol, self.maxiter, self.device = H, tol, maxiter, device
+        native = isinstance(H, ComplexMPOHamiltonian)
+        self.opp = [H[s] if native else HalfEmbeddedOp._cslice(be, H[s]) for s in range(H.period)]
+        self.rng = np.random.default_rng(0) if rng is None else rng
+        self.ws = krylov.KrylovWorkspace(be)
+        self._blk, self._col, self._eyes, self._cache = {}, {}, {}, {}
+        self.n_reg = 0                        # applications of the regularised operator (both routes), for inspection
+        self._start(psi)
+        self.recalculate(psi, tol)
+
+    def O(self, pos):
+        """the MPSK_C128 slice of site pos"""
+        return self.opp[pos % len(self.opp)]
+
+    def isid(self, i):
+        return all(s.isscal(i, i) and abs(s.blocks[(i, i)] - 1) < 1e-14 for s in self.opp)
+
+    def _start(self, psi):
+        """random start environments in the bond spaces of psi (mpohaminfenv.jl:40-44)"""
+        be, rng, n, odim = self.be, self.rng, len(psi), self.H.odim
+
+        def rand(chi, D):
+            return be.upload_env_c([np.transpose(rng.random((chi, D, D)), (1, 0, 2)).astype(np.complex128)])
+        self.lw = [[rand(self.O(s).chil[i], psi.dims(s)[0]) for s in range(n)] for i in range(odim)]
+        self.rw = [[rand(self.O(s).chir[i], psi.dims(s)[2]) for s in range(n)] for i in range(odim)]
+
+    # ---- public ----
+    def recalculate(self, psi: NativeInfiniteMPS, tol=None):
+        tol = self.tol if tol is None else tol
+        n = len(psi)
+        if n % len(self.opp) != 0:
+            raise ValueError(f"unit cell of the state ({n}) is not a multiple of the Hamiltonian's period ({len(self.opp)})")
+        if len(self.lw[0]) != n or any(self.lw[0][s].shape[2] != psi.dims(s)[0] or self.rw[0][s].shape[2] != psi.dims(s)[2]
+                                       for s in range(n)):
+            self._start(psi)                  # the bond spaces changed: the old solutions do not fit
+        self._calclw(psi, tol)
+        self._calcrw(psi, tol)
+        self.dependency, self.tol = psi, tol
+        self._cache = {}
+        return self
+
+    def _assemble(self, which, pos, n):
+        key = (which, pos % n)
+        if key not in self._cache:
+            src = self.lw if which == "l" else self.rw
+            parts = [src[i][pos % n] for i in range(self.H.odim)]
+            out = self.be.empty(sum(p.shape[0] for p in parts), parts[0].shape[1], parts[0].shape[2])
+            off = 0
+            for p in parts:
+                out.buf[off:off + p.size].copy_(p.buf[:p.size])
+                off += p.size
+            self._cache[key] = out
+        return self._cache[key]
+
+    def leftenv(self, pos, psi):
+        if self.dependency is not psi:
+            self.recalculate(psi)
+        return self._assemble("l", pos, len(psi))
+
+    def rightenv(self, pos, psi):
+        if self.dependency is not psi:
+            self.recalculate(psi)
+        return self._assemble("r", pos, len(psi))
+
+    def bytes(self):
+        return 8 * sum(t.size for lv in self.lw + self.rw for t in lv) + 8 * sum(t.size for t in self._cache.values())
+
+    # ---- helpers ----
+    def _scaled(self, z, t):
+        """z t for a complex number z (mpsk_vaxpby_c into a new tensor; never the real scal)"""
+        return krylov.ComplexVec(self.be).axpby(z, t, 0.0, self.be.empty(*t.shape))
+
+    def _level_slice(self, s, i, j):
+        key = (s % len(self.opp), i, j)
+        if key not in self._blk:
+            O = self.O(s).blocks[(i, j)]
+            self._blk[key] = self.be.mposlice(1, self.H.d, [O.shape[0]], [O.shape[3]], {(0, 0): O}, cplx=True)
+        return self._blk[key]
+
+    def _tl(self, v, s, i, j, A):
+        """the (i -> j) block of the left transfer through site s: a scalar block is the pass-through transfer times it"""
+        be, O = self.be, self.O(s).blocks[(i, j)]
+        if np.isscalar(O):
+            out = be.transfer_left(None, v, A, A, cplx=True)
+            return out if O == 1 else self._scaled(O, out)
+        return be.transfer_left(self._level_slice(s, i, j), v, A, A)
+
+    def _tr(self, v, s, i, j, A):
+        be, O = self.be, self.O(s).blocks[(i, j)]
+        if np.isscalar(O):
+            out = be.transfer_right(None, v, A, A, cplx=True)
+            return out if O == 1 else self._scaled(O, out)
+        return be.transfer_right(self._level_slice(s, i, j), v, A, A)
+
+    def _left_cycle(self, idx, psi):  # mpohaminfenv.jl:177-195
+        n, be = len(psi), self.be
+        for s in range(n):
+            acc = be.zeros(*self.lw[idx][(s + 1) % n].shape)
+            for j in range(idx, -1, -1):
+                if self.O(s).contains(j, idx):
+                    be.axpby(1.0, self._tl(self.lw[j][s], s, j, idx, psi.AL[s]), 1.0, acc)
+            self.lw[idx][(s + 1) % n] = acc
+
+    def _right_cycle(self, idx, psi):  # :197-215
+        n, be = len(psi), self.be
+        for s in range(n - 1, -1, -1):
+            acc = be.zeros(*self.rw[idx][(s - 1) % n].shape)
+            for j in range(idx, self.H.odim):
+                if self.O(s).contains(idx, j):
+                    be.axpby(1.0, self._tr(self.rw[j][s], s, idx, j, psi.AR[s]), 1.0, acc)
+            self.rw[idx][(s - 1) % n] = acc
+
+    def _CCd(self, psi, s):
+        """r_LL of the bond right of site s as mpsk_regularize_axpby reads it: lvec[ket, bra] = C C^dag"""
+        c = psi.CR[s % len(psi)]
+        return self.be.gemm_c(c, c, transB=True)
+
+    def _CdC(self, psi, s):
+        """l_RR of the bond left of site s: lvec[bra, ket] = C^dag C"""
+        c = psi.CR[(s - 1) % len(psi)]
+        return self.be.gemm_c(c, c, transA=True)
+
+    def _eye(self, D):
+        if D not in self._eyes:
+            self._eyes[D] = self.be.upload_c(np.eye(D, dtype=np.complex128))
+        return self._eyes[D]
+
+    def _identity_level(self, chi, D):
+        return self.be.upload_env_c([np.stack([np.eye(D, dtype=np.complex128)] * chi, axis=1)])
+
+    def _solve(self, op, b, x0, tol):
+        if self.be.norm(b) == 0:
+            return self.be.zeros(*b.shape)
+        x, info = krylov.linsolve(self.be, op, b, x0, a0=0.0, a1=1.0, tol=tol, maxiter=self.maxiter, ws=self.ws, cplx=True)
+        self.n_reg += info.numops
+        return x
+
+    def _calclw(self, psi, tol):  # mpohaminfenv.jl:76-123
+        n, odim, be = len(psi), self.H.odim, self.be
+        fused = _reg_route(be, self.device)
+        self.lw[0][0] = self._identity_level(self.O(0).chil[0], psi.dims(0)[0])
+        if n > 1:
+            self._left_cycle(0, psi)
+        for i in range(1, odim):
+            prev = self.lw[i][0]
+            self.lw[i][0] = be.zeros(*prev.shape)
+            self._left_cycle(i, psi)
+            if self.isid(i):
+                def cell(v):
+                    for s in range(n):
+                        v = be.transfer_left(None, v, psi.AL[s], psi.AL[s], cplx=True)
+                    return v
+                op = _RegOp(be, cell, self._CCd(psi, n - 1), self._eye(psi.dims(0)[0]), fused)
+                self.lw[i][0] = self._solve(op, self.lw[i][0], prev, tol)
+                if n > 1:
+                    self._left_cycle(i, psi)
+                for s in range(n):  # :103-107 subtract the fixed-point projection at every site
+                    _RegOp(be, None, self._CCd(psi, s - 1), self._eye(psi.dims(s)[0]), fused).project(self.lw[i][s])
+            else:
+                if all(self.O(s).contains(i, i) for s in range(n)):
+                    def cell(v, i=i):
+                        for s in range(n):
+                            v = self._tl(v, s, i, i, psi.AL[s])
+                        return v
+                    self.lw[i][0] = self._solve(_PlainOp(be, cell), self.lw[i][0], prev, tol)
+                if n > 1:
+                    self._left_cycle(i, psi)
+
+    def _calcrw(self, psi, tol):  # :125-175
+        n, odim, be = len(psi), self.H.odim, self.be
+        fused = _reg_route(be, self.device)
+        self.rw[odim - 1][n - 1] = self._identity_level(self.O(n - 1).chir[odim - 1], psi.dims(n - 1)[2])
+        if n > 1:
+            self._right_cycle(odim - 1, psi)
+        for i in range(odim - 2, -1, -1):
+            prev = self.rw[i][n - 1]
+            self.rw[i][n - 1] = be.zeros(*prev.shape)
+            self._right_cycle(i, psi)
+            if self.isid(i):
+                def cell(v):
+                    for s in range(n - 1, -1, -1):
+                        v = be.transfer_right(None, v, psi.AR[s], psi.AR[s], cplx=True)
+                    return v
+                op = _RegOp(be, cell, self._CdC(psi, 0), self._eye(psi.dims(n - 1)[2]), fused)
+                self.rw[i][n - 1] = self._solve(op, self.rw[i][n - 1], prev, tol)
+                if n > 1:
+                    self._right_cycle(i, psi)
+                for s in range(n):
+                    _RegOp(be, None, self._CdC(psi, s + 1), self._eye(psi.dims(s)[2]), fused).project(self.rw[i][s])
+            else:
+                if all(self.O(s).contains(i, i) for s in range(n)):
+                    def cell(v, i=i):
+                        for s in range(n - 1, -1, -1):
+                            v = self._tr(v, s, i, i, psi.AR[s])
+                        return v
+                    self.rw[i][n - 1] = self._solve(_PlainOp(be, cell), self.rw[i][n - 1], prev, tol)
+                if n > 1:
+                    self._right_cycle(i, psi)
+
+    # ---- the site operators (derivatives.jl:3-31, :77-93) ----
+    def hac(self, pos, psi):
+        """the prepared H_AC of site pos (mpsk_hac_create on the assembled environments, mode 2)"""
+        return self.be.hac_create(self.O(pos), self.leftenv(pos, psi), self.rightenv(pos, psi))
+
+    def hc(self, pos, psi):
+        """H_C of the bond right of site pos"""
+        be, GL, GR = self.be, self.leftenv(pos + 1, psi), self.rightenv(pos, psi)
+        return lambda x, out=None: be.dC(GL, GR, x, out=out, cplx=True)
+
+
+def environments(psi: NativeInfiniteMPS, H, **kw):
+    """environments(psi, H): NativeMPOHamInfEnv for a Hamiltonian, NativePerMPOInfEnv for H = (O, above)"""
+    if isinstance(H, tuple):
+        return NativePerMPOInfEnv(psi, H, **kw)
+    return NativeMPOHamInfEnv(psi, H, **kw)
+
+
+def _galerkin_ham(psi: NativeInfiniteMPS, envs: NativeMPOHamInfEnv, loc):
+    """|| (1 - AL AL^dag) normalize(H_AC AC) || of one site (toolbox.jl:17-22)"""
+    be = psi.be
+    g = envs.hac(loc, psi).apply(psi.AC[loc])
+    be.scal(1.0 / be.norm(g), g)
+    Dl2, d, Dr = psi.AL[loc].shape
+    alm, gm = psi.AL[loc].reshape(Dl2 * d, Dr), g.reshape(Dl2 * d, g.shape[2])
+    be.gemm_c(alm, be.gemm_c(alm, gm, transA=True), alpha=-1.0, beta=1.0, out=gm)
+    return be.norm(gm)
+
+
+def _energy_inf(psi: NativeInfiniteMPS, H, envs: NativeMPOHamInfEnv = None):
+    """energy per site of the unit cell (expval.jl:111-124), complex: the last column of the site slice applied to the assembled
+    left environment through AC, traced over the bond -- one transfer and one dotc per site, on the device."""
+    envs = NativeMPOHamInfEnv(psi, H) if envs is None else envs
+    be, n, odim = psi.be, len(psi), envs.H.odim
+    vs = krylov.ComplexVec(be)
+    ens = np.zeros(n, dtype=np.complex128)
+    for i in range(n):
+        O, key = envs.O(i), i % len(envs.opp)
+        if key not in envs._col:
+            col = {(j, 0): O.blocks[(j, odim - 1)] for j in range(odim) if O.contains(j, odim - 1)}
+            envs._col[key] = be.mposlice(odim, envs.H.d, O.chil, [O.chir[odim - 1]] + [1] * (odim - 1), col, cplx=True)
+        apl = be.transfer_left(envs._col[key], envs.leftenv(i, psi), psi.AC[i], psi.AC[i])
+        first = DTensor(apl.buf[:apl.shape[1] * apl.shape[2]], (apl.shape[1], apl.shape[2]))      # slab 0: [bra, ket]
+        ens[i] = vs.dot(envs._eye(first.shape[1]), first)
+    return ens
+
+
+def _vumps_inf(psi: NativeInfiniteMPS, H, alg, envs=None, device=None):  # vumps.jl:29-92
+    import time
+    from .algorithms import updatetol, _log
+    be, n = psi.be, len(psi)
+    envs = NativeMPOHamInfEnv(psi, H, device=device) if envs is None else envs
+    galerkin = lambda p: max(_galerkin_ham(p, envs, loc) for loc in range(n))
+    eps = galerkin(psi)
+    ws = krylov.KrylovWorkspace(be)
+    t0, history = time.time(), []
+    for it in range(1, alg.maxiter + 1):
+        etol = updatetol(alg.eig_tol_min, alg.eig_tol_max, alg.eig_tol_factor, it, eps)
+        newAL = []
+        for loc in range(n):
+            _, AC, _, _ = krylov.eigsolve_sr(be, envs.hac(loc, psi).apply, psi.AC[loc], tol=etol, krylovdim=alg.krylovdim, ws=ws)
+            _, C, _, _ = krylov.eigsolve_sr(be, envs.hc(loc, psi), psi.CR[loc], tol=etol, krylovdim=alg.krylovdim, ws=ws)
+            newAL.append(regauge(be, AC, C))
+        gtol = updatetol(alg.gauge_tol_min, alg.gauge_tol_max, alg.gauge_tol_factor, it, eps)
+        psi = NativeInfiniteMPS.from_AL(newAL, psi.CR[n - 1], tol=gtol, be=be)
+        envs.recalculate(psi, updatetol(alg.env_tol_min, alg.env_tol_max, alg.env_tol_factor, it, eps))
+        if alg.finalize is not None:
+            psi, envs = alg.finalize(it, psi, H, envs)
+        eps = galerkin(psi)
+        if alg.verbosity >= 3 or eps <= alg.tol or it == alg.maxiter:
+            E = float(np.sum(_energy_inf(psi, H, envs)).real)
+            history.append((it, E, eps))
+            _log(alg, "VUMPS (interleaved complex)", it, E, eps, t0)
+        if eps <= alg.tol:
+            break
+    envs.history = history
+    return psi, envs, eps
+
+
+def _timestep_inf(psi: NativeInfiniteMPS, H, t, dt, alg, envs=None, device=None):  # tdvp.jl:21-59 (leftorthflag = true)
+    from .algorithms import _integrate_embedded
+    be, n = psi.be, len(psi)
+    envs = NativeMPOHamInfEnv(psi, H, device=device) if envs is None else envs
+    ws = krylov.KrylovWorkspace(be)
+    z = -1j * complex(dt)
+    newAL = []
+    for loc in range(n):
+        h = envs.hac(loc, psi)
+        ac = _integrate_embedded(be, lambda x, out=None: h.apply(x, out=out), psi.AC[loc], z, alg, ws)
+        c = _integrate_embedded(be, envs.hc(loc, psi), psi.CR[loc], z, alg, ws)
+        newAL.append(regauge(be, ac, c))
+    psi2 = NativeInfiniteMPS.from_AL(newAL, psi.CR[n - 1], tol=alg.tolgauge, maxiter=alg.gaugemaxiter, be=be)
+    envs.recalculate(psi2)
+    return psi2, envs
+
+
+def time_evolve(psi, H, t_span, alg=None, envs=None):
+    """time_evolve(psi, H, t_span, TDVP())  (time_evolve.jl:20-40) on interleaved states: consecutive timesteps"""
+    from .algorithms import TDVP
+    alg = TDVP() if alg is None else alg
+    for t0, t1 in zip(t_span[:-1], t_span[1:]):
+        psi, envs = timestep(psi, H, t0, t1 - t0, alg, envs)
+        if alg.finalize is not None:
+            psi, envs = alg.finalize(t0, psi, H, envs)
+    return psi, envs
+
+
+def _refuse_inf_alg(alg, what):
+    from .algorithms import GradientGrassmann, IDMRG1, IDMRG2, UnionAlg
+    if isinstance(alg, UnionAlg):
+        _refuse_inf_alg(alg.alg1, what)
+        _refuse_inf_alg(alg.alg2, what)
+    if isinstance(alg, (GradientGrassmann, IDMRG1, IDMRG2)):
+        raise NotImplementedError(f"{what} on a NativeInfiniteMPS: {type(alg).__name__} is not implemented (VUMPS only)")
