@@ -179,7 +179,10 @@ int mpsk_dAC_blocked(mpsk_ctx* ctx, const mpsk_mposlice* H, int nblk, int Dlo, i
  * TWO GEMM launches with no slab mix and one intermediate instead of two; otherwise it applies exactly what mpsk_dAC
  * does.  GL / GR must stay valid and unchanged while the object lives.  x may be in the blocked layout (nblk row
  * blocks, see mpsk_dAC_blocked; nblk = 1: plain).  mpsk_hac_info: mode 1 = combined environment (nslabs of them);
- * mode 4 = dense-slice GEMM route (mpsk_mposlice_create_dense). */
+ * mode 4 = dense-slice GEMM route (mpsk_mposlice_create_dense).
+ * The blocked layout (nblk > 1) is taken by MPSK_F64 operators in modes 0, 1 and 4; nblk must divide Dl and be at most 32
+ * (MPSK_ERR_INVALID otherwise).  MPSK_C128 operators (mode 2, complex mode 3) and the real mode 3 take the plain layout only:
+ * nblk > 1 returns MPSK_ERR_UNSUPPORTED and launches nothing. */
 typedef struct mpsk_hac mpsk_hac;
 int mpsk_hac_create(mpsk_ctx* ctx, const mpsk_mposlice* H, int Dlo, int Dl, int Dr, const void* GL, const void* GR,
                     mpsk_hac** out);
