@@ -507,37 +507,69 @@ def regauge(be, AC: DTensor, C: DTensor, cplx=False):
     return be.gemm(Qac, Qc, transB=True).reshape(Dl, d, Dr)
 
 
+# What the two uniform loops below ask of the state's storage.  An InfiniteMPS (real, or complex on the bond embedding) gets the
+# functions of this block; a NativeInfiniteMPS gets the functions of the same names in native_cplx.py (_storage).
+
+VUMPS_LABEL = "VUMPS"
+
+
+def _groundstate_AL(psi, H, envs, loc, tol, krylovdim, ws):
+    """AL of site loc from the lowest eigenvectors of H_AC and H_C, solved to `tol` (vumps.jl:46-60)"""
+    be, eig = psi.be, Arnoldi(tol=tol, krylovdim=krylovdim)
+    _, AC = fixedpoint(be, ddAC(loc, psi, H, envs), psi.AC[loc], eig, ws)
+    _, C = fixedpoint(be, ddC(loc, psi, H, envs), psi.CR[loc], eig, ws)
+    return regauge(be, AC, C, getattr(psi, "cplx", False))
+
+
+def _evolved_AL(psi, H, envs, loc, t, dt, alg, ws):
+    """AL of site loc from AC and C evolved over dt (tdvp.jl:27-45)"""
+    be = psi.be
+    ac = integrate(be, ddAC(loc, psi, H, envs), psi.AC[loc], t, dt, alg, ws)
+    c = integrate(be, ddC(loc, psi, H, envs), psi.CR[loc], t, dt, alg, ws)
+    return regauge(be, ac, c, getattr(psi, "cplx", False))
+
+
+def _from_AL(psi, AL, **kw):
+    return InfiniteMPS.from_AL(AL, psi.CR[len(psi) - 1], be=psi.be, cplx=getattr(psi, "cplx", False), **kw)
+
+
 def _calc_galerkin_inf(psi, envs):
     return max(calc_galerkin(psi, loc, envs) for loc in range(len(psi)))
 
 
+def _energy_sum(psi, H, envs):
+    return float(np.sum(expectation_value(psi, H, envs)))
+
+
+def _storage(psi):
+    """the module whose _groundstate_AL, _evolved_AL, _from_AL, _calc_galerkin_inf, _energy_sum and VUMPS_LABEL serve psi"""
+    import sys
+    from . import native_cplx
+    return native_cplx if isinstance(psi, native_cplx.NativeInfiniteMPS) else sys.modules[__name__]
+
+
 def _vumps(psi, H, alg: VUMPS, envs=None):  # vumps.jl:29-92
-    be = psi.be
+    on = _storage(psi)
     envs = environments(psi, H) if envs is None else envs
-    eps = _calc_galerkin_inf(psi, envs)
+    eps = on._calc_galerkin_inf(psi, envs)
     n = len(psi)
-    ws = krylov.KrylovWorkspace(be)
+    ws = krylov.KrylovWorkspace(psi.be)
     t0 = time.time()
     history = []
     for it in range(1, alg.maxiter + 1):
-        eig = Arnoldi(tol=updatetol(alg.eig_tol_min, alg.eig_tol_max, alg.eig_tol_factor, it, eps),
-                      krylovdim=alg.krylovdim)
-        newAL = []
-        for loc in range(n):
-            _, AC = fixedpoint(be, ddAC(loc, psi, H, envs), psi.AC[loc], eig, ws)
-            _, C = fixedpoint(be, ddC(loc, psi, H, envs), psi.CR[loc], eig, ws)
-            newAL.append(regauge(be, AC, C, getattr(psi, "cplx", False)))
+        eigtol = updatetol(alg.eig_tol_min, alg.eig_tol_max, alg.eig_tol_factor, it, eps)
+        newAL = [on._groundstate_AL(psi, H, envs, loc, eigtol, alg.krylovdim, ws) for loc in range(n)]
         gtol = updatetol(alg.gauge_tol_min, alg.gauge_tol_max, alg.gauge_tol_factor, it, eps)
-        psi = InfiniteMPS.from_AL(newAL, psi.CR[n - 1], tol=gtol, be=be, cplx=getattr(psi, "cplx", False))
+        psi = on._from_AL(psi, newAL, tol=gtol)
         etol = updatetol(alg.env_tol_min, alg.env_tol_max, alg.env_tol_factor, it, eps)
         envs.recalculate(psi, etol)
         if alg.finalize is not None:
             psi, envs = alg.finalize(it, psi, H, envs)
-        eps = _calc_galerkin_inf(psi, envs)
+        eps = on._calc_galerkin_inf(psi, envs)
         if alg.verbosity >= 3 or eps <= alg.tol or it == alg.maxiter:
-            E = float(np.sum(expectation_value(psi, H, envs)))
+            E = on._energy_sum(psi, H, envs)
             history.append((it, E, eps))
-            _log(alg, "VUMPS", it, E, eps, t0)
+            _log(alg, on.VUMPS_LABEL, it, E, eps, t0)
         if eps <= alg.tol:
             break
     envs.history = history
@@ -660,15 +692,10 @@ def _timestep_tdvp2(psi, H, t, dt, alg: TDVP2, envs):  # tdvp.jl:113-146
 
 
 def _timestep_inf(psi, H, t, dt, alg: TDVP, envs):  # tdvp.jl:21-59 (leftorthflag = true)
-    be, n = psi.be, len(psi)
-    ws = krylov.KrylovWorkspace(be)
-    newAL = []
-    for loc in range(n):
-        ac = integrate(be, ddAC(loc, psi, H, envs), psi.AC[loc], t, dt, alg, ws)
-        c = integrate(be, ddC(loc, psi, H, envs), psi.CR[loc], t, dt, alg, ws)
-        newAL.append(regauge(be, ac, c, getattr(psi, "cplx", False)))
-    psi2 = InfiniteMPS.from_AL(newAL, psi.CR[n - 1], tol=alg.tolgauge, maxiter=alg.gaugemaxiter, be=be,
-                               cplx=getattr(psi, "cplx", False))
+    on = _storage(psi)
+    ws = krylov.KrylovWorkspace(psi.be)
+    newAL = [on._evolved_AL(psi, H, envs, loc, t, dt, alg, ws) for loc in range(len(psi))]
+    psi2 = on._from_AL(psi, newAL, tol=alg.tolgauge, maxiter=alg.gaugemaxiter)
     envs.recalculate(psi2)
     return psi2, envs
 

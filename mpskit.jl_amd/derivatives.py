@@ -181,6 +181,7 @@ def _timed_lazy(fn, pos, psi, H, envs):
     es = envs.envs
     make = wrap = None
     on = os.environ.get("MPSK_HSUM", "1") != "0"              # "0": always the composed route (A/B switch)
+    # `type(e) is`, not isinstance: native_cplx.NativeMPOHamInfEnv subclasses MPOHamInfEnv and must stay excluded here
     if (fn is ddAC and on and hasattr(be, "hsum_create") and len(es) <= 8
             and (all(type(e) is FinEnv for e in es) or all(type(e) is MPOHamInfEnv for e in es))):
         opps = [e.opp[pos] if hasattr(e, "opp") else h[pos] for h, e in zip(H, es)]

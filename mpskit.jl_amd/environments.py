@@ -227,7 +227,10 @@ class MPOHamInfEnv:
     """Infinite-MPS Hamiltonian environments: level-by-level triangular solve, GMRES on the
     regularised transfer matrix for identity levels (mpohaminfenv.jl:76-215).  Level i of site s is
     stored as its own (chi, D, D) device tensor; a site's full environment for the matvec kernels
-    is assembled (device-to-device) on demand."""
+    is assembled (device-to-device) on demand.
+    This class owns the algorithm: which level is zeroed, when a cycle runs, which bond's fixed point regularises which site.
+    The arithmetic sits in the methods under "leaves"; native_cplx.NativeMPOHamInfEnv overrides exactly those for interleaved
+    complex storage, level tensors (chi, 2 D, D)."""
 
     def __init__(self, psi, H, tol=1e-12, maxiter=100, rng=None):
         self.be = psi.be
@@ -240,23 +243,15 @@ class MPOHamInfEnv:
 
     def _start(self, psi):
         """random start environments in the bond spaces of psi (mpohaminfenv.jl:40-44)"""
-        be, H, rng = self.be, self.H, self.rng
-        n, odim = len(psi), H.odim
-        self.lw = [[be.upload(np.transpose(rng.random((H[s].chil[i], psi.AL[s].shape[0], psi.AL[s].shape[0])), (1, 2, 0)))
-                    for s in range(n)] for i in range(odim)]
-        self.rw = [[be.upload(np.transpose(rng.random((H[s].chir[i], psi.AR[s].shape[2], psi.AR[s].shape[2])), (1, 2, 0)))
-                    for s in range(n)] for i in range(odim)]
-        for i in range(odim):
-            for s in range(n):
-                self.lw[i][s] = DTensor(self.lw[i][s].buf, (H[s].chil[i],) + self.lw[i][s].shape[:2])
-                self.rw[i][s] = DTensor(self.rw[i][s].buf, (H[s].chir[i],) + self.rw[i][s].shape[:2])
+        n, odim = len(psi), self.H.odim
+        self._started = [self._bonds(psi, s) for s in range(n)]
+        self.lw = [[self._random_level(self.O(s).chil[i], self._started[s][0]) for s in range(n)] for i in range(odim)]
+        self.rw = [[self._random_level(self.O(s).chir[i], self._started[s][1]) for s in range(n)] for i in range(odim)]
 
     # ---- public ------------------------------------------------------------------------------
     def recalculate(self, psi, tol=None):
-        tol = self.tol if tol is None else tol
-        n = len(psi)
-        if len(self.lw[0]) != n or any(self.lw[0][s].shape[1] != psi.AL[s].shape[0] or
-                                       self.rw[0][s].shape[1] != psi.AR[s].shape[2] for s in range(n)):
+        tol = self._solve_tol(psi, tol)
+        if self._started != [self._bonds(psi, s) for s in range(len(psi))]:
             self._start(psi)                     # the bond spaces changed (changebonds): the old solutions do not fit
         self._calclw(psi, tol)
         self._calcrw(psi, tol)
@@ -288,51 +283,34 @@ class MPOHamInfEnv:
             self.recalculate(psi)
         return self._assemble("r", pos, len(psi))
 
-    # ---- helpers -------------------------------------------------------------------------------
-    def _tl(self, v, O, A):
-        """one (j -> idx) block of the left transfer: O scalar -> pass-through * O, dense -> MPO block."""
-        be = self.be
-        if np.isscalar(O):
-            out = be.transfer_left(None, v, A, A)
-            if O != 1:
-                be.scal(O, out)
-            return out
-        blk = be.mposlice(1, A.shape[1], [O.shape[0]], [O.shape[3]], {(0, 0): O})
-        return be.transfer_left(blk, v, A, A)
+    def bytes(self):
+        return 8 * sum(t.size for lv in self.lw + self.rw for t in lv) + 8 * sum(t.size for t in self._cache.values())
 
-    def _tr(self, v, O, A):
-        be = self.be
-        if np.isscalar(O):
-            out = be.transfer_right(None, v, A, A)
-            if O != 1:
-                be.scal(O, out)
-            return out
-        blk = be.mposlice(1, A.shape[1], [O.shape[0]], [O.shape[3]], {(0, 0): O})
-        return be.transfer_right(blk, v, A, A)
+    # ---- leaves: the arithmetic of real storage --------------------------------------------------
+    def O(self, s):
+        """the slice of site s"""
+        return self.H[s]
 
-    def _left_cycle(self, idx, psi):  # mpohaminfenv.jl:177-195
-        n, H, be = len(psi), self.H, self.be
-        for s in range(n):
-            tgt = self.lw[idx][(s + 1) % n]
-            acc = be.zeros(*tgt.shape)
-            for j in range(idx, -1, -1):
-                if not H[s].contains(j, idx):
-                    continue
-                t = self._tl(self.lw[j][s], H[s].blocks[(j, idx)], psi.AL[s])
-                be.axpby(1.0, t, 1.0, acc)
-            self.lw[idx][(s + 1) % n] = acc
+    def isid(self, i):
+        return self.H.isid(i)
 
-    def _right_cycle(self, idx, psi):  # :197-215
-        n, H, be = len(psi), self.H, self.be
-        for s in range(n - 1, -1, -1):
-            tgt = self.rw[idx][(s - 1) % n]
-            acc = be.zeros(*tgt.shape)
-            for j in range(idx, H.odim):
-                if not H[s].contains(idx, j):
-                    continue
-                t = self._tr(self.rw[j][s], H[s].blocks[(idx, j)], psi.AR[s])
-                be.axpby(1.0, t, 1.0, acc)
-            self.rw[idx][(s - 1) % n] = acc
+    def _bonds(self, psi, s):
+        """(left, right) bond dimension of site s"""
+        return psi.AL[s].shape[0], psi.AR[s].shape[2]
+
+    def _solve_tol(self, psi, tol):
+        """the tolerance of a recalculation that was asked for with `tol`: None is the constructor's"""
+        return self.tol if tol is None else tol
+
+    def _random_level(self, chi, D):
+        t = self.be.upload(np.transpose(self.rng.random((chi, D, D)), (1, 2, 0)))
+        return DTensor(t.buf, (chi, D, D))
+
+    def _identity_level(self, chi, D):
+        return DTensor(self.be.upload(np.transpose(np.stack([np.eye(D)] * chi), (1, 2, 0))).buf, (chi, D, D))
+
+    def _eye(self, D):
+        return self.be.upload(np.eye(D))
 
     def _CCd(self, psi, s):  # r_LL: C C^T of the bond right of site s
         c = psi.CR[s % len(psi)]
@@ -342,91 +320,128 @@ class MPOHamInfEnv:
         c = psi.CR[(s - 1) % len(psi)]
         return self.be.gemm(c, c, transA=True)
 
-    def _eye(self, D):
-        return self.be.upload(np.eye(D))
+    def _tl(self, v, s, i, j, A):
+        """the (i -> j) block of the left transfer through site s: O scalar -> pass-through * O, dense -> MPO block."""
+        be, O = self.be, self.O(s).blocks[(i, j)]
+        if np.isscalar(O):
+            out = be.transfer_left(None, v, A, A)
+            if O != 1:
+                be.scal(O, out)
+            return out
+        blk = be.mposlice(1, A.shape[1], [O.shape[0]], [O.shape[3]], {(0, 0): O})
+        return be.transfer_left(blk, v, A, A)
+
+    def _tr(self, v, s, i, j, A):
+        be, O = self.be, self.O(s).blocks[(i, j)]
+        if np.isscalar(O):
+            out = be.transfer_right(None, v, A, A)
+            if O != 1:
+                be.scal(O, out)
+            return out
+        blk = be.mposlice(1, A.shape[1], [O.shape[0]], [O.shape[3]], {(0, 0): O})
+        return be.transfer_right(blk, v, A, A)
+
+    def _solve_identity(self, cell, lvec, rvec, b, x0, tol):
+        """(1 - regularised T) x = b for an identity level: x -> x - [x T - <lvec, x T> rvec] with T = `cell`, one unit cell
+        of pass-through transfers (transfermatrix.jl:29-33, :70-76)"""
+        be = self.be
+
+        def op(x, out):
+            y = cell(x)
+            be.regularize(y, lvec, rvec)
+            be.axpby(1.0, x, 0.0, out)
+            be.axpby(-1.0, y, 1.0, out)
+            return out
+        return krylov.gmres(be, op, b, x0, tol=tol, maxiter=self.maxiter, ws=self.ws)
+
+    def _solve_plain(self, cell, b, x0, tol):
+        """(1 - T) x = b for a diagonal level that is not the identity (mpohaminfenv.jl:109-115)"""
+        be = self.be
+
+        def op(x, out):
+            y = cell(x)
+            be.axpby(1.0, x, 0.0, out)
+            be.axpby(-1.0, y, 1.0, out)
+            return out
+        return krylov.gmres(be, op, b, x0, tol=tol, maxiter=self.maxiter, ws=self.ws)
+
+    def project(self, v, lvec, rvec):
+        """regularize!(v, lvec, rvec) in place: v - <lvec, v> rvec, the contraction sum_xy lvec[x,y] v[y,x] per slab"""
+        return self.be.regularize(v, lvec, rvec)
+
+    # ---- the level solver: storage enters through the leaves above only (be.zeros / be.axpby serve either layout) ----
+    def _left_cycle(self, idx, psi):  # mpohaminfenv.jl:177-195
+        n, be = len(psi), self.be
+        for s in range(n):
+            acc = be.zeros(*self.lw[idx][(s + 1) % n].shape)
+            for j in range(idx, -1, -1):
+                if self.O(s).contains(j, idx):
+                    be.axpby(1.0, self._tl(self.lw[j][s], s, j, idx, psi.AL[s]), 1.0, acc)
+            self.lw[idx][(s + 1) % n] = acc
+
+    def _right_cycle(self, idx, psi):  # :197-215
+        n, be = len(psi), self.be
+        for s in range(n - 1, -1, -1):
+            acc = be.zeros(*self.rw[idx][(s - 1) % n].shape)
+            for j in range(idx, self.H.odim):
+                if self.O(s).contains(idx, j):
+                    be.axpby(1.0, self._tr(self.rw[j][s], s, idx, j, psi.AR[s]), 1.0, acc)
+            self.rw[idx][(s - 1) % n] = acc
 
     def _calclw(self, psi, tol):  # mpohaminfenv.jl:76-123
-        n, H, odim, be = len(psi), self.H, self.H.odim, self.be
-        D0 = psi.AL[0].shape[0]
-        chi0 = H[0].chil[0]
-        self.lw[0][0] = DTensor(be.upload(np.transpose(np.stack([np.eye(D0)] * chi0), (1, 2, 0))).buf, (chi0, D0, D0))
+        n, odim, be = len(psi), self.H.odim, self.be
+        D0 = self._bonds(psi, 0)[0]
+        self.lw[0][0] = self._identity_level(self.O(0).chil[0], D0)
         if n > 1:
             self._left_cycle(0, psi)
         for i in range(1, odim):
             prev = self.lw[i][0]
             self.lw[i][0] = be.zeros(*prev.shape)
             self._left_cycle(i, psi)
-            if H.isid(i):
-                # regularised transfer matrix  x -> x - [x T - <r, x T> l]   (transfermatrix.jl:29-33,70-76)
-                rfix = self._CCd(psi, n - 1)      # contracted with v:  sum_xy r[x,y] v[y,x]
-                lfix = self._eye(D0)
 
-                def op(x, out):
-                    y = x
-                    for s in range(n):
-                        y = be.transfer_left(None, y, psi.AL[s], psi.AL[s])
-                    be.regularize(y, rfix, lfix)
-                    be.axpby(1.0, x, 0.0, out)
-                    be.axpby(-1.0, y, 1.0, out)
-                    return out
-                self.lw[i][0] = krylov.gmres(be, op, self.lw[i][0], prev, tol=tol, maxiter=self.maxiter, ws=self.ws)
+            def cell(v, i=i):             # the diagonal block of level i through one unit cell; the bare transfer if it is 1
+                for s in range(n):
+                    v = self._tl(v, s, i, i, psi.AL[s])
+                return v
+            if self.isid(i):
+                # the fixed points of the regulariser: r_LL = C C^dag of the last bond, contracted with v, and the identity
+                lvec, rvec = self._CCd(psi, n - 1), self._eye(D0)
+                self.lw[i][0] = self._solve_identity(cell, lvec, rvec, self.lw[i][0], prev, tol)
                 if n > 1:
                     self._left_cycle(i, psi)
                 for s in range(n):  # :103-107 subtract the fixed-point projection at every site
-                    be.regularize(self.lw[i][s], self._CCd(psi, s - 1), self._eye(self.lw[i][s].shape[1]))
+                    self.project(self.lw[i][s], self._CCd(psi, s - 1), self._eye(self._bonds(psi, s)[0]))
             else:
-                if all(H[s].contains(i, i) for s in range(n)):
-                    def op(x, out):
-                        y = x
-                        for s in range(n):
-                            y = self._tl(y, H[s].blocks[(i, i)], psi.AL[s])
-                        be.axpby(1.0, x, 0.0, out)
-                        be.axpby(-1.0, y, 1.0, out)
-                        return out
-                    self.lw[i][0] = krylov.gmres(be, op, self.lw[i][0], prev, tol=tol, maxiter=self.maxiter, ws=self.ws)
+                if all(self.O(s).contains(i, i) for s in range(n)):
+                    self.lw[i][0] = self._solve_plain(cell, self.lw[i][0], prev, tol)
                 if n > 1:
                     self._left_cycle(i, psi)
 
     def _calcrw(self, psi, tol):  # :125-175
-        n, H, odim, be = len(psi), self.H, self.H.odim, self.be
-        DL = psi.AR[n - 1].shape[2]
-        chiL = H[n - 1].chir[odim - 1]
-        self.rw[odim - 1][n - 1] = DTensor(
-            be.upload(np.transpose(np.stack([np.eye(DL)] * chiL), (1, 2, 0))).buf, (chiL, DL, DL))
+        n, odim, be = len(psi), self.H.odim, self.be
+        DL = self._bonds(psi, n - 1)[1]
+        self.rw[odim - 1][n - 1] = self._identity_level(self.O(n - 1).chir[odim - 1], DL)
         if n > 1:
             self._right_cycle(odim - 1, psi)
         for i in range(odim - 2, -1, -1):
             prev = self.rw[i][n - 1]
             self.rw[i][n - 1] = be.zeros(*prev.shape)
             self._right_cycle(i, psi)
-            if H.isid(i):
-                # <l_RR, x> with l = C^T C of the bond left of site 0:  sum_xy l[x,y] x[x,y]
-                # mpsk_regularize contracts lvec[x,y] v[y,x] -> pass l^T (symmetric here)
-                lfix = self._CdC(psi, 0)
-                rfix = self._eye(DL)
 
-                def op(x, out):
-                    y = x
-                    for s in range(n - 1, -1, -1):
-                        y = be.transfer_right(None, y, psi.AR[s], psi.AR[s])
-                    be.regularize(y, lfix, rfix)
-                    be.axpby(1.0, x, 0.0, out)
-                    be.axpby(-1.0, y, 1.0, out)
-                    return out
-                self.rw[i][n - 1] = krylov.gmres(be, op, self.rw[i][n - 1], prev, tol=tol, maxiter=self.maxiter, ws=self.ws)
+            def cell(v, i=i):
+                for s in range(n - 1, -1, -1):
+                    v = self._tr(v, s, i, i, psi.AR[s])
+                return v
+            if self.isid(i):
+                # l_RR = C^dag C of the bond left of site 0 (as `project` contracts it: lvec[x,y] v[y,x]) and the identity
+                lvec, rvec = self._CdC(psi, 0), self._eye(DL)
+                self.rw[i][n - 1] = self._solve_identity(cell, lvec, rvec, self.rw[i][n - 1], prev, tol)
                 if n > 1:
                     self._right_cycle(i, psi)
                 for s in range(n):
-                    be.regularize(self.rw[i][s], self._CdC(psi, s + 1), self._eye(self.rw[i][s].shape[1]))
+                    self.project(self.rw[i][s], self._CdC(psi, s + 1), self._eye(self._bonds(psi, s)[1]))
             else:
-                if all(H[s].contains(i, i) for s in range(n)):
-                    def op(x, out):
-                        y = x
-                        for s in range(n - 1, -1, -1):
-                            y = self._tr(y, H[s].blocks[(i, i)], psi.AR[s])
-                        be.axpby(1.0, x, 0.0, out)
-                        be.axpby(-1.0, y, 1.0, out)
-                        return out
-                    self.rw[i][n - 1] = krylov.gmres(be, op, self.rw[i][n - 1], prev, tol=tol, maxiter=self.maxiter, ws=self.ws)
+                if all(self.O(s).contains(i, i) for s in range(n)):
+                    self.rw[i][n - 1] = self._solve_plain(cell, self.rw[i][n - 1], prev, tol)
                 if n > 1:
                     self._right_cycle(i, psi)

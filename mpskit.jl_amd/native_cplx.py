@@ -26,6 +26,7 @@ import numpy as np
 from .backend import Backend, DTensor
 from . import krylov
 from .cplx import HalfEmbeddedOp
+from .environments import MPOHamInfEnv
 
 
 def _mat(t: DTensor, rows2, cols):
@@ -1121,16 +1122,17 @@ def regauge(be, AC: DTensor, C: DTensor):
 def calc_galerkin(psi: NativeInfiniteMPS, envs: NativePerMPOInfEnv):
     """max over the unit cell of || (1 - AL AL^dag) normalize(ac_proj) ||  (toolbox.jl:26-38, environments with a state above)"""
     if isinstance(envs, NativeMPOHamInfEnv):     # toolbox.jl:17-22 with the Hamiltonian's H_AC
-        return max(_galerkin_ham(psi, envs, loc) for loc in range(len(psi)))
-    be, out = psi.be, 0.0
-    for loc in range(len(psi)):
-        g = envs.ac_proj(loc, psi)
-        be.scal(1.0 / be.norm(g), g)
-        Dl2, d, Dr = psi.AL[loc].shape
-        alm, gm = psi.AL[loc].reshape(Dl2 * d, Dr), g.reshape(Dl2 * d, g.shape[2])
-        be.gemm_c(alm, be.gemm_c(alm, gm, transA=True), alpha=-1.0, beta=1.0, out=gm)
-        out = max(out, be.norm(gm))
-    return out
+        return _calc_galerkin_inf(psi, envs)
+    return max(_galerkin_norm(psi.be, psi.AL[loc], envs.ac_proj(loc, psi)) for loc in range(len(psi)))
+
+
+def _galerkin_norm(be, AL: DTensor, g: DTensor):
+    """|| (1 - AL AL^dag) normalize(g) || on interleaved tensors; g is overwritten"""
+    be.scal(1.0 / be.norm(g), g)
+    Dl2, d, Dr = AL.shape
+    alm, gm = AL.reshape(Dl2 * d, Dr), g.reshape(Dl2 * d, g.shape[2])
+    be.gemm_c(alm, be.gemm_c(alm, gm, transA=True), alpha=-1.0, beta=1.0, out=gm)
+    return be.norm(gm)
 
 
 def _approximate_inf(psi: NativeInfiniteMPS, toapprox, alg, envs=None, device=None):  # approximate/vomps.jl:1-80 (one row)
@@ -1293,12 +1295,12 @@ class _PlainOp:
         return self(x, out)
 
 
-class NativeMPOHamInfEnv:
-    """environments(psi::NativeInfiniteMPS, H) of mpohaminfenv.jl:40-215 on interleaved storage: the counterpart of
-    environments.MPOHamInfEnv.  Level i of site s is its own (chi, 2 D, D) tensor of interleaved slabs, a site's environment for
-    the matvec kernels is assembled on demand and cached.  The triangular system is solved level by level; identity levels by
-    GMRES over the complex numbers (krylov.linsolve, cplx=True) on the regularised transfer matrix, whose application is the n
-    pass-through complex transfers and one mpsk_regularize_axpby.
+class NativeMPOHamInfEnv(MPOHamInfEnv):
+    """environments(psi::NativeInfiniteMPS, H) of mpohaminfenv.jl:40-215 on interleaved storage: environments.MPOHamInfEnv
+    with its leaves overridden, and nothing else -- the level solver, the cycles, recalculate and the assembled, cached site
+    environments are the base class's.  Level i of site s is its own (chi, 2 D, D) tensor of interleaved slabs.  Identity
+    levels are solved by GMRES over the complex numbers (krylov.linsolve, cplx=True) on the regularised transfer matrix, whose
+    application is the n pass-through complex transfers and one mpsk_regularize_axpby.
     H: a real MPOHamiltonian (its slices get complex twins) or a ComplexMPOHamiltonian whose period divides the unit cell.
     device: the route of the regulariser (None: REG_FUSED_DEFAULT, True: mpsk_regularize_axpby, False: composed from
     dotc / axpby_c)."""
@@ -1309,17 +1311,14 @@ class NativeMPOHamInfEnv:
             raise TypeError("NativeMPOHamInfEnv takes a NativeInfiniteMPS (NativeInfiniteMPS.from_real converts one)")
         if len(psi) % H.period != 0:
             raise ValueError(f"unit cell of the state ({len(psi)}) is not a multiple of the Hamiltonian's period ({H.period})")
-        be = self.be = psi.be
-        self.H, self.tol, self.maxiter, self.device = H, tol, maxiter, device
+        be, self.device = psi.be, device
         native = isinstance(H, ComplexMPOHamiltonian)
         self.opp = [H[s] if native else HalfEmbeddedOp._cslice(be, H[s]) for s in range(H.period)]
-        self.rng = np.random.default_rng(0) if rng is None else rng
-        self.ws = krylov.KrylovWorkspace(be)
-        self._blk, self._col, self._eyes, self._cache = {}, {}, {}, {}
+        self._blk, self._col, self._eyes = {}, {}, {}
         self.n_reg = 0                        # applications of the regularised operator (both routes), for inspection
-        self._start(psi)
-        self.recalculate(psi, tol)
+        super().__init__(psi, H, tol, maxiter, rng)
 
+    # ---- the leaves of MPOHamInfEnv on interleaved storage ----
     def O(self, pos):
         """the MPSK_C128 slice of site pos"""
         return self.opp[pos % len(self.opp)]
@@ -1327,57 +1326,41 @@ class NativeMPOHamInfEnv:
     def isid(self, i):
         return all(s.isscal(i, i) and abs(s.blocks[(i, i)] - 1) < 1e-14 for s in self.opp)
 
-    def _start(self, psi):
-        """random start environments in the bond spaces of psi (mpohaminfenv.jl:40-44)"""
-        be, rng, n, odim = self.be, self.rng, len(psi), self.H.odim
+    def _bonds(self, psi, s):
+        Dl, _, Dr = psi.dims(s)
+        return Dl, Dr
 
-        def rand(chi, D):
-            return be.upload_env_c([np.transpose(rng.random((chi, D, D)), (1, 0, 2)).astype(np.complex128)])
-        self.lw = [[rand(self.O(s).chil[i], psi.dims(s)[0]) for s in range(n)] for i in range(odim)]
-        self.rw = [[rand(self.O(s).chir[i], psi.dims(s)[2]) for s in range(n)] for i in range(odim)]
+    def _solve_tol(self, psi, tol):
+        """None is the tolerance of the last recalculation that named one; the route of the regulariser is settled here, so
+        that device=True on a backend without the entry is refused before anything is computed"""
+        if len(psi) % len(self.opp) != 0:
+            raise ValueError(f"unit cell of the state ({len(psi)}) is not a multiple of the Hamiltonian's period "
+                             f"({len(self.opp)})")
+        self._fused = _reg_route(self.be, self.device)
+        self.tol = self.tol if tol is None else tol
+        return self.tol
 
-    # ---- public ----
-    def recalculate(self, psi: NativeInfiniteMPS, tol=None):
-        tol = self.tol if tol is None else tol
-        n = len(psi)
-        if n % len(self.opp) != 0:
-            raise ValueError(f"unit cell of the state ({n}) is not a multiple of the Hamiltonian's period ({len(self.opp)})")
-        if len(self.lw[0]) != n or any(self.lw[0][s].shape[2] != psi.dims(s)[0] or self.rw[0][s].shape[2] != psi.dims(s)[2]
-                                       for s in range(n)):
-            self._start(psi)                  # the bond spaces changed: the old solutions do not fit
-        self._calclw(psi, tol)
-        self._calcrw(psi, tol)
-        self.dependency, self.tol = psi, tol
-        self._cache = {}
-        return self
+    def _random_level(self, chi, D):
+        return self.be.upload_env_c([np.transpose(self.rng.random((chi, D, D)), (1, 0, 2)).astype(np.complex128)])
 
-    def _assemble(self, which, pos, n):
-        key = (which, pos % n)
-        if key not in self._cache:
-            src = self.lw if which == "l" else self.rw
-            parts = [src[i][pos % n] for i in range(self.H.odim)]
-            out = self.be.empty(sum(p.shape[0] for p in parts), parts[0].shape[1], parts[0].shape[2])
-            off = 0
-            for p in parts:
-                out.buf[off:off + p.size].copy_(p.buf[:p.size])
-                off += p.size
-            self._cache[key] = out
-        return self._cache[key]
+    def _identity_level(self, chi, D):
+        return self.be.upload_env_c([np.stack([np.eye(D, dtype=np.complex128)] * chi, axis=1)])
 
-    def leftenv(self, pos, psi):
-        if self.dependency is not psi:
-            self.recalculate(psi)
-        return self._assemble("l", pos, len(psi))
+    def _eye(self, D):
+        if D not in self._eyes:
+            self._eyes[D] = self.be.upload_c(np.eye(D, dtype=np.complex128))
+        return self._eyes[D]
 
-    def rightenv(self, pos, psi):
-        if self.dependency is not psi:
-            self.recalculate(psi)
-        return self._assemble("r", pos, len(psi))
+    def _CCd(self, psi, s):
+        """r_LL of the bond right of site s as mpsk_regularize_axpby reads it: lvec[ket, bra] = C C^dag"""
+        c = psi.CR[s % len(psi)]
+        return self.be.gemm_c(c, c, transB=True)
 
-    def bytes(self):
-        return 8 * sum(t.size for lv in self.lw + self.rw for t in lv) + 8 * sum(t.size for t in self._cache.values())
+    def _CdC(self, psi, s):
+        """l_RR of the bond left of site s: lvec[bra, ket] = C^dag C"""
+        c = psi.CR[(s - 1) % len(psi)]
+        return self.be.gemm_c(c, c, transA=True)
 
-    # ---- helpers ----
     def _scaled(self, z, t):
         """z t for a complex number z (mpsk_vaxpby_c into a new tensor; never the real scal)"""
         return krylov.ComplexVec(self.be).axpby(z, t, 0.0, self.be.empty(*t.shape))
@@ -1404,42 +1387,6 @@ class NativeMPOHamInfEnv:
             return out if O == 1 else self._scaled(O, out)
         return be.transfer_right(self._level_slice(s, i, j), v, A, A)
 
-    def _left_cycle(self, idx, psi):  # mpohaminfenv.jl:177-195
-        n, be = len(psi), self.be
-        for s in range(n):
-            acc = be.zeros(*self.lw[idx][(s + 1) % n].shape)
-            for j in range(idx, -1, -1):
-                if self.O(s).contains(j, idx):
-                    be.axpby(1.0, self._tl(self.lw[j][s], s, j, idx, psi.AL[s]), 1.0, acc)
-            self.lw[idx][(s + 1) % n] = acc
-
-    def _right_cycle(self, idx, psi):  # :197-215
-        n, be = len(psi), self.be
-        for s in range(n - 1, -1, -1):
-            acc = be.zeros(*self.rw[idx][(s - 1) % n].shape)
-            for j in range(idx, self.H.odim):
-                if self.O(s).contains(idx, j):
-                    be.axpby(1.0, self._tr(self.rw[j][s], s, idx, j, psi.AR[s]), 1.0, acc)
-            self.rw[idx][(s - 1) % n] = acc
-
-    def _CCd(self, psi, s):
-        """r_LL of the bond right of site s as mpsk_regularize_axpby reads it: lvec[ket, bra] = C C^dag"""
-        c = psi.CR[s % len(psi)]
-        return self.be.gemm_c(c, c, transB=True)
-
-    def _CdC(self, psi, s):
-        """l_RR of the bond left of site s: lvec[bra, ket] = C^dag C"""
-        c = psi.CR[(s - 1) % len(psi)]
-        return self.be.gemm_c(c, c, transA=True)
-
-    def _eye(self, D):
-        if D not in self._eyes:
-            self._eyes[D] = self.be.upload_c(np.eye(D, dtype=np.complex128))
-        return self._eyes[D]
-
-    def _identity_level(self, chi, D):
-        return self.be.upload_env_c([np.stack([np.eye(D, dtype=np.complex128)] * chi, axis=1)])
-
     def _solve(self, op, b, x0, tol):
         if self.be.norm(b) == 0:
             return self.be.zeros(*b.shape)
@@ -1447,67 +1394,14 @@ class NativeMPOHamInfEnv:
         self.n_reg += info.numops
         return x
 
-    def _calclw(self, psi, tol):  # mpohaminfenv.jl:76-123
-        n, odim, be = len(psi), self.H.odim, self.be
-        fused = _reg_route(be, self.device)
-        self.lw[0][0] = self._identity_level(self.O(0).chil[0], psi.dims(0)[0])
-        if n > 1:
-            self._left_cycle(0, psi)
-        for i in range(1, odim):
-            prev = self.lw[i][0]
-            self.lw[i][0] = be.zeros(*prev.shape)
-            self._left_cycle(i, psi)
-            if self.isid(i):
-                def cell(v):
-                    for s in range(n):
-                        v = be.transfer_left(None, v, psi.AL[s], psi.AL[s], cplx=True)
-                    return v
-                op = _RegOp(be, cell, self._CCd(psi, n - 1), self._eye(psi.dims(0)[0]), fused)
-                self.lw[i][0] = self._solve(op, self.lw[i][0], prev, tol)
-                if n > 1:
-                    self._left_cycle(i, psi)
-                for s in range(n):  # :103-107 subtract the fixed-point projection at every site
-                    _RegOp(be, None, self._CCd(psi, s - 1), self._eye(psi.dims(s)[0]), fused).project(self.lw[i][s])
-            else:
-                if all(self.O(s).contains(i, i) for s in range(n)):
-                    def cell(v, i=i):
-                        for s in range(n):
-                            v = self._tl(v, s, i, i, psi.AL[s])
-                        return v
-                    self.lw[i][0] = self._solve(_PlainOp(be, cell), self.lw[i][0], prev, tol)
-                if n > 1:
-                    self._left_cycle(i, psi)
+    def _solve_identity(self, cell, lvec, rvec, b, x0, tol):
+        return self._solve(_RegOp(self.be, cell, lvec, rvec, self._fused), b, x0, tol)
 
-    def _calcrw(self, psi, tol):  # :125-175
-        n, odim, be = len(psi), self.H.odim, self.be
-        fused = _reg_route(be, self.device)
-        self.rw[odim - 1][n - 1] = self._identity_level(self.O(n - 1).chir[odim - 1], psi.dims(n - 1)[2])
-        if n > 1:
-            self._right_cycle(odim - 1, psi)
-        for i in range(odim - 2, -1, -1):
-            prev = self.rw[i][n - 1]
-            self.rw[i][n - 1] = be.zeros(*prev.shape)
-            self._right_cycle(i, psi)
-            if self.isid(i):
-                def cell(v):
-                    for s in range(n - 1, -1, -1):
-                        v = be.transfer_right(None, v, psi.AR[s], psi.AR[s], cplx=True)
-                    return v
-                op = _RegOp(be, cell, self._CdC(psi, 0), self._eye(psi.dims(n - 1)[2]), fused)
-                self.rw[i][n - 1] = self._solve(op, self.rw[i][n - 1], prev, tol)
-                if n > 1:
-                    self._right_cycle(i, psi)
-                for s in range(n):
-                    _RegOp(be, None, self._CdC(psi, s + 1), self._eye(psi.dims(s)[2]), fused).project(self.rw[i][s])
-            else:
-                if all(self.O(s).contains(i, i) for s in range(n)):
-                    def cell(v, i=i):
-                        for s in range(n - 1, -1, -1):
-                            v = self._tr(v, s, i, i, psi.AR[s])
-                        return v
-                    self.rw[i][n - 1] = self._solve(_PlainOp(be, cell), self.rw[i][n - 1], prev, tol)
-                if n > 1:
-                    self._right_cycle(i, psi)
+    def _solve_plain(self, cell, b, x0, tol):
+        return self._solve(_PlainOp(self.be, cell), b, x0, tol)
+
+    def project(self, v, lvec, rvec):
+        return _RegOp(self.be, None, lvec, rvec, self._fused).project(v)
 
     # ---- the site operators (derivatives.jl:3-31, :77-93) ----
     def hac(self, pos, psi):
@@ -1529,13 +1423,7 @@ def environments(psi: NativeInfiniteMPS, H, **kw):
 
 def _galerkin_ham(psi: NativeInfiniteMPS, envs: NativeMPOHamInfEnv, loc):
     """|| (1 - AL AL^dag) normalize(H_AC AC) || of one site (toolbox.jl:17-22)"""
-    be = psi.be
-    g = envs.hac(loc, psi).apply(psi.AC[loc])
-    be.scal(1.0 / be.norm(g), g)
-    Dl2, d, Dr = psi.AL[loc].shape
-    alm, gm = psi.AL[loc].reshape(Dl2 * d, Dr), g.reshape(Dl2 * d, g.shape[2])
-    be.gemm_c(alm, be.gemm_c(alm, gm, transA=True), alpha=-1.0, beta=1.0, out=gm)
-    return be.norm(gm)
+    return _galerkin_norm(psi.be, psi.AL[loc], envs.hac(loc, psi).apply(psi.AC[loc]))
 
 
 def _energy_inf(psi: NativeInfiniteMPS, H, envs: NativeMPOHamInfEnv = None):
@@ -1556,59 +1444,58 @@ def _energy_inf(psi: NativeInfiniteMPS, H, envs: NativeMPOHamInfEnv = None):
     return ens
 
 
+# ---- what the uniform drivers ask of the state's storage: algorithms._vumps / algorithms._timestep_inf are the loops, and look
+# these names up here for a NativeInfiniteMPS and in algorithms.py for an InfiniteMPS (algorithms._storage) ----
+
+VUMPS_LABEL = "VUMPS (interleaved complex)"
+
+
+def _groundstate_AL(psi, H, envs, loc, tol, krylovdim, ws):
+    """AL of site loc from the lowest eigenvectors of H_AC and H_C, solved to `tol` (vumps.jl:46-60)"""
+    be = psi.be
+    _, AC, _, _ = krylov.eigsolve_sr(be, envs.hac(loc, psi).apply, psi.AC[loc], tol=tol, krylovdim=krylovdim, ws=ws)
+    _, C, _, _ = krylov.eigsolve_sr(be, envs.hc(loc, psi), psi.CR[loc], tol=tol, krylovdim=krylovdim, ws=ws)
+    return regauge(be, AC, C)
+
+
+def _evolved_AL(psi, H, envs, loc, t, dt, alg, ws):
+    """AL of site loc from AC and C evolved over dt (tdvp.jl:27-45)"""
+    from .algorithms import _integrate_embedded
+    be, z, h = psi.be, -1j * complex(dt), envs.hac(loc, psi)
+    ac = _integrate_embedded(be, lambda x, out=None: h.apply(x, out=out), psi.AC[loc], z, alg, ws)
+    c = _integrate_embedded(be, envs.hc(loc, psi), psi.CR[loc], z, alg, ws)
+    return regauge(be, ac, c)
+
+
+def _from_AL(psi, AL, **kw):
+    return NativeInfiniteMPS.from_AL(AL, psi.CR[len(psi) - 1], be=psi.be, **kw)
+
+
+def _calc_galerkin_inf(psi, envs):
+    return max(_galerkin_ham(psi, envs, loc) for loc in range(len(psi)))
+
+
+def _energy_sum(psi, H, envs):
+    return float(np.sum(_energy_inf(psi, H, envs)).real)
+
+
 def _vumps_inf(psi: NativeInfiniteMPS, H, alg, envs=None, device=None):  # vumps.jl:29-92
-    import time
-    from .algorithms import updatetol, _log
-    be, n = psi.be, len(psi)
-    envs = NativeMPOHamInfEnv(psi, H, device=device) if envs is None else envs
-    galerkin = lambda p: max(_galerkin_ham(p, envs, loc) for loc in range(n))
-    eps = galerkin(psi)
-    ws = krylov.KrylovWorkspace(be)
-    t0, history = time.time(), []
-    for it in range(1, alg.maxiter + 1):
-        etol = updatetol(alg.eig_tol_min, alg.eig_tol_max, alg.eig_tol_factor, it, eps)
-        newAL = []
-        for loc in range(n):
-            _, AC, _, _ = krylov.eigsolve_sr(be, envs.hac(loc, psi).apply, psi.AC[loc], tol=etol, krylovdim=alg.krylovdim, ws=ws)
-            _, C, _, _ = krylov.eigsolve_sr(be, envs.hc(loc, psi), psi.CR[loc], tol=etol, krylovdim=alg.krylovdim, ws=ws)
-            newAL.append(regauge(be, AC, C))
-        gtol = updatetol(alg.gauge_tol_min, alg.gauge_tol_max, alg.gauge_tol_factor, it, eps)
-        psi = NativeInfiniteMPS.from_AL(newAL, psi.CR[n - 1], tol=gtol, be=be)
-        envs.recalculate(psi, updatetol(alg.env_tol_min, alg.env_tol_max, alg.env_tol_factor, it, eps))
-        if alg.finalize is not None:
-            psi, envs = alg.finalize(it, psi, H, envs)
-        eps = galerkin(psi)
-        if alg.verbosity >= 3 or eps <= alg.tol or it == alg.maxiter:
-            E = float(np.sum(_energy_inf(psi, H, envs)).real)
-            history.append((it, E, eps))
-            _log(alg, "VUMPS (interleaved complex)", it, E, eps, t0)
-        if eps <= alg.tol:
-            break
-    envs.history = history
-    return psi, envs, eps
+    from .algorithms import _vumps
+    return _vumps(psi, H, alg, NativeMPOHamInfEnv(psi, H, device=device) if envs is None else envs)
 
 
 def _timestep_inf(psi: NativeInfiniteMPS, H, t, dt, alg, envs=None, device=None):  # tdvp.jl:21-59 (leftorthflag = true)
-    from .algorithms import _integrate_embedded
-    be, n = psi.be, len(psi)
-    envs = NativeMPOHamInfEnv(psi, H, device=device) if envs is None else envs
-    ws = krylov.KrylovWorkspace(be)
-    z = -1j * complex(dt)
-    newAL = []
-    for loc in range(n):
-        h = envs.hac(loc, psi)
-        ac = _integrate_embedded(be, lambda x, out=None: h.apply(x, out=out), psi.AC[loc], z, alg, ws)
-        c = _integrate_embedded(be, envs.hc(loc, psi), psi.CR[loc], z, alg, ws)
-        newAL.append(regauge(be, ac, c))
-    psi2 = NativeInfiniteMPS.from_AL(newAL, psi.CR[n - 1], tol=alg.tolgauge, maxiter=alg.gaugemaxiter, be=be)
-    envs.recalculate(psi2)
-    return psi2, envs
+    from . import algorithms
+    return algorithms._timestep_inf(psi, H, t, dt, alg, NativeMPOHamInfEnv(psi, H, device=device) if envs is None else envs)
 
 
 def time_evolve(psi, H, t_span, alg=None, envs=None):
     """time_evolve(psi, H, t_span, TDVP())  (time_evolve.jl:20-40) on interleaved states: consecutive timesteps"""
-    from .algorithms import TDVP
-    alg = TDVP() if alg is None else alg
+    from . import algorithms
+    if isinstance(psi, NativeInfiniteMPS):       # algorithms.timestep hands a uniform state back to timestep above
+        return algorithms.time_evolve(psi, H, t_span, alg, envs)
+    # a NativeFiniteMPS keeps its own loop: algorithms.timestep would copy it and build the environments of a real chain
+    alg = algorithms.TDVP() if alg is None else alg
     for t0, t1 in zip(t_span[:-1], t_span[1:]):
         psi, envs = timestep(psi, H, t0, t1 - t0, alg, envs)
         if alg.finalize is not None:

@@ -268,7 +268,7 @@ def environments(state, H, lenvs=None, renvs=None):
     lenvs = _environments(state.left_gs, H) if lenvs is None else lenvs
     if renvs is None:
         renvs = lenvs if state.right_gs is state.left_gs else _environments(state.right_gs, H)
-    if not isinstance(lenvs, MPOHamInfEnv) or not isinstance(renvs, MPOHamInfEnv):
+    if type(lenvs) is not MPOHamInfEnv or type(renvs) is not MPOHamInfEnv:      # not its interleaved subclass either
         raise TypeError("lenvs / renvs are the MPOHamInfEnv of the uniform states")
     GL0 = lenvs.leftenv(0, state.left_gs)
     GRL = renvs.rightenv(L - 1, state.right_gs)

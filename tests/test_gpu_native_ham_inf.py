@@ -83,3 +83,16 @@ def test_refusals(be):
 
 def test_restart_after_the_bonds_change(be):
     cs.case_restart_after_bond_change(be)
+
+
+def test_fused_route_makes_the_recorded_calls(be):
+    """one construction at n = 2, D = 4 on the fused route of the regulariser (it has no host stand-in): the backend calls of
+    tests/golden/ham_inf_env_calls.json, in that order (tests/test_ham_inf_env_calls_cpu.py holds the other sections)"""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+    import make_ham_inf_env_calls as gen
+    got = gen.record_device(be)[gen.DEVICE_SECTION]
+    assert any(c.startswith("regularize_axpby(") for c in got)
+    diff = gen.first_difference(got, gen.load()[gen.DEVICE_SECTION])
+    assert diff is None, diff
