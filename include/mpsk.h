@@ -318,7 +318,8 @@ int mpsk_dAC2_proj(mpsk_ctx* ctx, const mpsk_mposlice* H1, const mpsk_mposlice* 
  * [Dr, Dr]; AC: [Dl, d1, Dm]; AR: [Dm, d2, Dr]; Y: [Dl, d1, Dr, d2] (the layout of mpsk_dAC2's result).  Both slice
  * kinds; a dense slice above the crossover of mpsk_mposlice_create_dense contracts its MPO tensor as an fp64 MFMA GEMM,
  * never as a slab mix.  Workspace: (Wl + Wm) d1 Dl Dm + (Wr + Wm) d2 Dm Dr doubles, no single intermediate above
- * max(Wl, Wm, Wr) d Dmax^2.  MPSK_F64 only. */
+ * max(Wl, Wm, Wr) d Dmax^2.  MPSK_F64 only: the complex Y of a bond expansion is mpsk_dAC2_proj under MPSK_C128 with
+ * Dlo = Dl, Dro = Dr, which mpsk_complement_tsvd takes under MPSK_C128. */
 int mpsk_dAC2_product(mpsk_ctx* ctx, const mpsk_mposlice* H1, const mpsk_mposlice* H2, int Dl, int Dm, int Dr,
                       const void* GL, const void* GR, const void* AC, const void* AR, void* Y);
 /* mpsk_complement_tsvd == VL = leftnull(AL); VR = rightnull(AR); U, S, V = tsvd(VL' * Y * VR'; trunc = truncdim(k));
@@ -336,7 +337,24 @@ int mpsk_dAC2_product(mpsk_ctx* ctx, const mpsk_mposlice* H1, const mpsk_mposlic
  * other case, and when the check fails, its full iteration runs on X (not mpsk_tsvd: the split needs the vectors of one
  * side only).  mpsk_ctx_split_stats describes that split.  mpsk_ctx_complement_stats: calls with a non-empty complement /
  * calls answered by the accepted subspace stage / all other calls (full iteration of the split, mpsk_tsvd of a small X,
- * X = 0); any pointer may be NULL.  Synchronises.  MPSK_F64 only. */
+ * X = 0); any pointer may be NULL.  Synchronises.
+ *   MPSK_C128 (mpsk_ctx_set_dtype): Y, QL, QR, U, Vt interleaved complex128, column-major, leading dimensions in complex
+ *   elements; S stays kept real doubles, descending.  Adjoint replaces transpose: X = (1 - QL QL^H) Y (1 - QR^H QR), and the
+ *   contract reads U^H U = 1, Vt Vt^H = 1, QL^H U = 0, Vt QR^H = 0.  Everything else above carries over (kept, NULL sides,
+ *   completion, refusals, synchronisation, the counters, non-finite Y).  Method: min(m, n) <= 64: the complex mpsk_tsvd of X.
+ *   Otherwise, in svd mode 3 and while the ctx is not backing off, a truncated range finder on the interleaved tensors:
+ *   r = min(k + max(64, k / 2), m - pl, n - pr) rows (rank(X) cannot exceed the complement, so the 5/8 cap of the fp64 split
+ *   does not apply), structured random start, 4 rounds of  Z = W X^H, LQpos, B = Z X, LQpos,  the complex mpsk_tsvd of
+ *   B = Z X (r x n), U = Z^H U_B.  X and X^H are the SECOND operands of the complex GEMM and are read as stored: only the
+ *   r-row block is embedded, no 2m x 2n real copy of X or Y exists, a product costs 8 r m n flops (16 (pl + pr) m n for the
+ *   projection, 64 r m n for the iteration).  The kept triplets are checked against X itself:
+ *   |(1 - Z^H Z) X Vt^H|_F <= 1e-12 |X|_F (MPSK_SPLIT_TOL) -> counted under n_subspace; a failed check, a lower svd mode or
+ *   a ctx that backs off (after a failed check: 4, 8, ... 64 calls) -> the complex mpsk_tsvd of X, counted under n_full.
+ *   Singular values at or below 32 eps sqrt(m + n) max|Y_ij|, the rounding level of the projection, are returned as exactly
+ *   0 and their directions completed inside the complement.  Scratch (the ctx's expansion scratch, in doubles, interleaved
+ *   operands): 4 m n (X, X^H) + 2 min(m, n) n + 6 r max(m, n) + 2 r n + 4 r^2 + 2 k (2 m + n + r + k)
+ *   + 2 max(pl n, pr m, pl k, k pr), plus what the complex GEMM, QRpos / LQpos and SVD take for themselves.
+ *   The complex Y comes from mpsk_dAC2_proj (Dlo = Dl, Dro = Dr): mpsk_dAC2_product stays MPSK_F64 only. */
 int mpsk_complement_tsvd(mpsk_ctx* ctx, int m, int n, const void* Y, int ldy, const void* QL, int ldql, int pl,
                          const void* QR, int ldqr, int pr, int k, void* U, int ldu, void* S, void* Vt, int ldvt, int* kept);
 int mpsk_ctx_complement_stats(mpsk_ctx* ctx, long* n_calls, long* n_subspace, long* n_full);

@@ -503,6 +503,30 @@ class Backend:
             return None, None, None, 0
         return U, S, Vt, kk
 
+    def complement_tsvd_c(self, Y: DTensor, QL: DTensor, QR: DTensor, k: int):
+        """mpsk_complement_tsvd under MPSK_C128: the k leading singular triplets of (1 - QL QL^H) Y (1 - QR^H QR) on interleaved
+        complex128 matrices; Y (2 m, n), QL (2 m, pl) with orthonormal columns or None, QR (2 pr, n) with orthonormal rows or
+        None.  Returns (U (2 m, kept), S (kept,) real, Vt (2 kept, n), kept); kept = 0: (None, None, None, 0)."""
+        m2, n = Y.shape
+        m = m2 // 2
+        assert m2 == 2 * m
+        pl = 0 if QL is None else QL.shape[1]
+        pr = 0 if QR is None else QR.shape[0] // 2
+        kk = max(0, min(int(k), m - pl, n - pr))
+        U, S, Vt = self.empty(m2, kk), self.empty(kk), self.empty(2 * kk, n)
+        kept = C.c_int(-1)
+        self._set_dtype(True)
+        try:
+            check(self.lib.mpsk_complement_tsvd(self.ctx, m, n, Y.ptr, m, None if QL is None else QL.ptr, m, pl,
+                                                None if QR is None else QR.ptr, max(pr, 1), pr, int(k), U.ptr, m, S.ptr,
+                                                Vt.ptr, max(kk, 1), C.byref(kept)), "mpsk_complement_tsvd (C128)")
+        finally:
+            self._set_dtype(False)
+        assert kept.value == kk, (kept.value, kk)
+        if kk == 0:
+            return None, None, None, 0
+        return U, S, Vt, kk
+
     def complement_stats(self):
         """mpsk_complement_tsvd calls: {"calls", "subspace" (answered by the accepted subspace stage), "full" (all others: full
         iteration of the split, mpsk_tsvd of a small X, X = 0)}"""

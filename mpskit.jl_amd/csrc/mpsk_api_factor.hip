@@ -1206,6 +1206,205 @@ int mpsk_ctx_split_stats(mpsk_ctx* c, int* path, int* iterations, double* residu
   return MPSK_OK;
 }
 
+// ---- complex128 complement SVD (ctx dtype MPSK_C128) -------------------------------------------------------------------
+// The k leading singular triplets of X = (1 - QL QL^H) Y (1 - QR^H QR) on interleaved complex operands (leading dimensions
+// in complex elements, S real).  Every product is gemm_c128 with X -- or its conjugate transpose XH, kept beside it -- as
+// the SECOND operand: that operand is read as stored, and only the thin first operand (QL, QR, a block of r rows) is
+// embedded, so no 2m x 2n real copy of X or Y ever exists and a product of a p-row block with X costs 8 p m n real flops, the
+// complex optimum (the two-K-segment form of dAC_c128 has the same count and needs the planes of its second operand, i.e. a
+// planar copy of X per product; gemm_c128 needs nothing but the thin embedding).
+//   projection   X <- X - QL (QL^H X);  XH = X^H;  XH <- XH - QR^H (QR XH);  X = XH^H       four thin products, 16 (pl + pr) m n
+//   min(m, n) <= 64: tsvd_c128_entry on X.
+//   otherwise, in svd mode 3 and not while the ctx backs off: a truncated range finder on r = min(k + max(64, k / 2), m - pl,
+//   n - pr) rows (rank(X) cannot exceed the dimension of the complement, so more rows add nothing and the fp64 cap of 5/8 of
+//   the matrix does not apply):  W (r x n) structured random;  CX_RANGE_ITERS times  Z = W XH, Z <- rows of LQpos(Z),
+//   B = Z X, W <- rows of LQpos(B)  (2 CX_RANGE_ITERS products of 8 r m n flops, lqpos_c128 in between; the last LQpos is
+//   not taken);  B = Z X = U_B S V_B (tsvd_c128_entry, r x n);  U = Z^H U_B, Vt = V_B.
+//   the check, not an estimate: U^H X = S Vt holds by construction, so the triplets are singular triplets of X exactly when
+//   X Vt^H = U S, and X Vt^H - U S = (1 - Z^H Z) X Vt^H:  rho = |(Vt XH)(1 - Z^H Z)|_F / |X|_F <= 1e-12 (MPSK_SPLIT_TOL) and
+//   |U|_F^2 = kept (a collapsed basis has rho = 0 too) -> accepted, counted under n_subspace.  Otherwise, and in every other
+//   case above 64, tsvd_c128_entry on X itself (n_full); a failed check makes the ctx back off as the fp64 split does.
+// Singular values at or below 32 eps sqrt(m + n) max|Y_ij| -- the rounding level of the projection -- are returned as
+// exactly 0 (X = 0, rank(X) < kept, Y inside the range of QL): their directions are completed inside the complement.
+// Then, as in the fp64 entry, two rounds of projection and QRpos / LQpos impose the complement condition and the isometry.
+static const int CX_RANGE_ITERS = 4;
+
+static int cx_copy2d(mpsk_ctx* c, void* dst, int lddst, const void* src, int ldsrc, int rows, int cols) {
+  HIPCHK(hipMemcpy2DAsync(dst, sizeof(double) * 2 * lddst, src, sizeof(double) * 2 * ldsrc, sizeof(double) * 2 * rows, cols,
+                          hipMemcpyDeviceToDevice, c->stream));
+  return MPSK_OK;
+}
+static int cx_absmax(mpsk_ctx* c, const double* A, int64_t ld_doubles, int rows_doubles, int cols, double* out) {
+  unsigned long long* d_mx = (unsigned long long*)c->d_partial;
+  unsigned long long h_mx = 0;
+  HIPCHK(hipMemsetAsync(d_mx, 0, sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(split_absmax_kernel, dim3(1024), dim3(256), 0, c->stream, A, ld_doubles, rows_doubles, cols, d_mx);
+  HIPCHK(hipMemcpyAsync(&h_mx, d_mx, sizeof(h_mx), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  std::memcpy(out, &h_mx, sizeof(double));
+  return MPSK_OK;
+}
+
+// (arguments checked by mpsk_complement_tsvd; kk = the number of triplets to deliver, > 0)
+static int complement_tsvd_c128(mpsk_ctx* c, int m, int n, const void* Y, int ldy, const void* QL, int ldql, int pl,
+                                const void* QR, int ldqr, int pr, int kk, void* U, int ldu, void* S, void* Vt, int ldvt) {
+  static const double sub_tol = getenv("MPSK_SPLIT_TOL") ? atof(getenv("MPSK_SPLIT_TOL")) : 1.0e-12;
+  const int nn = std::min(m, n), mx_dim = std::max(m, n);
+  const bool small = nn <= 64;
+  int r = 0;                                            // rows of the range finder (0: not taken)
+  if (!small) {
+    if (c->split_skip > 0) --c->split_skip;             // (backing off after a failed check)
+    else if (c->svd_precondition == 3) r = std::min(kk + std::max(64, kk / 2), std::min(m - pl, n - pr));
+  }
+  // scratch, in doubles (every part an even count: 16-byte aligned complex elements)
+  const size_t x_d = (size_t)2 * m * n, bf_d = (size_t)2 * nn * n, s_d = ev2((size_t)nn);
+  const size_t tp_d = 2 * std::max(std::max((size_t)pl * n, (size_t)pr * m), std::max(std::max((size_t)pl * kk, (size_t)kk * pr), (size_t)1));
+  const size_t g_d = (size_t)2 * r * mx_dim, l_d = (size_t)2 * r * r, vb_d = (size_t)2 * r * n, sb_d = ev2((size_t)r);
+  const size_t th_d = (size_t)2 * kk * m, p1_d = (size_t)2 * kk * r;
+  const size_t ut_d = (size_t)2 * m * kk, vtt_d = (size_t)2 * kk * n, rt_d = (size_t)2 * kk * kk;
+  double* base = nullptr;
+  if (int rc = ex_scratch(c, sizeof(double) * (2 * x_d + bf_d + s_d + tp_d + 3 * g_d + 2 * l_d + vb_d + sb_d + th_d + p1_d + ut_d +
+                                                vtt_d + rt_d), &base))
+    return rc;
+  double* X = base;                  // m x n
+  double* XH = X + x_d;              // n x m = X^H; U of the full SVD once the range finder is over (m x nn)
+  double* Bf = XH + x_d;             // Vh of the full SVD (nn x n)
+  double* Ss = Bf + bf_d;
+  double* TP = Ss + s_d;
+  double* GW = TP + tp_d;            // r x n   right block W
+  double* GZ = GW + g_d;             // r x m   left block Z (orthonormal rows)
+  double* GT = GZ + g_d;             // product before its LQpos; B = Z X at the end
+  double* Lr = GT + g_d;             // triangular factors (discarded)
+  double* UB = Lr + l_d;             // r x r
+  double* VB = UB + l_d;             // r x n
+  double* SB = VB + vb_d;
+  double* Th = SB + sb_d;            // kk x m
+  double* P1 = Th + th_d;            // kk x r
+  double* Ut = P1 + p1_d;            // QRpos output
+  double* Vtt = Ut + ut_d;           // LQpos output
+  double* Rt = Vtt + vtt_d;
+  hipStream_t st = c->stream;
+  ++c->n_compl;
+  c->last_split_iters = 0; c->last_split_resid = 0.0; c->last_split_path = 0;
+  double my = 0.0, mx = 0.0;
+  if (int rc = cx_absmax(c, (const double*)Y, (int64_t)2 * ldy, 2 * m, n, &my)) return rc;
+  if (!std::isfinite(my)) return fail(MPSK_ERR_INVALID, "mpsk_complement_tsvd: Y is not finite");
+  const double thr = 32.0 * 2.220446049250313e-16 * std::sqrt((double)m + (double)n) * my;
+  int have = 0;                      // triplets delivered by the SVD; the rest is completed below
+  if (my > 0.0) {
+    // X = (1 - QL QL^H) Y (1 - QR^H QR)
+    if (int rc = cx_copy2d(c, X, m, Y, ldy, m, n)) return rc;
+    if (pl > 0) {
+      if (int rc = gemm_c128(c, 1, 0, pl, n, m, 1.0, QL, ldql, X, m, 0.0, TP, pl)) return rc;
+      if (int rc = gemm_c128(c, 0, 0, m, n, pl, -1.0, QL, ldql, TP, pl, 1.0, X, m)) return rc;
+    }
+    hipLaunchKernelGGL(cx_ctranspose_kernel, dim3(1024), dim3(256), 0, st, X, (int64_t)2 * m, m, n, XH, (int64_t)2 * n);
+    if (pr > 0) {
+      if (int rc = gemm_c128(c, 0, 0, pr, m, n, 1.0, QR, ldqr, XH, n, 0.0, TP, pr)) return rc;
+      if (int rc = gemm_c128(c, 1, 0, n, m, pr, -1.0, QR, ldqr, TP, pr, 1.0, XH, n)) return rc;
+      hipLaunchKernelGGL(cx_ctranspose_kernel, dim3(1024), dim3(256), 0, st, XH, (int64_t)2 * n, n, m, X, (int64_t)2 * m);
+    }
+    if (int rc = cx_absmax(c, X, (int64_t)2 * m, 2 * m, n, &mx)) return rc;
+    if (!std::isfinite(mx)) return fail(MPSK_ERR_INVALID, "mpsk_complement_tsvd: Y is not finite");
+  }
+  const double* Usrc = nullptr; const double* Vsrc = nullptr; const double* Ssrc = nullptr;
+  int ldus = 0, ldvs = 0, ns = 0;    // where the accepted SVD left its factors, and how many values it has
+  bool done = false;
+  if (!(mx > thr)) {
+    ++c->n_compl_full;               // X = 0 to the rounding level of the projection: nothing to decompose
+    done = true;
+  } else if (r > 0) {
+    // the range finder; a factorization that refuses its input sends the call to the full SVD like a failed check
+    bool ok = true;
+    double xn = 0.0, rho = INFINITY;
+    if (int rc = mpsk_vnrm2(c, (int64_t)2 * m * n, X, &xn)) return rc;
+    hipLaunchKernelGGL(split_fill_kernel, dim3(1024), dim3(256), 0, st, GW, (int64_t)2 * r * n, 0x5eedu);
+    for (int it = 0; it < CX_RANGE_ITERS && ok; ++it) {
+      if (int rc = gemm_c128(c, 0, 0, r, m, n, 1.0, GW, r, XH, n, 0.0, GT, r)) return rc;       // Z = W XH
+      if (int rc = lqpos_c128(c, r, m, GT, r, Lr, r, GZ, r)) { if (rc != MPSK_ERR_INVALID) return rc; ok = false; break; }
+      if (int rc = gemm_c128(c, 0, 0, r, n, m, 1.0, GZ, r, X, m, 0.0, GT, r)) return rc;        // B = Z X
+      if (it + 1 < CX_RANGE_ITERS)
+        if (int rc = lqpos_c128(c, r, n, GT, r, Lr, r, GW, r)) { if (rc != MPSK_ERR_INVALID) return rc; ok = false; }
+    }
+    int kb = 0; double dn = 0.0;
+    if (ok) {
+      if (int rc = tsvd_c128_entry(c, r, n, GT, r, UB, r, SB, VB, r, 0, 0.0, &kb, &dn)) { if (rc != MPSK_ERR_INVALID) return rc; ok = false; }
+    }
+    if (ok) {
+      const int kc = std::min(kk, kb);
+      // Th = Vt XH (= (X Vt^H)^H, kc x m);  Th <- Th - (Th Z^H) Z;  rho = |Th| / |X|
+      if (int rc = gemm_c128(c, 0, 0, kc, m, n, 1.0, VB, r, XH, n, 0.0, Th, kc)) return rc;
+      if (int rc = gemm_c128(c, 0, 1, kc, r, m, 1.0, Th, kc, GZ, r, 0.0, P1, kc)) return rc;
+      if (int rc = gemm_c128(c, 0, 0, kc, m, r, -1.0, P1, kc, GZ, r, 1.0, Th, kc)) return rc;
+      if (int rc = mpsk_vnrm2(c, (int64_t)2 * kc * m, Th, &rho)) return rc;
+      rho = xn > 0.0 ? rho / xn : rho;
+      // U = Z^H U_B into Ut (m x kc): nothing is written to the caller's buffers before the check has passed
+      if (int rc = gemm_c128(c, 1, 0, m, kc, r, 1.0, GZ, r, UB, r, 0.0, Ut, m)) return rc;
+      double un = 0.0;
+      if (int rc = mpsk_vnrm2(c, (int64_t)2 * m * kc, Ut, &un)) return rc;
+      if (!(std::fabs(un * un - (double)kc) <= 1.0e-8 * kc)) rho = INFINITY;
+      c->last_split_iters = CX_RANGE_ITERS; c->last_split_resid = rho;
+      if (getenv("MPSK_SVD_DEBUG"))
+        fprintf(stderr, "[mpsk_complement_tsvd C128] range finder: r = %d of %d x %d, %d iterations, residual %.3e (tol %.1e)\n",
+                r, m, n, CX_RANGE_ITERS, rho, sub_tol);
+      if (rho <= sub_tol) {
+        ++c->n_compl_sub;
+        c->last_split_path = 1; c->split_backoff = 0;
+        Usrc = Ut; ldus = m; Vsrc = VB; ldvs = r; Ssrc = SB; ns = kc;
+        done = true;
+      }
+    }
+    if (!done) {                     // flat spectra come in runs: the next calls skip the range finder, 4, 8, ... 64 of them
+      c->last_split_path = 2;
+      c->split_backoff = c->split_backoff ? std::min(2 * c->split_backoff, 64) : 4;
+      c->split_skip = c->split_backoff;
+    }
+  }
+  if (!done) {                       // small X, svd mode below 3, backing off, failed check: the full SVD of X
+    int kf = 0; double dn = 0.0;
+    double* Af = XH;                 // (X^H is no longer needed; m x nn fits in n x m)
+    if (int rc = tsvd_c128_entry(c, m, n, X, m, Af, m, Ss, Bf, nn, 0, 0.0, &kf, &dn)) return rc;
+    ++c->n_compl_full;
+    Usrc = Af; ldus = m; Vsrc = Bf; ldvs = nn; Ssrc = Ss; ns = std::min(kk, kf);
+  }
+  if (ns > 0) {                      // values above the rounding level of the projection count; S is descending
+    std::vector<double> hs((size_t)ns);
+    HIPCHK(hipMemcpyAsync(hs.data(), Ssrc, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    while (have < ns && hs[have] > thr) ++have;
+  }
+  if (have > 0) {
+    if (int rc = cx_copy2d(c, U, ldu, Usrc, ldus, m, have)) return rc;
+    if (int rc = cx_copy2d(c, Vt, ldvt, Vsrc, ldvs, have, n)) return rc;
+    HIPCHK(hipMemcpyAsync(S, Ssrc, sizeof(double) * have, hipMemcpyDeviceToDevice, st));
+  }
+  if (have < kk) {                   // directions the SVD did not deliver: random, singular value 0
+    const int rr = kk - have;
+    hipLaunchKernelGGL(split_fill_kernel, dim3(256), dim3(256), 0, st, Vtt, (int64_t)2 * rr * n, 0xfeedu);
+    if (int rc = cx_copy2d(c, (double*)Vt + (size_t)2 * have, ldvt, Vtt, rr, rr, n)) return rc;
+    hipLaunchKernelGGL(split_fill_kernel, dim3(256), dim3(256), 0, st, Ut, (int64_t)2 * m * rr, 0x5eedu);    // (Ut is copied out by now)
+    if (int rc = cx_copy2d(c, (double*)U + (size_t)2 * have * ldu, ldu, Ut, m, m, rr)) return rc;
+    HIPCHK(hipMemsetAsync((double*)S + have, 0, sizeof(double) * rr, st));
+  }
+  // the complement condition and the isometry, by construction
+  for (int round = 0; round < 2; ++round) {
+    if (pl > 0) {
+      if (int rc = gemm_c128(c, 1, 0, pl, kk, m, 1.0, QL, ldql, U, ldu, 0.0, TP, pl)) return rc;
+      if (int rc = gemm_c128(c, 0, 0, m, kk, pl, -1.0, QL, ldql, TP, pl, 1.0, U, ldu)) return rc;
+    }
+    if (int rc = qrpos_c128(c, m, kk, U, ldu, Ut, m, Rt, kk)) return rc;
+    if (int rc = cx_copy2d(c, U, ldu, Ut, m, m, kk)) return rc;
+    if (pr > 0) {
+      if (int rc = gemm_c128(c, 0, 1, kk, pr, n, 1.0, Vt, ldvt, QR, ldqr, 0.0, TP, kk)) return rc;
+      if (int rc = gemm_c128(c, 0, 0, kk, n, pr, -1.0, TP, kk, QR, ldqr, 1.0, Vt, ldvt)) return rc;
+    }
+    if (int rc = lqpos_c128(c, kk, n, Vt, ldvt, Rt, kk, Vtt, kk)) return rc;
+    if (int rc = cx_copy2d(c, Vt, ldvt, Vtt, kk, kk, n)) return rc;
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return MPSK_OK;
+}
+
 // mpsk_complement_tsvd: the k leading singular triplets of X = (1 - QL QL^T) Y (1 - QR^T QR) without null-space bases
 // (NL NL' = 1 - AL AL', NR' NR = 1 - AR' AR in optimalexpand.jl:22-29).  X is formed with four thin GEMMs; the triplets come
 // from the checked subspace iteration of the truncated split (tsplit_f64: X ~ A C B, kept subspace verified against X
@@ -1215,7 +1414,6 @@ int mpsk_ctx_split_stats(mpsk_ctx* c, int* path, int* iterations, double* residu
 int mpsk_complement_tsvd(mpsk_ctx* c, int m, int n, const void* Y, int ldy, const void* QL, int ldql, int pl, const void* QR,
                          int ldqr, int pr, int k, void* U, int ldu, void* S, void* Vt, int ldvt, int* kept) {
   REQUIRE(c && Y && kept, "NULL argument");
-  REQUIRE(c->dtype == MPSK_F64, "MPSK_F64 only");
   REQUIRE(m > 0 && n > 0 && ldy >= m && k >= 0, "bad dimensions");
   REQUIRE(pl >= 0 && pl <= m && pr >= 0 && pr <= n, "pl / pr out of range");
   REQUIRE((pl == 0 || (QL && ldql >= m)) && (pr == 0 || (QR && ldqr >= pr)), "QL / QR missing or leading dimension too small");
@@ -1225,6 +1423,7 @@ int mpsk_complement_tsvd(mpsk_ctx* c, int m, int n, const void* Y, int ldy, cons
   REQUIRE(U && S && Vt && ldu >= m && ldvt >= kk, "U / S / Vt missing or leading dimension too small");
   REQUIRE(!c->pend.active && !c->on_side, "not accepted inside a side-stream section / with a deferred factorization pending");
   HIPCHK(hipSetDevice(c->device));
+  if (c->dtype == MPSK_C128) return complement_tsvd_c128(c, m, n, Y, ldy, QL, ldql, pl, QR, ldqr, pr, kk, U, ldu, S, Vt, ldvt);
   const auto ev = [](size_t v) { return (v + 1) & ~(size_t)1; };
   const int nn = std::min(m, n);
   const bool small = nn <= 64;

@@ -1510,3 +1510,183 @@ def _refuse_inf_alg(alg, what):
         _refuse_inf_alg(alg.alg2, what)
     if isinstance(alg, (GradientGrassmann, IDMRG1, IDMRG2)):
         raise NotImplementedError(f"{what} on a NativeInfiniteMPS: {type(alg).__name__} is not implemented (VUMPS only)")
+
+
+# ---- changebonds on interleaved storage (changebonds/optimalexpand.jl:16-67, randexpand.jl:15-34, svdcut.jl:35-46,
+# changebonds.jl:13-38): changebonds._changebonds_infinite with complex operands.  An interleaved tensor (2 Dl, d, Dr) is a real
+# tensor whose first dimension is doubled, so the layout helpers of changebonds.py (_tail_matrix, _from_tail_matrix, _pad_site)
+# serve on doubled row counts as they are ----
+
+# route of the expansion directions when the caller does not force one, above changebonds.DEVICE_ROUTE_MIN: mpsk_complement_tsvd
+# under MPSK_C128 wherever the backend has it (profiles/expand_native_timings.json)
+EXPAND_DEVICE_DEFAULT = True
+
+
+def _expand_route(be, m, n, route):
+    from .changebonds import DEVICE_ROUTE_MIN
+    has = hasattr(be, "complement_tsvd_c")
+    if route is None:
+        return has and EXPAND_DEVICE_DEFAULT and min(m, n) > DEVICE_ROUTE_MIN
+    if route not in ("device", "composed"):
+        raise ValueError(f"route must be None, 'device' or 'composed', not {route!r}")
+    if route == "device" and not has:
+        from ._lib import MpskError
+        raise MpskError("route='device': this backend has no complement_tsvd_c")
+    return route == "device"
+
+
+def _gauss_c(be, rng, r, c):
+    return be.upload_c(rng.standard_normal((r, c)) + 1j * rng.standard_normal((r, c)))
+
+
+def _complement_cols_c(be, Q: DTensor, rng):
+    """orthonormal basis N (m x (m - p)) of the complement of the orthonormal columns of Q (m x p): QRpos of a projected
+    Gaussian block, projected twice (changebonds._complement_cols on complex tensors)"""
+    m, p = Q.shape[0] // 2, Q.shape[1]
+    if m == p:
+        return None
+    Y = _gauss_c(be, rng, m, m - p)
+    for _ in range(2):
+        be.gemm_c(Q, be.gemm_c(Q, Y, transA=True), alpha=-1.0, beta=1.0, out=Y)
+        Y, _ = be.qrpos_c(Y)
+    return Y
+
+
+def _complement_rows_c(be, B: DTensor, rng):
+    """orthonormal rows N ((n - p) x n) spanning the complement of the orthonormal rows of B (p x n)"""
+    p, n = B.shape[0] // 2, B.shape[1]
+    if p == n:
+        return None
+    Y = _gauss_c(be, rng, n - p, n)
+    for _ in range(2):
+        be.gemm_c(be.gemm_c(Y, B, transB=True), B, alpha=-1.0, beta=1.0, out=Y)
+        _, Y = be.lqpos_c(Y)
+    return Y
+
+
+def _complement_directions_c(be, Y, QL, Bm, k, rng, dev):
+    """the k leading singular vectors of NL^dag Y NR^dag lifted back (optimalexpand.jl:25-32): U (m x kept), Vt (kept x n) and
+    the singular values on the host.  dev: mpsk_complement_tsvd under MPSK_C128; otherwise the literal algorithm."""
+    n = Y.shape[1]
+    if dev:
+        U, S, Vt, kept = be.complement_tsvd_c(Y, QL, Bm, k)
+        if kept == 0:
+            return None, None, np.zeros(0), 0
+        return U, Vt, be.download(S), kept
+    NL, NR = _complement_cols_c(be, QL, rng), _complement_rows_c(be, Bm, rng)
+    if NL is None or NR is None:
+        return None, None, np.zeros(0), 0
+    nl, nr = NL.shape[1], NR.shape[0] // 2
+    inter = be.gemm_c(be.gemm_c(NL, Y, transA=True), NR, transB=True)          # nl x nr
+    Uk, S, Vh, kept, _ = be.tsvd_c(inter, max_keep=min(k, nl, nr))
+    kmax = Vh.shape[0] // 2
+    Vk = be.empty(2 * kept, nr)
+    be.copy2d(2 * kept, nr, Vh.ptr, 2 * kmax, Vk.ptr, 2 * kept)
+    U = be.gemm_c(NL, DTensor(Uk.buf, (2 * nl, kept)))
+    Vt = be.gemm_c(Vk, NR)
+    return U, Vt, be.download(DTensor(S.buf, (kept,))), kept
+
+
+def expansion_directions(psi: NativeInfiniteMPS, H, envs, i, k, rng=None, route=None, Y=None):
+    """Expansion directions of bond i (between sites i and i + 1): (U (2 Dl d, kept), Vt (2 kept, Dr d) with (b, s) columns, S on
+    the host, kept).  Y given: that matrix instead of H_AC2 (AC_i AR_{i+1}) (RandExpand)."""
+    from .changebonds import _tail_matrix
+    be, n = psi.be, len(psi)
+    rng = np.random.default_rng(0) if rng is None else rng
+    ac, al, ar = psi.AC[i % n], psi.AL[i % n], psi.AR[(i + 1) % n]
+    Dl2, d1, Dm = ac.shape
+    _, d2, Dr = ar.shape
+    m, nn = (Dl2 // 2) * d1, Dr * d2
+    dev = _expand_route(be, m, nn, route)
+    if Y is None:
+        Y = be.dAC2_proj(envs.O(i), envs.O(i + 1), envs.leftenv(i, psi), envs.rightenv(i + 1, psi), ac, ar)
+    return _complement_directions_c(be, Y.reshape(2 * m, nn), al.reshape(2 * m, Dm), _tail_matrix(be, ar), k, rng, dev)
+
+
+def _expand(psi: NativeInfiniteMPS, Us, Vts, ks):
+    """changebonds.jl:13-38 on device tensors: AL -> [AL U; 0 0], AR -> [AR 0; Vt 0], CR -> [CR 0; 0 0], AC = AL CR.  Us[i] /
+    Vts[i] / ks[i] belong to the bond right of site i.  The result is in mixed gauge as it stands (changebonds._expand)."""
+    from .changebonds import _from_tail_matrix, _pad_site
+    be, n = psi.be, len(psi)
+    AL, AR, CR, AC = [None] * n, [None] * n, [None] * n, [None] * n
+    for i in range(n):
+        kl, kr = ks[(i - 1) % n], ks[i]
+        Dl2, d, Dr = psi.AL[i].shape
+        Dn2 = Dl2 + 2 * kl
+        al = _pad_site(be, psi.AL[i], 2 * kl, kr)
+        if kr:                                                # U[(a, s), j] -> al[a, s, Dr + j]
+            for s in range(d):
+                be.copy2d(Dl2, kr, Us[i].ptr + 8 * s * Dl2, Dl2 * d, al.ptr + 8 * (s * Dn2 + Dn2 * d * Dr), Dn2 * d)
+        ar = _pad_site(be, psi.AR[i], 2 * kl, kr)
+        if kl:                                                # Vt[j, (b, s)] -> ar[Dl + j, s, b]
+            _from_tail_matrix(be, Vts[(i - 1) % n], d, Dr, ar, Dl2)
+        c = be.zeros(2 * (Dr + kr), Dr + kr)
+        be.copy2d(2 * Dr, Dr, psi.CR[i].ptr, 2 * Dr, c.ptr, 2 * (Dr + kr))
+        AL[i], AR[i], CR[i] = al, ar, c
+    for i in range(n):
+        AC[i] = _mul_AC(be, AL[i], CR[i])
+    return NativeInfiniteMPS._of(AL, AR, CR, AC, be)
+
+
+def _expand_inf(psi: NativeInfiniteMPS, H, alg, envs, rng, route):
+    from .changebonds import RandExpand
+    n = len(psi)
+    Us, Vts, ks = [None] * n, [None] * n, [0] * n
+    for i in range(n):
+        Y = None
+        if isinstance(alg, RandExpand):                       # randexpand.jl:20: a Gaussian two-site block
+            Dl, d1, _ = psi.dims(i)
+            _, d2, Dr = psi.dims(i + 1)
+            Y = _gauss_c(psi.be, rng, Dl * d1, Dr * d2)
+        Us[i], Vts[i], _, ks[i] = expansion_directions(psi, H, envs, i, alg.trunc_dim, rng, route, Y)
+    return _expand(psi, Us, Vts, ks)
+
+
+def _svd_cut_inf(psi: NativeInfiniteMPS, alg):
+    """svdcut.jl:35-46: tsvd of every CR, AL[i] <- AL[i] U_i, AL[i+1] <- U_i^dag AL[i+1], then the gauge from the new ALs"""
+    be, n = psi.be, len(psi)
+    ALs = list(psi.AL)
+    ncr = None
+    for i in range(n):
+        c = psi.CR[i]
+        D = c.shape[1]
+        U, S, _, k, _ = be.tsvd_c(c, max_keep=alg.trunc_dim, trunc_err=alg.trunc_err)
+        Uk = DTensor(U.buf, (2 * D, k))                       # the leading columns of U (2 D, D)
+        Dl2, d, _ = ALs[i].shape
+        ALs[i] = be.gemm_c(ALs[i].reshape(Dl2 * d, D), Uk).reshape(Dl2, d, k)
+        j = (i + 1) % n
+        _, d2, Dr2 = ALs[j].shape
+        ALs[j] = be.gemm_c(Uk, ALs[j].reshape(2 * D, d2 * Dr2), transA=True).reshape(2 * k, d2, Dr2)
+        ncr = be.upload_c(np.diag(be.download(DTensor(S.buf, (k,)))).astype(np.complex128))
+    return NativeInfiniteMPS.from_AL(ALs, ncr, be=be)
+
+
+def changebonds(psi: NativeInfiniteMPS, H=None, alg=None, envs=None, rng=None, route=None):
+    """changebonds(psi, H, alg[, envs]) -> (psi', envs)  /  changebonds(psi, SvdCut(...) | RandExpand(...)) -> psi' for a
+    NativeInfiniteMPS (copying versions; changebonds.changebonds keeps refusing the class, this is its entry).  OptimalExpand:
+    H a real MPOHamiltonian or a ComplexMPOHamiltonian whose period divides the unit cell; the environments are
+    environments(psi, H) when none are passed, and the ones returned are still attached to the old state, as in the
+    reference: they recalculate themselves when they are next read with the new one.  route: None = dispatch, "device"
+    (mpsk_complement_tsvd under MPSK_C128) / "composed" (null-space bases, full SVD) = forced."""
+    from .changebonds import OptimalExpand, RandExpand, SvdCut
+    if not isinstance(psi, NativeInfiniteMPS):
+        raise TypeError(f"native_cplx.changebonds takes a NativeInfiniteMPS, not {type(psi).__name__}")
+    if isinstance(H, (OptimalExpand, SvdCut, RandExpand)) and alg is None:
+        H, alg = None, H
+    if H is not None:
+        _refuse_ham(H)
+    if not isinstance(alg, (OptimalExpand, RandExpand, SvdCut)):
+        raise TypeError(f"unknown changebonds algorithm {alg!r}")
+    rng = np.random.default_rng(0) if rng is None else rng
+    if isinstance(alg, SvdCut):
+        out = _svd_cut_inf(psi, alg)
+        return out if H is None else (out, envs)
+    if isinstance(alg, RandExpand):
+        out = _expand_inf(psi, None, alg, None, rng, route)
+        return out if H is None else (out, envs)
+    if H is None:
+        raise TypeError("OptimalExpand needs the operator: changebonds(psi, H, OptimalExpand(...)[, envs])")
+    if len(psi) % H.period != 0:
+        raise ValueError(f"unit cell of the state ({len(psi)}) is not a multiple of the Hamiltonian's period ({H.period})")
+    envs = environments(psi, H) if envs is None else envs
+    return _expand_inf(psi, H, alg, envs, rng, route), envs
